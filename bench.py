@@ -4,7 +4,7 @@ resident in HBM (BASELINE.json metric; workload = configs[2]: PE 2x150, auto-ada
 overlap + quality-trim), with the kernel's roofline position and the reference's CPU path
 timed beside it.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs B]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs B] [--dump-outputs DIR]
 
 A step = one pass of the hot path (fused kernel + slab fold + duplicate kernels) over one
 batch of B pairs already in HBM.  N > 1: launched by torch.distributed.run, one rank per GPU,
@@ -497,6 +497,42 @@ def other_configs(dev, only=None):
     return res
 
 
+DUMP_ROWS = 1 << 19      # --dump-outputs: pairs sampled from the last step's batch (16 float32 columns: 32 MiB)
+DUMP_SEED = 20261015
+
+
+def dump_outputs(out_dir, eng, B, r1, r2, pr, ncorr, dev):
+    """--dump-outputs DIR: what the timed path handed its caller after the last timed step, one DIR/<name>.npy per array
+    (float32 / float64), for comparing two builds output for output on the same inputs:
+      read1_<field>, read2_<field>  the ReadResult fields of the last step's batch (abi.ReadResult minus `reserved`),
+      pair_<field>                  its PairResult fields,
+      rows                          which pairs of the batch those are (a fixed, seeded sample of DUMP_ROWS when B is larger),
+      counters                      the counter block the run's steps left (Stats / FilterResult / Duplicate; merged if N > 1),
+      n_corrections                 the correction count of the last step."""
+    import numpy as np
+    import torch
+    from fastp_amd import abi
+    os.makedirs(out_dir, exist_ok=True)
+    rows = np.arange(B, dtype=np.int64)
+    if B > DUMP_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(B, DUMP_ROWS, replace=False))
+    sel = torch.from_numpy(rows).to(dev)
+    arrays = {"rows": rows.astype(np.float64)}
+    for prefix, buf, struct in (("read1", r1, abi.ReadResult), ("read2", r2, abi.ReadResult), ("pair", pr, abi.PairResult)):
+        rec = buf.view(B, C.sizeof(struct)).index_select(0, sel).cpu().numpy().reshape(-1).view(np.dtype(struct))
+        for f in rec.dtype.names:
+            if f != "reserved":
+                arrays[f"{prefix}_{f}"] = rec[f].astype(np.float32)
+    arrays["counters"] = eng.counters().astype(np.float64)     # counts stay far below 2^53: exact in float64
+    arrays["n_corrections"] = ncorr.cpu().numpy().astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (more than 64 MiB)")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"dumped {len(arrays)} arrays ({total} bytes) to {out_dir}")
+
+
 def log(msg):
     if os.environ.get("BENCH_VERBOSE"):
         print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
@@ -545,7 +581,11 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the end-to-end legs and the other configurations")
     ap.add_argument("--cpu-sample", type=int, default=4_000_000)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # Every FASTP_GPU_* variable of the environment is an A/B switch of the library: a bench line says which ones it ran
     # with (`config.switches`), and does not run at all with the profiling build's ablation switch - its results are meaningless.
@@ -763,6 +803,8 @@ def main():
     kms, klaunches = eng.kernel_time()
     plan = eng.plan()
     log(f"timed region done: {elapsed:.3f}s, kernel {kms:.2f} ms over {klaunches} launches")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, B, r1, r2, pr, ncorr, dev)
     if rank == 0:
         total_pairs = B * args.steps * world
         value = 2.0 * total_pairs / elapsed / 1e6

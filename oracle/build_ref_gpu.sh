@@ -56,7 +56,8 @@ echo "built $OUT/fastp_ref_gpu"
 # the patched reference end to end on small inputs
 SIM=$ROOT/tests/hostsim/libfastp_gpu_sim.so
 if [ -f "$SIM" ]; then
-    $CXX -pthread "$OBJ"/*.o -o "$OUT/fastp_ref_gpusim.tmp.$$" "$DEFLATE" -lz -lpthread "$SIM" -Wl,-rpath,"$ROOT/tests/hostsim"
+    $CXX -pthread "$OBJ"/*.o -o "$OUT/fastp_ref_gpusim.tmp.$$" "$DEFLATE" -lz -lpthread \
+        -L"$ROOT/tests/hostsim" -Wl,-rpath,'$ORIGIN/../../tests/hostsim' -lfastp_gpu_sim
     mv -f "$OUT/fastp_ref_gpusim.tmp.$$" "$OUT/fastp_ref_gpusim"
     echo "built $OUT/fastp_ref_gpusim"
 fi

@@ -66,13 +66,15 @@ _BUILT = False
 
 def _ensure_built():
     global _BUILT
+    import engines
     if not _BUILT and os.path.isdir("/root/reference/src"):
         import __graft_entry__ as g
-        import engines
         engines.build_sim()     # the emulator build of the engine, which fastp_ref_gpusim links
         g.build()               # libfastp_gpu.so, fastp_ref, fastp_ref_gpu (+ fastp_ref_gpusim now that the emulator exists)
         subprocess.check_call([os.path.join(ROOT, "oracle", "build_ref_gpu.sh")], stdout=subprocess.DEVNULL)
         _BUILT = True
+    elif os.path.exists(REF_SIM):
+        engines.build_sim()     # oracle/_ref/ was built in another tree: the emulator library it links is this tree's own
     return os.path.exists(REF)
 
 
