@@ -264,6 +264,7 @@ struct fastp_gpu_ctx {
     fastp_gpu_counter_layout cl;
     int device = 0;
     int cus = 0;
+    int lds_bytes = 0;       // the device's LDS per workgroup (hipDeviceProp_t::sharedMemPerBlock): every LDS decision uses it
     int blocks = 0;           // persistent workgroups per launch
     int max_pairs_per_launch = 0;
     // split plan (fq_stats.h): the per-read kernel as small workgroups, Stats::statRead as its own streaming kernel
@@ -473,8 +474,8 @@ static int stats5_copies(const DevParams& p, int lds_bytes, int* hb_out = nullpt
     }
     return 0;
 }
-static bool lane_plan_supported(const DevParams& p, const HostLuts& luts) {
-    if (p.front_per_read && !stats5_copies(p, 160 * 1024)) return false;   // a front per read: form 5 of the Stats kernel only
+static bool lane_plan_supported(const DevParams& p, const HostLuts& luts, int lds_bytes) {
+    if (p.front_per_read && !stats5_copies(p, lds_bytes)) return false;   // a front per read: form 5 of the Stats kernel only
     if (!(p.stats_one_pass || p.front_lane || p.corr_lane || p.merge_lane) || p.allow_gap || p.overlapped_out) return false;
     if (p.n_fasta && p.fasta_max_len > 64) return false;   // (--adapter_fasta: each sequence like -a, in four uniform words)
     if (p.merge && !p.merge_lane) return false;
@@ -485,6 +486,9 @@ static bool lane_plan_supported(const DevParams& p, const HostLuts& luts) {
     if (p.dup_enabled && !(luts.dup_nq > 0 && (p.dup_bufnum == 2 || p.dup_bufnum == 4) && p.dup_npl == 3)) return false;
     return true;
 }
+
+// the dynamic LDS the overrepresentation count and text kernels may take (they size their tables to it at each launch)
+static int aux_lds_cap(const fastp_gpu_ctx* ctx) { return std::min(150 * 1024, ctx->lds_bytes); }
 
 typedef void (*lane_kernel_fn)(LaneArgs);
 template <int EXT>
@@ -556,18 +560,21 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
     he = hipGetDeviceProperties(&prop, device);
     if (he != hipSuccess) { delete ctx; return fail(nullptr, FASTP_GPU_E_HIP, "hipGetDeviceProperties failed"); }
     ctx->cus = prop.multiProcessorCount;
+    ctx->lds_bytes = (int)std::min<size_t>(prop.sharedMemPerBlock, (size_t)1 << 30);
+    const int lds_max = ctx->lds_bytes;
     // tile / launch geometry (tunable without a rebuild)
-    const int lds_kb_default = (int)(prop.sharedMemPerBlock / 1024) >= 160 ? 160 : (int)(prop.sharedMemPerBlock / 1024);
+    const int lds_kb_default = lds_max / 1024 >= 160 ? 160 : lds_max / 1024;
     // The split plan (per-read kernel as 256-lane workgroups, several per CU, + the streaming Stats kernel) whenever no
     // option moves or edits a kept base; FASTP_GPU_SPLIT=0 keeps Stats inside the one-workgroup-per-CU fused kernel.
     // the Stats kernel as its own launch: options that leave every kept base where it was, or (lane plan only) move it by the
     // same front for every read that is written out (DevParams::front_lane)
-    const bool lane_wanted = env_int("FASTP_GPU_LANE", 1) != 0 && lane_plan_supported(ctx->dp, ctx->luts);
+    const bool lane_wanted = env_int("FASTP_GPU_LANE", 1) != 0 && lane_plan_supported(ctx->dp, ctx->luts, lds_max);
     ctx->split = (ctx->dp.stats_one_pass || ((ctx->dp.front_lane || ctx->dp.corr_lane || ctx->dp.merge_lane) && lane_wanted)) && env_int("FASTP_GPU_SPLIT", 1) != 0;
     ctx->cfg.split = ctx->split ? 1 : 0;
     ctx->cfg.threads = env_int("FASTP_GPU_THREADS", ctx->split ? 256 : 1024);
     ctx->cfg.P = env_int("FASTP_GPU_TILE", 0);
-    ctx->cfg.lds_budget = env_int("FASTP_GPU_LDS_KB", ctx->split ? std::min(40, lds_kb_default) : lds_kb_default) * 1024;
+    // (FASTP_GPU_LDS_KB above what the device has is clamped to it: a budget the card cannot give would only fail the launch)
+    ctx->cfg.lds_budget = std::min(env_int("FASTP_GPU_LDS_KB", ctx->split ? std::min(40, lds_kb_default) : lds_kb_default), lds_max / 1024) * 1024;
     // two tiles in flight per workgroup (each half of the waves owns one) when the halves are whole wavefronts
     ctx->cfg.halves = (env_int("FASTP_GPU_HALVES", 1) == 2 && ctx->cfg.threads % 128 == 0) ? 2 : 1;
     if (ctx->cfg.threads < 64 || ctx->cfg.threads > 1024 || (ctx->cfg.threads & 63)) {
@@ -588,7 +595,7 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
         rc = compute_lds_layout(ctx->dp, ctx->cfg, ctx->L, err, ctx->luts.dup_nq);
     }
     if (rc) { delete ctx; return fail(nullptr, rc, err); }
-    int blocks_per_cu = env_int("FASTP_GPU_BLOCKS_PER_CU", std::max(1, (int)((160 * 1024) / (ctx->L.total * 4))));
+    int blocks_per_cu = env_int("FASTP_GPU_BLOCKS_PER_CU", std::max(1, (int)(lds_max / (ctx->L.total * 4))));
     blocks_per_cu = std::max(1, std::min(blocks_per_cu, 2048 / ctx->cfg.threads));   // 32 wavefronts per CU
 #ifndef FQ_HOSTSIM
     if (!getenv("FASTP_GPU_BLOCKS_PER_CU")) {
@@ -619,7 +626,7 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
             // fits one workgroup's LDS (reads of up to 176 bases; merge mode's third pass exists in form 4 only)
             ctx->st_H16 = (ctx->dp.qw_g + 3) / 4;
             int hb = 0;
-            const int kc = stats5_copies(ctx->dp, (int)prop.sharedMemPerBlock, &hb);
+            const int kc = stats5_copies(ctx->dp, lds_max, &hb);
             if (kc) {
                 int o = 0;
                 ctx->st_l_cyc = o; o += 2 * 8 * 4 * ST5_QN * hb;
@@ -654,7 +661,7 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
                 ctx->st_l_mt = o; o += 18 + 2;
                 ctx->st_l_wl = o; o += 1 + ctx->st_wl_cap;
                 ctx->st_lds_dwords = o;
-                if (2 * o * 4 <= 160 * 1024) break;                       // two workgroups per CU
+                if (2 * o * 4 <= lds_max) break;                          // two workgroups per CU
                 if (ctx->st_Hs > ctx->st_H) ctx->st_Hs = ctx->st_H;       // first the padding,
                 else if (ctx->st_kc > 1) ctx->st_kc /= 2;                 // then the copies
                 else break;
@@ -667,7 +674,7 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
         ctx->st_wl_cap = ctx->st_Hs > ctx->st_H ? 511 : 2047;
         for (;;) {
             const int bytes = (4 * 8 * N_CLS * ctx->st_Hs * 2 + 4 * KMER_BINS + ST_QH_COPIES * 4 * 128 + 4 * 256 + 20 + 1 + ctx->st_wl_cap + 3) * 4;
-            if (ctx->st_Hs == ctx->st_H || 2 * bytes <= 160 * 1024) break;
+            if (ctx->st_Hs == ctx->st_H || 2 * bytes <= lds_max) break;
             ctx->st_Hs = ctx->st_H;
             ctx->st_wl_cap = 2047;
         }
@@ -684,11 +691,11 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
         ctx->st_slab_dwords = 4 * ctx->L.Cp * N_CLS * 2 + 4 * KMER_BINS + 4 * 128;
         ctx->st_threads = env_int("FASTP_GPU_STATS_THREADS", 1024);
         if (ctx->st_threads < 64 || ctx->st_threads > 1024 || (ctx->st_threads & 63) || ctx->st_form == 5) ctx->st_threads = 1024;
-        if (ctx->st_lds_dwords * 4 > (int)prop.sharedMemPerBlock) { delete ctx; return fail(nullptr, FASTP_GPU_E_INVALID, "reads too long for the Stats kernel's LDS"); }
-        int st_per_cu = std::min(2048 / ctx->st_threads, (int)((160 * 1024) / (ctx->st_lds_dwords * 4)));
+        if (ctx->st_lds_dwords * 4 > lds_max) { delete ctx; return fail(nullptr, FASTP_GPU_E_INVALID, "reads too long for the Stats kernel's LDS"); }
+        int st_per_cu = std::min(2048 / ctx->st_threads, lds_max / (ctx->st_lds_dwords * 4));
         st_per_cu = env_int("FASTP_GPU_STATS_BLOCKS_PER_CU", std::max(1, st_per_cu));
         ctx->st_blocks = ctx->cus * std::max(1, st_per_cu);
-        ctx->lane = env_int("FASTP_GPU_LANE", 1) != 0 && lane_plan_supported(ctx->dp, ctx->luts);
+        ctx->lane = env_int("FASTP_GPU_LANE", 1) != 0 && lane_plan_supported(ctx->dp, ctx->luts, lds_max);
         ctx->ln_glds = env_int("FASTP_GPU_LANE_GLDS", 0);
         ctx->ln_prefetch = env_int("FASTP_GPU_LANE_PREFETCH", 0);
         ctx->ln_grab = env_int("FASTP_GPU_LANE_GRAB", 4);   // (1.400 -> 1.350 ms per 4 Mi pairs, profiles/r06_d_lane_grab_prefetch_ab.txt)
@@ -720,7 +727,10 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
             ctx->ln_2w = ctx->ln_swm == 10 && ctx->dp.paired && lane_ext(ctx->dp) >= 2 && env_int("FASTP_GPU_LANE_EXT_WAVES", 3) == 2;
             const int max_waves = (ctx->ln_swm > 10 || ctx->ln_2w ? 512 : 256 * FQ_LANE_WAVES) / 64;
             l.clist_dwords = (ctx->dp.corr_lane && ctx->dp.paired) ? (ctx->ln_swm / 2) * 64 : 0;   // -c: read 1's edited positions, a bit mask per lane
-            int waves = (int)(((long long)prop.sharedMemPerBlock / 4 - o) / (l.stage_dwords + l.part_dwords + l.clist_dwords));
+            // the workgroup's chunk counter and the prefetch sink (l.ctr, l.sink below) come out of the LDS before it is divided
+            // into wavefronts (o and every per-wavefront size are multiples of 4 dwords: no padding in front of l.ctr)
+            const int tail_dwords = 4 + 64;
+            int waves = (int)(((long long)lds_max / 4 - o - tail_dwords) / (l.stage_dwords + l.part_dwords + l.clist_dwords));
             waves = std::max(1, std::min(waves, max_waves));
             const int env_threads = env_int("FASTP_GPU_LANE_THREADS", 0);   // A/B: 256 = round 3's geometry (several workgroups per CU)
             if (env_threads >= 64 && env_threads <= max_waves * 64) waves = env_threads / 64;
@@ -749,6 +759,30 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
             if (per_cu <= 0) per_cu = 4;
             ctx->ln_blocks = ctx->cus * per_cu;
         }
+    }
+    // --cut_front on the lane plan (a front per read) has its POST Stats only in form 5 of the Stats kernel
+    if (ctx->lane && ctx->dp.front_per_read && ctx->st_form != 5) {
+        delete ctx;
+        return fail(nullptr, FASTP_GPU_E_INVALID, "a front per read on the lane plan needs form 5 of the Stats kernel, which was not chosen");
+    }
+    {   // every kernel's dynamic LDS against what the device gives a workgroup: a layout that does not fit fails here, never at a launch
+        const char* name = ctx->split ? (ctx->cfg.threads > 256 ? "scan_wide kernel" : "scan kernel") : "fused kernel";
+        std::vector<std::pair<const char*, long long>> need = {{name, (long long)ctx->L.total * 4}, {"hash kernel", (long long)ctx->L.total * 4},
+                                                               {"text kernel", (long long)TEXT_WAVES * text_wave_bytes((ctx->dp.max_len + 8 + 7) & ~7)},
+                                                               {"deflate kernel", (long long)sizeof(DefLds)},
+                                                               {"inflate kernel", (long long)(INF_ENTRIES * INF_LANES * 2 + INF_SBUF * INF_LANES * 4)}};
+        if (ctx->split) need.push_back({ctx->st_form == 5 ? "Stats kernel (form 5)" : "Stats kernel", (long long)ctx->st_lds_dwords * 4});
+        if (ctx->lane) need.push_back({"lane kernel", (long long)ctx->ln_lds.total * 4});
+        if (ctx->split && ctx->dp.front_per_read) need.push_back({"front Stats kernel", (long long)(ctx->dp.paired ? 2 : 1) * 34 * ctx->dp.cycles * 4});
+        if (ctx->split && ctx->dp.corr_lane)
+            need.push_back({"correction Stats kernel", (long long)(ctx->dp.paired ? 2 : 1) * (33 * ctx->dp.cycles + 128 + KMER_BINS) * 4});
+        for (const auto& k : need)
+            if (k.second > lds_max) {
+                const std::string m = std::string(k.first) + ": " + std::to_string(k.second) + " bytes of LDS per workgroup, the device has " +
+                                      std::to_string(lds_max);
+                delete ctx;
+                return fail(nullptr, FASTP_GPU_E_INVALID, m);
+            }
     }
     auto set_launch_size = [&]() {
         long long mp = (long long)ctx->blocks * tiles_per_block * ctx->L.P;
@@ -916,10 +950,11 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
                                                hipFuncAttributeMaxDynamicSharedMemorySize, ctx->ln_lds.total * 4));
         }
     }
-    CREATE_TRY(hipFuncSetAttribute((const void*)fq_ovr_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    CREATE_TRY(hipFuncSetAttribute((const void*)fq_text_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    CREATE_TRY(hipFuncSetAttribute((const void*)fq_ovr_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, aux_lds_cap(ctx)));
+    CREATE_TRY(hipFuncSetAttribute((const void*)fq_text_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, aux_lds_cap(ctx)));
     CREATE_TRY(hipFuncSetAttribute((const void*)fq_deflate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(DefLds)));
-    CREATE_TRY(hipFuncSetAttribute((const void*)fq_inflate_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(IwLds)));
+    if ((int)sizeof(IwLds) <= ctx->lds_bytes)   // (a card with less LDS inflates with the lane kernel only)
+        CREATE_TRY(hipFuncSetAttribute((const void*)fq_inflate_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(IwLds)));
     CREATE_TRY(hipFuncSetAttribute((const void*)fq_inflate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    INF_ENTRIES * INF_LANES * 2 + INF_SBUF * INF_LANES * 4));
     fq::timeline("create: kernel attributes set");
@@ -1122,11 +1157,11 @@ static int launch_overrep(fastp_gpu_ctx* ctx, const KernelArgs& a, int n, hipStr
             const int longest = ctx->dp.max_len * (ctx->dp.merge ? 2 : 1);
             int lds_bytes = (((longest + 4) * OVR_SYM_STRIDE + 15) / 16) * 16;   // (+ 4 rows: a trip's four slides read unguarded)
             o.sym_cap = longest;
-            if (lds_bytes > 120 * 1024) { o.sym_cap = 0; lds_bytes = 0; }   // reads too long to stage: the global path
+            if (lds_bytes > std::min(120 * 1024, aux_lds_cap(ctx))) { o.sym_cap = 0; lds_bytes = 0; }   // reads too long to stage: the global path
             for (int m = 0; m < 2; m++) {
                 const size_t tb = ctx->luts.ovr_table[m].size() * 4;
                 o.table_lds[m] = -1;
-                if (o.mate[m].n_seeds > 0 && tb > 0 && lds_bytes + (int)tb <= 150 * 1024) {
+                if (o.mate[m].n_seeds > 0 && tb > 0 && lds_bytes + (int)tb <= aux_lds_cap(ctx)) {
                     o.table_lds[m] = lds_bytes / 4;
                     lds_bytes += (int)tb;
                 }
@@ -1395,7 +1430,7 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
         const size_t text_bytes = (size_t)TEXT_WAVES * text_wave_bytes(e.ML);
         const int slot_dwords = 34 * (int)c.cycles + 1024 + 128;
         const int slots = !ctx->dp.paired ? 2 : ctx->dp.merge ? 3 : 4;   // the Stats objects a unit can reach
-        const bool lds_tables = !hash_only && (size_t)slots * slot_dwords * 4 + text_bytes <= (size_t)150 * 1024 && env_int("FASTP_GPU_EXACT_LDS", 1);
+        const bool lds_tables = !hash_only && (size_t)slots * slot_dwords * 4 + text_bytes <= (size_t)aux_lds_cap(ctx) && env_int("FASTP_GPU_EXACT_LDS", 1);
         e.lds_slot_dwords = lds_tables ? slot_dwords : 0;
         e.lds_slots = lds_tables ? slots : 0;
         const int blocks = std::max(1, std::min((e.x_count + TEXT_WAVES - 1) / TEXT_WAVES, env_int("FASTP_GPU_EXACT_BLOCKS", ctx->cus)));
@@ -2254,12 +2289,14 @@ extern "C" int fastp_gpu_inflate_bgzf(fastp_gpu_ctx* ctx, const uint8_t* comp, i
     // 6144 blocks; beyond that blocks in flight decide and one lane per block (fq_inflate.h: ~50 ms per launch, 64 blocks
     // per wavefront) overtakes it (profiles/r02l_inflate.txt).  FASTP_GPU_INFLATE=lane|wave forces one.
     const char* how = getenv("FASTP_GPU_INFLATE");
-    const bool lane_kernel = how ? !strcmp(how, "lane") : n_blocks > 6144;
+    const bool wave_fits = (int)sizeof(IwLds) <= ctx->lds_bytes;
+    if (how && !strcmp(how, "wave") && !wave_fits) return fail(ctx, FASTP_GPU_E_INVALID, "FASTP_GPU_INFLATE=wave: the wave kernel's LDS does not fit this device");
+    const bool lane_kernel = how ? !strcmp(how, "lane") || !wave_fits : n_blocks > 6144 || !wave_fits;
     if (lane_kernel) {
         const int lds_bytes = INF_ENTRIES * INF_LANES * 2 + INF_SBUF * INF_LANES * 4;
         hipLaunchKernelGGL(fq_inflate_kernel, dim3((n_blocks + INF_LANES - 1) / INF_LANES), dim3(INF_LANES), lds_bytes, st, a);
     } else {
-        const int per_cu = std::max(1, (160 * 1024) / (int)sizeof(IwLds));
+        const int per_cu = std::max(1, ctx->lds_bytes / (int)sizeof(IwLds));
         hipLaunchKernelGGL(fq_inflate_wave_kernel, dim3(std::min(n_blocks, ctx->cus * per_cu)), dim3(64), sizeof(IwLds), st, a);
     }
     HIP_TRY(ctx, hipGetLastError());
@@ -2635,7 +2672,7 @@ extern "C" int fastp_gpu_deflate_bgzf(fastp_gpu_ctx* ctx, const uint8_t* text, i
         a.out = out;
         a.out_base = written;
         a.out_cap = (u64)out_capacity;
-        const int grid = std::min(a.nblocks, ctx->cus * std::max(1, (160 * 1024) / (int)sizeof(DefLds)));
+        const int grid = std::min(a.nblocks, ctx->cus * std::max(1, ctx->lds_bytes / (int)sizeof(DefLds)));
         hipLaunchKernelGGL(fq_deflate_kernel, dim3(grid), dim3(64), sizeof(DefLds), st, a);
         HIP_TRY(ctx, hipGetLastError());
         hipLaunchKernelGGL(fq_deflate_scan_kernel, dim3(1), dim3(1024), 1024 * 8, st, a);

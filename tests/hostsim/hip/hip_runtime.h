@@ -145,7 +145,7 @@ template <class T> static inline bool __hip_atomic_compare_exchange_strong(T* p,
 
 // ---- the sliver of the HIP runtime API that fastp_gpu.hip calls -------------------
 typedef int hipError_t;
-enum { hipSuccess = 0, hipErrorNotReady = 600, hipErrorUnknown = 999 };
+enum { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorNotReady = 600, hipErrorUnknown = 999 };
 typedef struct sim_stream* hipStream_t;
 typedef struct sim_event* hipEvent_t;
 enum { hipStreamNonBlocking = 1 };
@@ -155,7 +155,7 @@ struct hipDeviceProp_t {
     int multiProcessorCount;
     size_t sharedMemPerBlock;
 };
-static inline const char* hipGetErrorString(hipError_t) { return "hostsim error"; }
+const char* hipGetErrorString(hipError_t e);   // (the text of the emulator's last error: what a failed launch asked for)
 enum { hipEventDisableTiming = 2 };
 hipError_t hipGetDeviceCount(int* n);
 hipError_t hipSetDevice(int);
@@ -184,6 +184,7 @@ hipError_t hipEventSynchronize(hipEvent_t e);
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b);
 hipError_t hipFuncSetAttribute(const void* f, hipFuncAttribute a, int v);
 hipError_t hipGetLastError();
+hipError_t hipPeekAtLastError();
 inline hipError_t hipMemGetInfo(size_t* free_bytes, size_t* total_bytes) { *free_bytes = (size_t)8 << 30; *total_bytes = (size_t)16 << 30; return hipSuccess; }   // (a small card: the emulator keeps the small lists)
 
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \

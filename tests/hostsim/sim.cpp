@@ -16,6 +16,23 @@
 // the dynamic LDS of the block being emulated (`extern __shared__ u32 fq_lds[]` in the kernel)
 alignas(16) uint32_t fq_lds[(160 * 1024) / 4 + 64];
 
+// The emulated device's LDS per workgroup (hipDeviceProp_t::sharedMemPerBlock): the MI355X's 160 KiB unless
+// FASTP_SIM_LDS_BYTES asks for less (tests of the create-time sizing on a smaller card).  A launch, or a
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize), above it fails the way the runtime fails it: no body runs, and the
+// error stays until hipGetLastError takes it.
+// (read at every call: a test sets it with monkeypatch around the engines it creates)
+static size_t sim_lds_limit() {
+    const char* v = getenv("FASTP_SIM_LDS_BYTES");
+    const long long n = (v && *v) ? atoll(v) : 0;
+    return (n > 0 && (size_t)n < (size_t)160 * 1024) ? (size_t)n : (size_t)160 * 1024;
+}
+static thread_local hipError_t sim_last_error = hipSuccess;
+static thread_local char sim_last_error_text[256] = "";
+static void sim_set_error(hipError_t e, const char* text) {
+    sim_last_error = e;
+    snprintf(sim_last_error_text, sizeof(sim_last_error_text), "%s", text);
+}
+
 namespace sim {
 
 enum Wait { RUN = 0, AT_BLOCK = 1, AT_WAVE_BARRIER = 2, AT_BALLOT = 3, AT_SHFL = 4, AT_SHFL_XOR = 5, DONE = 6, AT_GROUP = 7 };
@@ -169,9 +186,15 @@ static void run_block(std::vector<ThreadState>& th) {
 void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()>& body) {
     // one launch at a time: the emulator's state (coroutine pool, LDS, indices) is global, and host code may drive two
     // contexts from two threads (the two ranks of tests/test_comm_stub.py, the stream loop's reader beside its caller)
+    if (shmem > sim_lds_limit()) {
+        char m[160];
+        snprintf(m, sizeof(m), "launch over the LDS limit: %zu bytes of dynamic LDS requested, the device has %zu per workgroup",
+                 shmem, sim_lds_limit());
+        sim_set_error(hipErrorInvalidValue, m);
+        return;
+    }
     static std::mutex launch_mu;
     std::lock_guard<std::mutex> launch_lock(launch_mu);
-    if (shmem > sizeof(fq_lds)) die("dynamic LDS request exceeds 160 KiB");
     static std::vector<ThreadState> pool;
     const int T = (int)block.x;
     while ((int)pool.size() < T) {
@@ -208,7 +231,7 @@ hipError_t hipSetDevice(int) { return hipSuccess; }
 hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) {
     const char* cu = getenv("FASTP_SIM_CUS");
     p->multiProcessorCount = cu ? atoi(cu) : 3;  // few "CUs" -> the grid-stride loop is exercised
-    p->sharedMemPerBlock = 160 * 1024;
+    p->sharedMemPerBlock = sim_lds_limit();
     return hipSuccess;
 }
 hipError_t hipMalloc(void** p, size_t bytes) {
@@ -259,5 +282,22 @@ hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
     *ms = std::chrono::duration<float, std::milli>(b->t - a->t).count();
     return hipSuccess;
 }
-hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
-hipError_t hipGetLastError() { return hipSuccess; }
+hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute a, int v) {
+    if (a == hipFuncAttributeMaxDynamicSharedMemorySize && (v < 0 || (size_t)v > sim_lds_limit())) {
+        char m[160];
+        snprintf(m, sizeof(m), "hipFuncSetAttribute: MaxDynamicSharedMemorySize %d bytes is over the device's %zu", v, sim_lds_limit());
+        sim_set_error(hipErrorInvalidValue, m);
+        return hipErrorInvalidValue;
+    }
+    return hipSuccess;
+}
+hipError_t hipGetLastError() {
+    const hipError_t e = sim_last_error;
+    sim_last_error = hipSuccess;
+    return e;
+}
+hipError_t hipPeekAtLastError() { return sim_last_error; }
+const char* hipGetErrorString(hipError_t e) {
+    if (e == hipSuccess) return "no error";
+    return sim_last_error_text[0] ? sim_last_error_text : "hostsim error";
+}

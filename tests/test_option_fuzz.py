@@ -12,10 +12,12 @@ import synth
 from fastp_amd import abi, engine, hostloop
 
 
-def random_case(seed):
+def random_case(seed, L_override=None):
     rng = np.random.default_rng(1000 + seed)
     paired = bool(rng.random() < 0.7)
     L = int(rng.choice([50, 76, 100, 150, 151, 250]))
+    if L_override is not None:   # (after the draw: every later draw stays what the seed gave)
+        L = L_override
     p = abi.default_params(paired, L)
     pick = lambda pr: bool(rng.random() < pr)
     if pick(0.3):
@@ -100,8 +102,28 @@ def random_case(seed):
     return p, d, paired
 
 
-def _check(mk_engine, seed):
-    p, d, paired = random_case(seed)
+# the launch geometry's thresholds (tests/test_launch_geometry.py): both sides of the seq-stride steps, the lane kernel's SWM 10 -> 16,
+# Stats form 5's column blocks, four bloom buffers' byte planes (202 / 203), the lane plan's limit; the lane layouts that overflowed
+EDGE_LENGTHS = [32, 33, 64, 65, 96, 97, 128, 129, 141, 142, 144, 150, 152, 160, 161, 176, 177, 202, 203, 256, 257]
+EDGE_ISIZES = [0, 1, 100, 511, 512, 1000, 2379, 4095, 4096]
+
+
+def random_edge_case(seed):
+    """random_case's option set and reads at a threshold length, with insert_size_max and the dup accuracy level (1 - 6) drawn
+    as well - a generator of its own, so that random_case's seeds keep their cases"""
+    rng = np.random.default_rng(50_000 + seed)
+    L = int(rng.choice(EDGE_LENGTHS))
+    isize = int(rng.choice(EDGE_ISIZES)) if rng.random() < 0.7 else int(rng.integers(2, 4095))
+    level = int(rng.integers(1, 7))
+    p, d, paired = random_case(seed, L_override=L)
+    p.insert_size_max = isize
+    if p.dup_enabled:
+        p.dup_accuracy_level = level
+    return p, d, paired
+
+
+def _check(mk_engine, seed, gen=random_case):
+    p, d, paired = gen(seed)
     args = (d["seq1"], d["qual1"], d["len1"]) + ((d["seq2"], d["qual2"], d["len2"]) if paired else ())
     o = oraclelib.Oracle(p)
     try:
@@ -135,3 +157,15 @@ def test_sim_random_option_sets_equal_oracle(seed):
 @pytest.mark.parametrize("seed", range(40, 85))
 def test_gpu_random_option_sets_equal_oracle(seed):
     _check(engines.gpu_engine, seed)
+
+
+@pytest.mark.parametrize("seed", range(40))
+def test_sim_random_option_sets_at_geometry_edges_equal_oracle(seed):
+    _check(engines.sim_engine, seed, random_edge_case)
+
+
+@pytest.mark.gpu
+@pytest.mark.twin("test_sim_random_option_sets_at_geometry_edges_equal_oracle")
+@pytest.mark.parametrize("seed", range(40))
+def test_gpu_random_option_sets_at_geometry_edges_equal_oracle(seed):
+    _check(engines.gpu_engine, seed, random_edge_case)
