@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -27,19 +28,19 @@ using namespace fq;
 // ---------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------
-extern "C" __global__ void __launch_bounds__(1024) fq_fused_kernel(FusedArgs a) {
+extern "C" __global__ void __launch_bounds__(1024) fq_fused_kernel(KernelArgs a) {
     extern __shared__ __attribute__((aligned(16))) u32 fq_lds[];
     // read the argument block through the kernarg segment pointer (scalar loads where a field is
     // used) instead of holding all ~150 dwords in SGPRs for the whole persistent loop
     fused_body<false>(*kernel_args(&a), fq_lds);
 }
 // the per-read kernel of the split plan as one large workgroup per CU (A/B against the small-workgroup form)
-extern "C" __global__ void __launch_bounds__(1024) fq_scan_wide_kernel(FusedArgs a) {
+extern "C" __global__ void __launch_bounds__(1024) fq_scan_wide_kernel(KernelArgs a) {
     extern __shared__ __attribute__((aligned(16))) u32 fq_lds[];
     fused_body<true>(*kernel_args(&a), fq_lds);
 }
 // the per-read kernel of the split plan: 256-lane workgroups, four to a CU (fq_stats_kernel counts afterwards)
-extern "C" __global__ void __launch_bounds__(256, 4) fq_scan_kernel(FusedArgs a) {
+extern "C" __global__ void __launch_bounds__(256, 4) fq_scan_kernel(KernelArgs a) {
     extern __shared__ __attribute__((aligned(16))) u32 fq_lds[];
     fused_body<true>(*kernel_args(&a), fq_lds);
 }
@@ -60,25 +61,14 @@ __global__ void __launch_bounds__(LaneGeom<SWM>::MAX_THREADS, 1) fq_lane_kernel(
     extern __shared__ __attribute__((aligned(16))) u32 fq_lds[];
     lane_body<SWM, B, NPL, PAIRED, EXT>(*kernel_args(&a), fq_lds);
 }
-// EXT >= 2 (fronts, -c, --merge) at 168 VGPRs spills ~150 dwords per lane; the same body compiled for two wavefronts per SIMD
-// (512 lanes, 256 VGPRs) - FASTP_GPU_LANE_EXT_WAVES picks (A/B, profiles/r05_lane_ext_waves_ab.txt)
-template <int B, int EXT>
-__global__ void __launch_bounds__(512, 1) fq_lane_pair2w_kernel(LaneArgs a) {
-    extern __shared__ __attribute__((aligned(16))) u32 fq_lds[];
-    lane_body<10, B, 3, true, EXT>(*kernel_args(&a), fq_lds);
-}
 extern "C" __global__ void __launch_bounds__(1024, 8) fq_stats_kernel(StatsArgs a) {
     extern __shared__ __attribute__((aligned(16))) u32 fq_lds[];
-    if (a.form == 4) {   // (uniform)
 #ifdef FQ_PROFILE_ABLATION
-        if ((a.debug_skip & 0x1C0u) && a.kc == 4) { stats_body4<4, true>(a, fq_lds); return; }   // profiling build only (FASTP_GPU_DEBUG_SKIP)
+    if ((a.debug_skip & 0x1C0u) && a.kc == 4) { stats_body4<4, true>(a, fq_lds); return; }   // profiling build only (FASTP_GPU_DEBUG_SKIP)
 #endif
-        if (a.kc == 4) stats_body4<4, false>(a, fq_lds);
-        else if (a.kc == 2) stats_body4<2, false>(a, fq_lds);
-        else stats_body4<1, false>(a, fq_lds);
-    } else {
-        stats_body(a, fq_lds);
-    }
+    if (a.kc == 4) stats_body4<4, false>(a, fq_lds);
+    else if (a.kc == 2) stats_body4<2, false>(a, fq_lds);
+    else stats_body4<1, false>(a, fq_lds);
 }
 // form 5 of the Stats kernel (fq_stats5.h): one 1024-lane workgroup per CU that owns the joint table (110 KB at ten item columns)
 extern "C" __global__ void __launch_bounds__(1024) fq_stats5_kernel(StatsArgs a) {
@@ -87,7 +77,7 @@ extern "C" __global__ void __launch_bounds__(1024) fq_stats5_kernel(StatsArgs a)
     if ((a.debug_skip & 0xC0u) && a.Hs == 10 && a.kc == 2) { stats_body5<2, 10, true>(a, fq_lds); return; }   // profiling build only
 #endif
 #ifndef FQ_ST5_ONEBLK
-#define FQ_ST5_ONEBLK 1   // (A/B: 0 = the block form for every length, tools/gpu_r6_n.sh)
+#define FQ_ST5_ONEBLK 1   // (A/B: 0 = the block form for every length)
 #endif
 #ifndef FQ_ST5_NOFRONT
 #define FQ_ST5_NOFRONT 1   // (A/B: 0 = the front read from the arguments / the records whatever the options)
@@ -153,7 +143,6 @@ extern "C" __global__ void __launch_bounds__(OVR_BLOCK) fq_ovr_count_kernel(OvrA
     ovr_count_body(o, fq_lds);
 }
 extern "C" __global__ void __launch_bounds__(256) fq_ovr_corr_link_kernel(OvrArgs o) { ovr_corr_link_body(o); }
-extern "C" __global__ void __launch_bounds__(64) fq_ovr_dist_kernel(OvrArgs o) { ovr_dist_body(o); }
 extern "C" __global__ void __launch_bounds__(256) fq_parse_count_kernel(ParseArgs p) {
     extern __shared__ __attribute__((aligned(16))) u32 fq_lds[];
     parse_count_body(p, fq_lds);
@@ -254,8 +243,32 @@ extern "C" __global__ void __launch_bounds__(1024) fq_dup_resolve_kernel(DupArgs
 // ---------------------------------------------------------------------------
 static thread_local std::string g_last_error;
 
+// The FASTP_GPU_* environment switches of this file, read once when a context is created (read_switches).  Each is what a
+// test or a tool sets before it creates the engine; DESIGN.md, "Environment switches", has the table.
+struct Switches {
+    int verbose;              // geometry lines on stderr: tests/test_launch_geometry.py, test_ref_binding.py, bench.py
+    int lane;                 // 0 = no lane plan: the parity tests run the tile kernels of the split plan
+    int split;                // 0 = Stats inside the fused kernel whatever the options: the parity tests
+    int threads;              // workgroup size of the tile kernels (0: 256 split, 1024 fused): the parity tests
+    int tile;                 // pairs per tile (0: the largest that fits): the parity tests
+    int lds_kb;               // the tile kernels' LDS budget (0: not set): tests/test_launch_geometry.py
+    int max_tiles_per_block;  // > 0 caps a launch so that a small batch takes several: the parity tests
+    int hash_generic;         // the multiply form of the duplicate hash: tests/test_hostsim_parity.py
+    int dup_table;            // Duplicate's first form (probe + resolve): tests/test_hostsim_parity.py, tools/dup_forms_check.py
+    int claim_fused;          // 0 = Duplicate's claim as its own kernel: tests/test_hostsim_parity.py, tools/dup_forms_check.py
+    int dedup_fold;           // 0 = --dedup through the hash pre-pass on the lane plan too: tests/test_hostsim_parity.py
+    int lane_pool_log2;       // the lane kernel's chunk pool (LaneArgs::pool): tests/test_hostsim_parity.py
+    int stats_blocks_per_cu;  // Stats workgroups per CU (0: what fits): tests/test_hostsim_parity.py, tools/two_engine_probe.py
+    int exact;                // every unit through the text kernel: tests/test_gpu_parity.py
+    int test_merge_slow;      // every merged read's second part counted by the lane kernel: the parity tests
+    int inflate;              // FASTP_GPU_INFLATE=lane (1) | wave (2) forces an inflate kernel (0: by size): the parity tests
+    int debug_skip;           // FQ_PROFILE_ABLATION builds only (tools/build_ablation.sh, tools/phase_pmc.sh); bench.py refuses it
+    int phase_timing;         // per-phase cycle counters: fastp_amd/engine.py, tools/phase_prof.py
+};
+
 struct fastp_gpu_ctx {
     fastp_gpu_params params;
+    Switches sw;
     std::string adapter1, adapter2;
     DevParams dp;
     HostLuts luts;
@@ -273,11 +286,7 @@ struct fastp_gpu_ctx {
     int st_H = 0, st_Hs = 0, st_lds_dwords = 0, st_slab_dwords = 0;
     u32* d_corr_int = nullptr; size_t corr_int_cap = 0;      // -c on the lane plan: the launch's corrections (KernelArgs::corr_int) + 1 counter word
     u32* d_corr_chain = nullptr; size_t corr_chain_cap = 0;  // their per-read chains: head[reads] | next[capacity]
-    int ln_prefetch = 0;   // FASTP_GPU_LANE_PREFETCH (round 6): LaneArgs::prefetch
-    int ln_grab = 1;       // FASTP_GPU_LANE_GRAB (round 6): LaneArgs::grab
-    int ln_glds = 0;   // FASTP_GPU_LANE_GLDS (A/B, measured null: profiles/r05_lane_glds_ab.txt): LaneArgs::glds
-    bool ln_2w = false;   // the lane kernel's EXT >= 2 instantiation compiled for two wavefronts per SIMD (FASTP_GPU_LANE_EXT_WAVES=2)
-    int st_form = 4, st_kc = 4, st_max_reads = CYC_MAX_READS, st_max_grid = 0;   // FASTP_GPU_STATS_V / _KC: the Stats kernel's form (fq_stats.h)
+    int st_form = 4, st_kc = 4, st_max_reads = CYC_MAX_READS, st_max_grid = 0;   // the Stats kernel's form: 5 (fq_stats5.h) where it fits, else 4 (fq_stats.h)
     int st_l_cyc = 0, st_l_kmer = 0, st_l_qh = 0, st_l_lut = 0, st_l_mt = 0, st_l_wl = 0, st_wl_cap = 0;
     int st_H16 = 0, st_l_ovf = 0;          // form 5 (fq_stats5.h)
     u32* d_st_slabs = nullptr;
@@ -286,23 +295,13 @@ struct fastp_gpu_ctx {
     int ln_swm = 0, ln_blocks = 0, ln_threads = 256;
     LaneLds ln_lds;
     u32* d_ln_slabs = nullptr;
-    int* d_ln_ctr = nullptr;       // the lane kernel's chunk counter
-    int ln_pool_base = 0;          // ... as the pool's counter (LaneArgs::pool_base): what it may have reached by the next launch
-    // split plans: Duplicate's losers / winners / finish kernels of a launch run on this stream beside its Stats kernel
+    int* d_ln_ctr = nullptr;       // the lane kernel's chunk pool counter (LaneArgs::chunk_ctr)
+    int ln_pool_base = 0;          // LaneArgs::pool_base: what the counter may have reached by the next launch
+    // split plans (never null there): Duplicate's losers / winners / finish kernels of a launch run on this stream beside its Stats kernel
     hipStream_t tail = nullptr;
     hipEvent_t ev_k1 = nullptr, ev_tail = nullptr;
     u32* d_swin[2] = {nullptr, nullptr}; size_t swin_cap = 0;
     hipStream_t stream = nullptr;
-    // Duplicate's probe + resolve of launch k run beside the fused kernel of launch k + 1 (see launch_chunk): the fused
-    // kernel holds every VGPR of the CUs it sits on, so the pair of streams is confined to disjoint CU sets
-    hipStream_t aux = nullptr;
-    hipEvent_t ev_fused[2] = {nullptr, nullptr}, ev_dup[2] = {nullptr, nullptr};
-    bool ev_dup_set[2] = {false, false};
-    bool aux_pending = false;      // the aux stream has work the main stream has not joined yet
-    int aux_last = 0;
-    uint64_t launch_seq = 0;
-    u64* d_dup_pos2[2] = {nullptr, nullptr}; size_t dup_pos2_cap[2] = {0, 0};
-    const void* last_res[2] = {nullptr, nullptr};   // result rows [begin, end) the aux stream's last resolve writes to
     // device buffers
     int16_t* d_ov_limit = nullptr;
     u16* d_lowq = nullptr;
@@ -348,7 +347,6 @@ struct fastp_gpu_ctx {
     int* d_x_unit = nullptr; size_t x_unit_cap = 0;        // the submitted batch's exotic unit list
     u8* d_x_skip = nullptr; size_t x_skip_cap = 0;          // KernelArgs::xskip of the launch
     u32* d_al[4] = {nullptr, nullptr, nullptr, nullptr}; size_t al_cap[4] = {0, 0, 0, 0};   // merge mode: 16-byte aligned copies of a launch's rows
-    int* d_ovr_diff = nullptr; size_t ovr_diff_cap = 0;     // OvrArgs::dist_diff, the four slots one behind the other (zero between launches)
     u16* d_x_len = nullptr; size_t x_len_cap = 0;          // the launch's length arrays with the text kernel's units zeroed (what the plan's kernels see)
     void* d_x_text[2] = {nullptr, nullptr}; size_t x_text_cap[2] = {0, 0};   // host submits: the raw text + offsets staged in HBM
     void* d_x_off[2] = {nullptr, nullptr}; size_t x_off_cap[2] = {0, 0};
@@ -391,6 +389,30 @@ static int env_int(const char* name, int dflt) {
     return (v && *v) ? atoi(v) : dflt;
 }
 
+static Switches read_switches() {
+    Switches w;
+    w.verbose = env_int("FASTP_GPU_VERBOSE", 0);
+    w.lane = env_int("FASTP_GPU_LANE", 1);
+    w.split = env_int("FASTP_GPU_SPLIT", 1);
+    w.threads = env_int("FASTP_GPU_THREADS", 0);
+    w.tile = env_int("FASTP_GPU_TILE", 0);
+    w.lds_kb = env_int("FASTP_GPU_LDS_KB", 0);
+    w.max_tiles_per_block = env_int("FASTP_GPU_MAX_TILES_PER_BLOCK", 0);
+    w.hash_generic = env_int("FASTP_GPU_HASH_GENERIC", 0);
+    w.dup_table = env_int("FASTP_GPU_DUP_TABLE", 0);
+    w.claim_fused = env_int("FASTP_GPU_CLAIM_FUSED", 1);
+    w.dedup_fold = env_int("FASTP_GPU_DEDUP_FOLD", 1);
+    w.lane_pool_log2 = env_int("FASTP_GPU_LANE_POOL_LOG2", 0);
+    w.stats_blocks_per_cu = env_int("FASTP_GPU_STATS_BLOCKS_PER_CU", 0);
+    w.exact = env_int("FASTP_GPU_EXACT", 0);
+    w.test_merge_slow = env_int("FASTP_GPU_TEST_MERGE_SLOW", 0);
+    const char* how = getenv("FASTP_GPU_INFLATE");
+    w.inflate = !how ? 0 : !strcmp(how, "lane") ? 1 : !strcmp(how, "wave") ? 2 : 3;   // (3: a word that is neither - the wave kernel where it fits)
+    w.debug_skip = env_int("FASTP_GPU_DEBUG_SKIP", 0);
+    w.phase_timing = env_int("FASTP_GPU_PHASE_TIMING", 0);
+    return w;
+}
+
 static int fail(fastp_gpu_ctx* ctx, int code, const std::string& msg) {
     if (ctx) ctx->err = msg;
     g_last_error = msg;
@@ -420,15 +442,8 @@ extern "C" void fastp_gpu_destroy(fastp_gpu_ctx* ctx) {
     if (!ctx) return;
     if (fastp_gpu_comm_destroy_hook) fastp_gpu_comm_destroy_hook(ctx);
     (void)hipSetDevice(ctx->device);
-    if (ctx->aux) (void)hipStreamSynchronize(ctx->aux);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     drain_events(ctx);
-    for (int k = 0; k < 2; k++) {
-        if (ctx->ev_fused[k]) (void)hipEventDestroy(ctx->ev_fused[k]);
-        if (ctx->ev_dup[k]) (void)hipEventDestroy(ctx->ev_dup[k]);
-        if (ctx->d_dup_pos2[k]) (void)hipFree(ctx->d_dup_pos2[k]);
-    }
-    if (ctx->aux) (void)hipStreamDestroy(ctx->aux);
     for (auto& sl : ctx->aslot) {
         if (sl.d_stage) (void)hipFree(sl.d_stage);
         if (sl.done) (void)hipEventDestroy(sl.done);
@@ -441,7 +456,7 @@ extern "C" void fastp_gpu_destroy(fastp_gpu_ctx* ctx) {
                     ctx->d_ovr_table[0], ctx->d_ovr_table[1], ctx->d_ovr_sym[0], ctx->d_ovr_sym[1], ctx->d_ovr_len[0],
                     ctx->d_ovr_len[1], ctx->d_post_seen, ctx->d_ovr_work, ctx->d_parse, ctx->d_fmt, ctx->d_prefix, ctx->d_inf, ctx->d_ovr_corr, ctx->d_eval, ctx->d_def, ctx->d_setw, ctx->d_cfilter,
                     ctx->d_st_slabs, ctx->d_swin[0], ctx->d_swin[1], ctx->d_ln_slabs, ctx->d_ln_ctr,
-                    ctx->d_corr_int, ctx->d_corr_chain, ctx->d_x_unit, ctx->d_x_len, ctx->d_x_skip, ctx->d_ovr_diff, ctx->d_al[0], ctx->d_al[1], ctx->d_al[2], ctx->d_al[3], ctx->d_x_text[0], ctx->d_x_text[1], ctx->d_x_off[0], ctx->d_x_off[1]};
+                    ctx->d_corr_int, ctx->d_corr_chain, ctx->d_x_unit, ctx->d_x_len, ctx->d_x_skip, ctx->d_al[0], ctx->d_al[1], ctx->d_al[2], ctx->d_al[3], ctx->d_x_text[0], ctx->d_x_text[1], ctx->d_x_off[0], ctx->d_x_off[1]};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->tail) (void)hipStreamDestroy(ctx->tail);
@@ -457,7 +472,7 @@ extern "C" void fastp_gpu_destroy(fastp_gpu_ctx* ctx) {
 // form 5 of the Stats kernel (fq_stats5.h): the copies of the 5-mer table its LDS layout has room for (0: it does not fit)
 // (and, through hb, the columns its table holds: reads with more 16-base columns than fit are taken in blocks of hb columns)
 static int stats5_copies(const DevParams& p, int lds_bytes, int* hb_out = nullptr) {
-    if (env_int("FASTP_GPU_STATS_V", 5) < 5 || p.merge_lane) return 0;
+    if (p.merge_lane) return 0;
     const int H16 = (p.qw_g + 3) / 4, Cp = (p.cycles + 3) & ~3;
     if (H16 > p.sw_g || H16 > 64) return 0;
     for (int nblk = 1; nblk <= 4; nblk++) {
@@ -514,9 +529,7 @@ static lane_kernel_fn lane_kernel_merge(int swm, int B) {
     if (swm == 10) return B == 0 ? fq_lane_kernel<10, 0, 3, true, 3> : B == 2 ? fq_lane_kernel<10, 2, 3, true, 3> : fq_lane_kernel<10, 4, 3, true, 3>;
     return B == 0 ? fq_lane_kernel<16, 0, 3, true, 3> : B == 2 ? fq_lane_kernel<16, 2, 3, true, 3> : fq_lane_kernel<16, 4, 3, true, 3>;
 }
-static lane_kernel_fn lane_kernel_for(int swm, int B, bool paired, int ext, bool two_waves = false) {
-    if (two_waves && swm == 10 && paired && ext == 3) return B == 0 ? fq_lane_pair2w_kernel<0, 3> : B == 2 ? fq_lane_pair2w_kernel<2, 3> : fq_lane_pair2w_kernel<4, 3>;
-    if (two_waves && swm == 10 && paired && ext == 2) return B == 0 ? fq_lane_pair2w_kernel<0, 2> : B == 2 ? fq_lane_pair2w_kernel<2, 2> : fq_lane_pair2w_kernel<4, 2>;
+static lane_kernel_fn lane_kernel_for(int swm, int B, bool paired, int ext) {
     if (ext == 3) return lane_kernel_merge(swm, B);
     return ext == 2 ? lane_kernel_pick<2>(swm, B, paired) : ext == 1 ? lane_kernel_pick<1>(swm, B, paired) : lane_kernel_pick<0>(swm, B, paired);
 }
@@ -529,7 +542,10 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, FASTP_GPU_E_NO_DEVICE, "no HIP device visible - the engine has no CPU fallback");
     if (device < 0 || device >= ndev) return fail(nullptr, FASTP_GPU_E_NO_DEVICE, "device ordinal out of range");
-    fastp_gpu_ctx* ctx = new fastp_gpu_ctx();
+    std::unique_ptr<fastp_gpu_ctx> owner(new fastp_gpu_ctx());   // released at `*out = ctx`: every return before that frees it
+    fastp_gpu_ctx* ctx = owner.get();
+    ctx->sw = read_switches();
+    const Switches& sw = ctx->sw;
     ctx->params = *params;
     if (params->adapter_seq_r1) ctx->adapter1 = params->adapter_seq_r1;
     if (params->adapter_seq_r2) ctx->adapter2 = params->adapter_seq_r2;
@@ -553,12 +569,12 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
     ctx->device = device;
     std::string err;
     int rc = build_dev_params(ctx->params, ctx->dp, ctx->luts, err);
-    if (rc) { delete ctx; return fail(nullptr, rc, err); }
+    if (rc) return fail(nullptr, rc, err);
     hipError_t he = hipSetDevice(device);
-    if (he != hipSuccess) { delete ctx; return fail(nullptr, FASTP_GPU_E_HIP, "hipSetDevice failed"); }
+    if (he != hipSuccess) return fail(nullptr, FASTP_GPU_E_HIP, "hipSetDevice failed");
     hipDeviceProp_t prop;
     he = hipGetDeviceProperties(&prop, device);
-    if (he != hipSuccess) { delete ctx; return fail(nullptr, FASTP_GPU_E_HIP, "hipGetDeviceProperties failed"); }
+    if (he != hipSuccess) return fail(nullptr, FASTP_GPU_E_HIP, "hipGetDeviceProperties failed");
     ctx->cus = prop.multiProcessorCount;
     ctx->lds_bytes = (int)std::min<size_t>(prop.sharedMemPerBlock, (size_t)1 << 30);
     const int lds_max = ctx->lds_bytes;
@@ -568,37 +584,30 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
     // option moves or edits a kept base; FASTP_GPU_SPLIT=0 keeps Stats inside the one-workgroup-per-CU fused kernel.
     // the Stats kernel as its own launch: options that leave every kept base where it was, or (lane plan only) move it by the
     // same front for every read that is written out (DevParams::front_lane)
-    const bool lane_wanted = env_int("FASTP_GPU_LANE", 1) != 0 && lane_plan_supported(ctx->dp, ctx->luts, lds_max);
-    ctx->split = (ctx->dp.stats_one_pass || ((ctx->dp.front_lane || ctx->dp.corr_lane || ctx->dp.merge_lane) && lane_wanted)) && env_int("FASTP_GPU_SPLIT", 1) != 0;
-    ctx->cfg.split = ctx->split ? 1 : 0;
-    ctx->cfg.threads = env_int("FASTP_GPU_THREADS", ctx->split ? 256 : 1024);
-    ctx->cfg.P = env_int("FASTP_GPU_TILE", 0);
-    // (FASTP_GPU_LDS_KB above what the device has is clamped to it: a budget the card cannot give would only fail the launch)
-    ctx->cfg.lds_budget = std::min(env_int("FASTP_GPU_LDS_KB", ctx->split ? std::min(40, lds_kb_default) : lds_kb_default), lds_max / 1024) * 1024;
-    // two tiles in flight per workgroup (each half of the waves owns one) when the halves are whole wavefronts
-    ctx->cfg.halves = (env_int("FASTP_GPU_HALVES", 1) == 2 && ctx->cfg.threads % 128 == 0) ? 2 : 1;
-    if (ctx->cfg.threads < 64 || ctx->cfg.threads > 1024 || (ctx->cfg.threads & 63)) {
-        delete ctx;
-        return fail(nullptr, FASTP_GPU_E_INVALID, "FASTP_GPU_THREADS must be a multiple of 64 in 64..1024");
-    }
-    if (env_int("FASTP_GPU_HASH_GENERIC", 0)) {  // tests: the multiply form of the duplicate hash (what B = 8 uses)
+    if (sw.hash_generic) {  // tests: the multiply form of the duplicate hash (what B = 8 uses; the lane plan has none)
         ctx->luts.dup_planes.clear();
         ctx->luts.dup_nq = 0;
     }
+    const bool lane_wanted = sw.lane != 0 && lane_plan_supported(ctx->dp, ctx->luts, lds_max);
+    ctx->split = (ctx->dp.stats_one_pass || ((ctx->dp.front_lane || ctx->dp.corr_lane || ctx->dp.merge_lane) && lane_wanted)) && sw.split != 0;
+    ctx->lane = ctx->split && lane_wanted;
+    ctx->cfg.split = ctx->split ? 1 : 0;
+    ctx->cfg.threads = sw.threads ? sw.threads : (ctx->split ? 256 : 1024);
+    ctx->cfg.P = sw.tile;
+    // (FASTP_GPU_LDS_KB above what the device has is clamped to it: a budget the card cannot give would only fail the launch)
+    ctx->cfg.lds_budget = std::min(sw.lds_kb ? sw.lds_kb : (ctx->split ? std::min(40, lds_kb_default) : lds_kb_default), lds_max / 1024) * 1024;
+    if (ctx->cfg.threads < 64 || ctx->cfg.threads > 1024 || (ctx->cfg.threads & 63))
+        return fail(nullptr, FASTP_GPU_E_INVALID, "FASTP_GPU_THREADS must be a multiple of 64 in 64..1024");
     rc = compute_lds_layout(ctx->dp, ctx->cfg, ctx->L, err, ctx->luts.dup_nq);
-    if (rc && ctx->cfg.halves == 2 && ctx->cfg.P > 0) {  // an explicit tile size that only fits once: one tile in flight
-        ctx->cfg.halves = 1;
-        rc = compute_lds_layout(ctx->dp, ctx->cfg, ctx->L, err, ctx->luts.dup_nq);
-    }
-    if (rc && ctx->split && !getenv("FASTP_GPU_LDS_KB")) {  // long reads (or a tile size asked for): the small budget holds no such tile
+    if (rc && ctx->split && !sw.lds_kb) {  // long reads (or a tile size asked for): the small budget holds no such tile
         ctx->cfg.lds_budget = lds_kb_default * 1024;
         rc = compute_lds_layout(ctx->dp, ctx->cfg, ctx->L, err, ctx->luts.dup_nq);
     }
-    if (rc) { delete ctx; return fail(nullptr, rc, err); }
-    int blocks_per_cu = env_int("FASTP_GPU_BLOCKS_PER_CU", std::max(1, (int)(lds_max / (ctx->L.total * 4))));
+    if (rc) return fail(nullptr, rc, err);
+    int blocks_per_cu = std::max(1, (int)(lds_max / (ctx->L.total * 4)));
     blocks_per_cu = std::max(1, std::min(blocks_per_cu, 2048 / ctx->cfg.threads));   // 32 wavefronts per CU
 #ifndef FQ_HOSTSIM
-    if (!getenv("FASTP_GPU_BLOCKS_PER_CU")) {
+    {
         // persistent workgroups: the grid must not exceed what is resident at once (registers bound it, not only LDS)
         int nb = 0;
         const void* kfn = ctx->split ? (ctx->cfg.threads > 256 ? (const void*)fq_scan_wide_kernel : (const void*)fq_scan_kernel) : (const void*)fq_fused_kernel;
@@ -611,44 +620,37 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
     ctx->blocks = ctx->cus * blocks_per_cu;
     // a workgroup's packed per-cycle counters hold CYC_MAX_READS reads per Stats slot
     int tiles_per_block = CYC_MAX_READS / ctx->L.P;
-    const int cap_tiles = env_int("FASTP_GPU_MAX_TILES_PER_BLOCK", 0);  // tests: force several launches
+    const int cap_tiles = sw.max_tiles_per_block;  // tests: force several launches
     if (cap_tiles > 0 && cap_tiles < tiles_per_block) tiles_per_block = cap_tiles;
-    if (ctx->cfg.halves == 2 && tiles_per_block > 1) tiles_per_block &= ~1;  // a workgroup's two halves take tiles in pairs
-    if (tiles_per_block < 1) { delete ctx; return fail(nullptr, FASTP_GPU_E_INVALID, "tile too large for the packed counters"); }
+    if (tiles_per_block < 1) return fail(nullptr, FASTP_GPU_E_INVALID, "tile too large for the packed counters");
     if (ctx->split) {
-        // the Stats kernel: [4][8][N_CLS][H] u64 per-cycle accumulators, k-mer and histogram counters, the increment table
+        // the Stats kernel: form 5 where its joint table fits the device's LDS and the options allow it (stats5_copies), else form 4
         ctx->st_H = ctx->dp.qw_g / 2;
-        const int st_want = env_int("FASTP_GPU_STATS_V", 5);
-        ctx->st_form = (st_want == 3 && !ctx->dp.front_lane && !ctx->dp.corr_lane && !ctx->dp.merge_lane) ? 3 : 4;   // (a front / -c / --merge: form 4 only)
-        if (st_want >= 5 && !ctx->dp.merge_lane) {
-            // round 6's form (fq_stats5.h): the joint table [2][8][4][ST5_QN][H16] of 16-bit cell pairs, KC copies of the mate's 5-mer
+        int hb = 0;
+        const int kc5 = stats5_copies(ctx->dp, lds_max, &hb);
+        if (kc5) {
+            ctx->st_H16 = (ctx->dp.qw_g + 3) / 4;
+            // form 5 (fq_stats5.h): the joint table [2][8][4][ST5_QN][H16] of 16-bit cell pairs, KC copies of the mate's 5-mer
             // counters, the packed cells of what the table has no cell for, the histogram of those, a list per wavefront - where it
             // fits one workgroup's LDS (reads of up to 176 bases; merge mode's third pass exists in form 4 only)
-            ctx->st_H16 = (ctx->dp.qw_g + 3) / 4;
-            int hb = 0;
-            const int kc = stats5_copies(ctx->dp, lds_max, &hb);
-            if (kc) {
-                int o = 0;
-                ctx->st_l_cyc = o; o += 2 * 8 * 4 * ST5_QN * hb;
-                ctx->st_l_kmer = o; o += 2 * KMER_BINS * kc;
-                o = (o + 1) & ~1;
-                ctx->st_l_ovf = o; o += 2 * ctx->L.Cp * N_CLS * 2;
-                ctx->st_l_qh = o; o += 2 * 128;
-                ctx->st_l_wl = o; o += (1024 / 64) * 2 * ST5_WL / 2;   // (u16 entries)
-                ctx->st_form = 5;
-                ctx->st_kc = kc;
-                ctx->st_Hs = hb;                     // the table's columns: all of a read's (st_H16), or a block of them
-                ctx->st_lds_dwords = o;
-                ctx->st_max_reads = CYC_MAX_READS;   // (a list entry holds the trip in 10 bits: 16 wavefronts x (64 / hb >= 4) units per trip, <= 256 trips)
-            }
-        }
-        if (ctx->st_form == 5) {
-        } else if (ctx->st_form == 4) {
-            // round 5's form: [2][8][ST4_ROWS][Hs] u32 per-cycle cells of ONE mate, KC copies of its 5-mer counters, its histogram
-            ctx->st_kc = env_int("FASTP_GPU_STATS_KC", 4);
-            if (ctx->st_kc != 1 && ctx->st_kc != 2 && ctx->st_kc != 4) ctx->st_kc = 4;
-            ctx->st_Hs = env_int("FASTP_GPU_STATS_HS", 0);
-            if (ctx->st_Hs < ctx->st_H) ctx->st_Hs = ctx->st_H < 32 ? 32 : ctx->st_H;
+            int o = 0;
+            ctx->st_l_cyc = o; o += 2 * 8 * 4 * ST5_QN * hb;
+            ctx->st_l_kmer = o; o += 2 * KMER_BINS * kc5;
+            o = (o + 1) & ~1;
+            ctx->st_l_ovf = o; o += 2 * ctx->L.Cp * N_CLS * 2;
+            ctx->st_l_qh = o; o += 2 * 128;
+            ctx->st_l_wl = o; o += (1024 / 64) * 2 * ST5_WL / 2;   // (u16 entries)
+            ctx->st_form = 5;
+            ctx->st_kc = kc5;
+            ctx->st_Hs = hb;                     // the table's columns: all of a read's (st_H16), or a block of them
+            ctx->st_lds_dwords = o;
+            ctx->st_max_reads = CYC_MAX_READS;   // (a list entry holds the trip in 10 bits: 16 wavefronts x (64 / hb >= 4) units per trip, <= 256 trips)
+        } else {
+            // form 4 (fq_stats.h): [2][8][ST4_ROWS][Hs] u32 per-cycle cells of ONE mate, four copies of its 5-mer counters, its histogram;
+            // the class stride padded to 32 items (= all 64 banks)
+            ctx->st_form = 4;
+            ctx->st_kc = 4;
+            ctx->st_Hs = ctx->st_H < 32 ? 32 : ctx->st_H;
             ctx->st_max_reads = ST4_MAX_READS;
             for (;;) {
                 ctx->st_wl_cap = 511;
@@ -666,39 +668,12 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
                 else if (ctx->st_kc > 1) ctx->st_kc /= 2;                 // then the copies
                 else break;
             }
-        } else {
-        // class stride of the per-cycle table: 32 items (= all 64 banks) where two workgroups per CU still fit
-        ctx->st_max_reads = CYC_MAX_READS;
-        ctx->st_Hs = ctx->st_H;
-        if (env_int("FASTP_GPU_STATS_PAD", 1) && ctx->st_H < 32) ctx->st_Hs = 32;
-        ctx->st_wl_cap = ctx->st_Hs > ctx->st_H ? 511 : 2047;
-        for (;;) {
-            const int bytes = (4 * 8 * N_CLS * ctx->st_Hs * 2 + 4 * KMER_BINS + ST_QH_COPIES * 4 * 128 + 4 * 256 + 20 + 1 + ctx->st_wl_cap + 3) * 4;
-            if (ctx->st_Hs == ctx->st_H || 2 * bytes <= lds_max) break;
-            ctx->st_Hs = ctx->st_H;
-            ctx->st_wl_cap = 2047;
-        }
-        int o = 0;
-        ctx->st_l_cyc = o; o += 4 * 8 * N_CLS * ctx->st_Hs * 2;
-        ctx->st_l_kmer = o; o += 4 * KMER_BINS;
-        ctx->st_l_qh = o; o += ST_QH_COPIES * 4 * 128;
-        o = (o + 3) & ~3;
-        ctx->st_l_lut = o; o += 4 * 256;
-        ctx->st_l_mt = o; o += 18 + 2;
-        ctx->st_l_wl = o; o += 1 + ctx->st_wl_cap;
-        ctx->st_lds_dwords = o;
         }
         ctx->st_slab_dwords = 4 * ctx->L.Cp * N_CLS * 2 + 4 * KMER_BINS + 4 * 128;
-        ctx->st_threads = env_int("FASTP_GPU_STATS_THREADS", 1024);
-        if (ctx->st_threads < 64 || ctx->st_threads > 1024 || (ctx->st_threads & 63) || ctx->st_form == 5) ctx->st_threads = 1024;
-        if (ctx->st_lds_dwords * 4 > lds_max) { delete ctx; return fail(nullptr, FASTP_GPU_E_INVALID, "reads too long for the Stats kernel's LDS"); }
-        int st_per_cu = std::min(2048 / ctx->st_threads, lds_max / (ctx->st_lds_dwords * 4));
-        st_per_cu = env_int("FASTP_GPU_STATS_BLOCKS_PER_CU", std::max(1, st_per_cu));
+        ctx->st_threads = 1024;
+        if (ctx->st_lds_dwords * 4 > lds_max) return fail(nullptr, FASTP_GPU_E_INVALID, "reads too long for the Stats kernel's LDS");
+        const int st_per_cu = sw.stats_blocks_per_cu ? sw.stats_blocks_per_cu : std::min(2048 / ctx->st_threads, lds_max / (ctx->st_lds_dwords * 4));
         ctx->st_blocks = ctx->cus * std::max(1, st_per_cu);
-        ctx->lane = env_int("FASTP_GPU_LANE", 1) != 0 && lane_plan_supported(ctx->dp, ctx->luts, lds_max);
-        ctx->ln_glds = env_int("FASTP_GPU_LANE_GLDS", 0);
-        ctx->ln_prefetch = env_int("FASTP_GPU_LANE_PREFETCH", 0);
-        ctx->ln_grab = env_int("FASTP_GPU_LANE_GRAB", 4);   // (1.400 -> 1.350 ms per 4 Mi pairs, profiles/r06_d_lane_grab_prefetch_ab.txt)
         if (ctx->lane) {
             ctx->ln_swm = ctx->dp.sw_g <= 10 ? 10 : 16;
             LaneLds& l = ctx->ln_lds;
@@ -724,16 +699,13 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
             l.stage_dwords = (64 * std::max(ctx->dp.qw_g, ctx->dp.sw_g) + 4 * ctx->ln_swm + 3) & ~3;   // + the over-read of the last row
             l.part_dwords = ctx->dp.paired ? (ctx->ln_swm / 2) * 64 : 0;   // read 1 of a pair: [ln_swm / 2 words][64 lanes]
             // as many wavefronts per workgroup as the LDS holds (up to three per SIMD for reads <= 160 bases, two above)
-            ctx->ln_2w = ctx->ln_swm == 10 && ctx->dp.paired && lane_ext(ctx->dp) >= 2 && env_int("FASTP_GPU_LANE_EXT_WAVES", 3) == 2;
-            const int max_waves = (ctx->ln_swm > 10 || ctx->ln_2w ? 512 : 256 * FQ_LANE_WAVES) / 64;
+            const int max_waves = (ctx->ln_swm > 10 ? 512 : 256 * FQ_LANE_WAVES) / 64;
             l.clist_dwords = (ctx->dp.corr_lane && ctx->dp.paired) ? (ctx->ln_swm / 2) * 64 : 0;   // -c: read 1's edited positions, a bit mask per lane
-            // the workgroup's chunk counter and the prefetch sink (l.ctr, l.sink below) come out of the LDS before it is divided
-            // into wavefronts (o and every per-wavefront size are multiples of 4 dwords: no padding in front of l.ctr)
-            const int tail_dwords = 4 + 64;
+            // the workgroup's chunk counter (l.ctr below) and the reserve come out of the LDS before it is divided into
+            // wavefronts (o and every per-wavefront size are multiples of 4 dwords: no padding in front of l.ctr)
+            const int tail_dwords = LANE_CTR_DWORDS + LANE_RESERVED_DWORDS;
             int waves = (int)(((long long)lds_max / 4 - o - tail_dwords) / (l.stage_dwords + l.part_dwords + l.clist_dwords));
             waves = std::max(1, std::min(waves, max_waves));
-            const int env_threads = env_int("FASTP_GPU_LANE_THREADS", 0);   // A/B: 256 = round 3's geometry (several workgroups per CU)
-            if (env_threads >= 64 && env_threads <= max_waves * 64) waves = env_threads / 64;
             ctx->ln_threads = waves * 64;
             o += waves * l.stage_dwords;
             l.part = o;
@@ -741,16 +713,14 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
             l.clist = o;
             o += waves * l.clist_dwords;
             o = (o + 3) & ~3;
-            l.ctr = o;           // the workgroup's chunk counter (LaneArgs::local_ctr)
-            o += 4;
-            l.sink = o;          // where the row prefetches land (LaneArgs::prefetch): 64 lanes x 4 bytes, every wavefront's
-            o += 64;
+            l.ctr = o;
+            o += tail_dwords;
             l.total = o;
-            int per_cu = env_int("FASTP_GPU_LANE_BLOCKS_PER_CU", 0);
+            int per_cu = 0;
 #ifndef FQ_HOSTSIM
-            if (per_cu <= 0) {
+            {
                 int nb = 0;
-                lane_kernel_fn fn = lane_kernel_for(ctx->ln_swm, ctx->dp.dup_enabled ? ctx->dp.dup_bufnum : 0, ctx->dp.paired != 0, lane_ext(ctx->dp), ctx->ln_2w);
+                lane_kernel_fn fn = lane_kernel_for(ctx->ln_swm, ctx->dp.dup_enabled ? ctx->dp.dup_bufnum : 0, ctx->dp.paired != 0, lane_ext(ctx->dp));
                 (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, l.total * 4);
                 if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, ctx->ln_threads, (size_t)l.total * 4) == hipSuccess && nb > 0) per_cu = nb;
                 (void)hipGetLastError();
@@ -761,10 +731,8 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
         }
     }
     // --cut_front on the lane plan (a front per read) has its POST Stats only in form 5 of the Stats kernel
-    if (ctx->lane && ctx->dp.front_per_read && ctx->st_form != 5) {
-        delete ctx;
+    if (ctx->lane && ctx->dp.front_per_read && ctx->st_form != 5)
         return fail(nullptr, FASTP_GPU_E_INVALID, "a front per read on the lane plan needs form 5 of the Stats kernel, which was not chosen");
-    }
     {   // every kernel's dynamic LDS against what the device gives a workgroup: a layout that does not fit fails here, never at a launch
         const char* name = ctx->split ? (ctx->cfg.threads > 256 ? "scan_wide kernel" : "scan kernel") : "fused kernel";
         std::vector<std::pair<const char*, long long>> need = {{name, (long long)ctx->L.total * 4}, {"hash kernel", (long long)ctx->L.total * 4},
@@ -780,11 +748,10 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
             if (k.second > lds_max) {
                 const std::string m = std::string(k.first) + ": " + std::to_string(k.second) + " bytes of LDS per workgroup, the device has " +
                                       std::to_string(lds_max);
-                delete ctx;
                 return fail(nullptr, FASTP_GPU_E_INVALID, m);
             }
     }
-    auto set_launch_size = [&]() {
+    {
         long long mp = (long long)ctx->blocks * tiles_per_block * ctx->L.P;
         if (ctx->split) {   // the per-read kernel has no packed counters; a Stats workgroup takes <= CYC_MAX_READS units
             mp = (long long)ctx->st_blocks * CYC_MAX_READS;   // (form 4 takes such a launch as several rounds of workgroups)
@@ -797,89 +764,34 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
             // pairs of 2x150 is then ONE launch instead of two (2 * index + 1 still fits an int)
             long long entries = 1ll << 29;
             size_t mfree = 0, mtotal = 0;
-            const int want = env_int("FASTP_GPU_CORR_LIST_LOG2", 0);
-            if (want == 30 || (want == 0 && hipMemGetInfo(&mfree, &mtotal) == hipSuccess && mfree >= ((size_t)64 << 30))) entries = (1ll << 30) - 64;
+            if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess && mfree >= ((size_t)64 << 30)) entries = (1ll << 30) - 64;
             (void)hipGetLastError();
             mp = std::min(mp, entries / std::max(1, ctx->dp.max_len));
         }
         mp = mp / ctx->L.P * ctx->L.P;
         ctx->max_pairs_per_launch = (int)mp;
-    };
-    set_launch_size();
+    }
     fastp_gpu_counter_layout_for_params(&ctx->params, &ctx->cl);
-    ctx->exact_all = env_int("FASTP_GPU_EXACT", 0) != 0;   // tests: every unit through the text kernel (fq_text.h)
-    if (ctx->exact_all && env_int("FASTP_GPU_VERBOSE", 0)) fprintf(stderr, "fastp_gpu: FASTP_GPU_EXACT=1, every unit takes the text kernel\n");
-    if (env_int("FASTP_GPU_VERBOSE", 0))
+    ctx->exact_all = sw.exact != 0;   // tests: every unit through the text kernel (fq_text.h)
+    if (ctx->exact_all && sw.verbose) fprintf(stderr, "fastp_gpu: FASTP_GPU_EXACT=1, every unit takes the text kernel\n");
+    if (sw.verbose)
         fprintf(stderr, "fastp_gpu: %s, tile P=%d (%d rows), %d threads, LDS %d bytes, %d workgroups, %d units/launch; stats kernel form %d, %d x %d threads, LDS %d bytes\n",
                 ctx->lane ? "lane plan" : (ctx->split ? "split plan" : "fused plan"), ctx->L.P, ctx->L.NR, ctx->cfg.threads, ctx->L.total * 4, ctx->blocks,
                 ctx->max_pairs_per_launch, ctx->st_form, ctx->st_blocks, ctx->st_threads, ctx->st_lds_dwords * 4);
-    if (env_int("FASTP_GPU_VERBOSE", 0) && ctx->lane)
+    if (sw.verbose && ctx->lane)
         fprintf(stderr, "fastp_gpu: lane kernel %d x %d threads (%d per CU), LDS %d bytes per workgroup (stage %d + read-1 sums %d per wavefront), SWM %d, ext %d\n",
                 ctx->ln_blocks, ctx->ln_threads, ctx->ln_blocks / std::max(1, ctx->cus), ctx->ln_lds.total * 4, ctx->ln_lds.stage_dwords * 4,
                 ctx->ln_lds.part_dwords * 4, ctx->ln_swm, (int)lane_ext(ctx->dp));
     ctx->slab_dwords = ctx->L.acc_end - ctx->L.acc_cyc;
 
-    *out = ctx;  // from here on errors go through destroy
+    *out = owner.release();  // from here on errors go through destroy
     fq::timeline("create: plan chosen (device properties, occupancy queries)");
 #define CREATE_TRY(call)                                               \
     do {                                                               \
         int r_ = [&]() -> int { HIP_TRY(ctx, call); return 0; }();     \
         if (r_) { std::string m = ctx->err; fastp_gpu_destroy(ctx); *out = nullptr; return fail(nullptr, r_, m); } \
     } while (0)
-    {
-        // FASTP_GPU_AUX_CUS compute units are set aside for the duplicate kernels (0, the default: one stream, everything
-        // in order).  Measured (profiles/r02k_cu_mask_sweep.txt): only a whole SE-even group of 32 CUs keeps the fused
-        // kernel's workgroups evenly placed; it hides the duplicate kernels (+4.5 % Mreads/s) but the fused kernel then
-        // runs on 224 CUs (-13 % of its own rate), so it stays an option.
-        const int aux_cus = (ctx->dp.dup_enabled && !ctx->dp.dedup) ? env_int("FASTP_GPU_AUX_CUS", 0) : 0;
-        bool split = false;
-        if (aux_cus > 0 && aux_cus * 4 <= ctx->cus && blocks_per_cu == 1) {
-            const int words = (ctx->cus + 31) / 32;
-            std::vector<uint32_t> m_main((size_t)words, 0u), m_aux((size_t)words, 0u);
-            // workgroups are dealt evenly to the XCDs, so every XCD gives up the same number of CUs; bit i of a CU mask
-            // belongs to XCD i % n_xcd (measured: profiles/r02k_cu_mask_sweep.txt)
-            const int n_xcd = env_int("FASTP_GPU_XCDS", ctx->cus % 8 == 0 && ctx->cus >= 64 ? 8 : 1);
-            const int per_xcd = std::max(1, aux_cus / n_xcd), slots = ctx->cus / n_xcd;
-            int n_aux = 0;
-            u64 slot_mask = 0;   // which CU slots of an XCD go to the aux stream
-            if (const char* e = getenv("FASTP_GPU_AUX_SLOTS")) {
-                for (const char* q = e; *q;) {
-                    slot_mask |= 1ull << (strtol(q, (char**)&q, 10) & 63);
-                    if (*q == ',') q++;
-                }
-            } else {
-                for (int j = slots - per_xcd; j < slots; j++) slot_mask |= 1ull << j;
-            }
-            for (int cu = 0; cu < ctx->cus; cu++) {
-                const bool to_aux = (slot_mask >> (cu / n_xcd)) & 1ull;
-                if (to_aux) n_aux++;
-                (to_aux ? m_aux : m_main)[(size_t)cu >> 5] |= 1u << (cu & 31);
-            }
-            if (hipExtStreamCreateWithCUMask(&ctx->stream, (uint32_t)words, m_main.data()) == hipSuccess) {
-                if (hipExtStreamCreateWithCUMask(&ctx->aux, (uint32_t)words, m_aux.data()) == hipSuccess) {
-                    split = true;
-                    ctx->blocks = ctx->cus - n_aux;
-                    set_launch_size();
-                } else {
-                    (void)hipStreamDestroy(ctx->stream);
-                    ctx->stream = nullptr;
-                    ctx->aux = nullptr;
-                }
-            } else {
-                ctx->stream = nullptr;
-            }
-            (void)hipGetLastError();
-        }
-        if (split) {
-            for (int k = 0; k < 2; k++) {
-                CREATE_TRY(hipEventCreateWithFlags(&ctx->ev_fused[k], hipEventDisableTiming));
-                CREATE_TRY(hipEventCreateWithFlags(&ctx->ev_dup[k], hipEventDisableTiming));
-            }
-            if (env_int("FASTP_GPU_VERBOSE", 0)) fprintf(stderr, "fastp_gpu: %d CUs for the fused kernel, %d for Duplicate\n", ctx->blocks, ctx->cus - ctx->blocks);
-        } else {
-            CREATE_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-        }
-    }
+    CREATE_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
     fq::timeline("create: launch stream created");
     CREATE_TRY(hipFuncSetAttribute(ctx->split ? (ctx->cfg.threads > 256 ? (const void*)fq_scan_wide_kernel : (const void*)fq_scan_kernel) : (const void*)fq_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->L.total * 4));
     CREATE_TRY(hipFuncSetAttribute((const void*)fq_hash_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->L.total * 4));
@@ -891,62 +803,47 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
         if (ctx->dp.corr_lane)
             CREATE_TRY(hipFuncSetAttribute((const void*)fq_corr_stats_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)((ctx->dp.paired ? 2 : 1) * (33 * (size_t)ctx->cl.cycles + 128 + KMER_BINS) * 4)));
-        // a slab per workgroup of the largest launch: st_blocks of them for the packed u64 form, rounds of st_blocks for the u32 form
-        ctx->st_max_grid = ctx->st_form == 4 ? (ctx->max_pairs_per_launch + ST4_MAX_READS - 1) / ST4_MAX_READS + ctx->st_blocks
-                                             : (ctx->st_form == 5 ? 2 * ctx->st_blocks + 2 : ctx->st_blocks);
+        // a slab per workgroup of the largest launch: rounds of st_blocks for form 4, two rounds for form 5
+        ctx->st_max_grid = ctx->st_form == 4 ? (ctx->max_pairs_per_launch + ST4_MAX_READS - 1) / ST4_MAX_READS + ctx->st_blocks : 2 * ctx->st_blocks + 2;
         if (ctx->st_form == 5) CREATE_TRY(hipFuncSetAttribute((const void*)fq_stats5_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->st_lds_dwords * 4));
         CREATE_TRY(hipMalloc((void**)&ctx->d_st_slabs, (size_t)ctx->st_max_grid * ctx->st_slab_dwords * 4));
-        if (env_int("FASTP_GPU_DUP_OVERLAP", 1)) {
 #ifdef FQ_HOSTSIM
-            CREATE_TRY(hipStreamCreateWithFlags(&ctx->tail, hipStreamNonBlocking));
+        CREATE_TRY(hipStreamCreateWithFlags(&ctx->tail, hipStreamNonBlocking));
 #else
-            // a second stream that really runs beside the first (fq_probe_wait_kernel): up to six candidates, the ones that share the
-            // first stream's queue are held until the search ends (the next one is then given another queue) and closed afterwards
-            int* d_flag = nullptr;
-            CREATE_TRY(hipMalloc((void**)&d_flag, 2 * sizeof(int)));
-            std::vector<hipStream_t> rejected;
-            const int tries = env_int("FASTP_GPU_TAIL_TRIES", 6);
-            const bool tail_prio = env_int("FASTP_GPU_TAIL_PRIORITY", 0) != 0;
-            for (int t = 0; t < std::max(1, tries) && !ctx->tail; t++) {
-                hipStream_t cand = nullptr;
-                if (tail_prio) {   // (A/B, FASTP_GPU_TAIL_PRIORITY=1: the tail stream's workgroups first when a CU frees up)
-                    int lo = 0, hi = 0;
-                    CREATE_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
-                    CREATE_TRY(hipStreamCreateWithPriority(&cand, hipStreamNonBlocking, hi));
-                } else
-                CREATE_TRY(hipStreamCreateWithFlags(&cand, hipStreamNonBlocking));
-                bool beside = tries <= 1;
-                if (!beside) {
-                    CREATE_TRY(hipMemsetAsync(d_flag, 0, 2 * sizeof(int), ctx->stream));
-                    CREATE_TRY(hipStreamSynchronize(ctx->stream));
-                    hipLaunchKernelGGL(fq_probe_wait_kernel, dim3(1), dim3(64), 0, ctx->stream, d_flag, 2000000ll);
-                    hipLaunchKernelGGL(fq_probe_set_kernel, dim3(1), dim3(64), 0, cand, d_flag);
-                    CREATE_TRY(hipStreamSynchronize(cand));
-                    CREATE_TRY(hipStreamSynchronize(ctx->stream));
-                    int h[2] = {0, 0};
-                    CREATE_TRY(hipMemcpy(h, d_flag, sizeof(h), hipMemcpyDeviceToHost));
-                    beside = h[1] != 0;
-                }
-                if (beside) ctx->tail = cand;
-                else rejected.push_back(cand);
-            }
-            if (!ctx->tail) { ctx->tail = rejected.back(); rejected.pop_back(); }   // (none runs beside it: correct, one behind the other)
-            if (env_int("FASTP_GPU_VERBOSE", 0)) fprintf(stderr, "fastp_gpu: second stream: candidate %d of %d runs beside the first\n", (int)rejected.size() + 1, tries);
-            for (hipStream_t r : rejected) (void)hipStreamDestroy(r);
-            (void)hipFree(d_flag);
-#endif
-            fq::timeline("create: second stream probed");
-            CREATE_TRY(hipEventCreateWithFlags(&ctx->ev_k1, hipEventDisableTiming));
-            CREATE_TRY(hipEventCreateWithFlags(&ctx->ev_tail, hipEventDisableTiming));
+        // a second stream that really runs beside the first (fq_probe_wait_kernel): up to six candidates, the ones that share the
+        // first stream's queue are held until the search ends (the next one is then given another queue) and closed afterwards
+        int* d_flag = nullptr;
+        CREATE_TRY(hipMalloc((void**)&d_flag, 2 * sizeof(int)));
+        std::vector<hipStream_t> rejected;
+        const int tries = 6;
+        for (int t = 0; t < tries && !ctx->tail; t++) {
+            hipStream_t cand = nullptr;
+            CREATE_TRY(hipStreamCreateWithFlags(&cand, hipStreamNonBlocking));
+            CREATE_TRY(hipMemsetAsync(d_flag, 0, 2 * sizeof(int), ctx->stream));
+            CREATE_TRY(hipStreamSynchronize(ctx->stream));
+            hipLaunchKernelGGL(fq_probe_wait_kernel, dim3(1), dim3(64), 0, ctx->stream, d_flag, 2000000ll);
+            hipLaunchKernelGGL(fq_probe_set_kernel, dim3(1), dim3(64), 0, cand, d_flag);
+            CREATE_TRY(hipStreamSynchronize(cand));
+            CREATE_TRY(hipStreamSynchronize(ctx->stream));
+            int h[2] = {0, 0};
+            CREATE_TRY(hipMemcpy(h, d_flag, sizeof(h), hipMemcpyDeviceToHost));
+            if (h[1] != 0) ctx->tail = cand;
+            else rejected.push_back(cand);
         }
+        if (!ctx->tail) { ctx->tail = rejected.back(); rejected.pop_back(); }   // (none runs beside it: correct, one behind the other)
+        if (sw.verbose) fprintf(stderr, "fastp_gpu: second stream: candidate %d of %d runs beside the first\n", (int)rejected.size() + 1, tries);
+        for (hipStream_t r : rejected) (void)hipStreamDestroy(r);
+        (void)hipFree(d_flag);
+#endif
+        fq::timeline("create: second stream probed");
+        CREATE_TRY(hipEventCreateWithFlags(&ctx->ev_k1, hipEventDisableTiming));
+        CREATE_TRY(hipEventCreateWithFlags(&ctx->ev_tail, hipEventDisableTiming));
         if (ctx->lane) {
             CREATE_TRY(hipMalloc((void**)&ctx->d_ln_slabs, (size_t)ctx->ln_blocks * ctx->ln_lds.n_misc * 4));
-            if (env_int("FASTP_GPU_LANE_DYNAMIC", 1)) {
-                CREATE_TRY(hipMalloc((void**)&ctx->d_ln_ctr, sizeof(int)));
-                CREATE_TRY(hipMemset(ctx->d_ln_ctr, 0, sizeof(int)));
-            }
+            CREATE_TRY(hipMalloc((void**)&ctx->d_ln_ctr, sizeof(int)));
+            CREATE_TRY(hipMemset(ctx->d_ln_ctr, 0, sizeof(int)));
             for (int Bh : {0, ctx->dp.dup_enabled ? ctx->dp.dup_bufnum : 0})
-                CREATE_TRY(hipFuncSetAttribute((const void*)lane_kernel_for(ctx->ln_swm, Bh, ctx->dp.paired != 0, lane_ext(ctx->dp), ctx->ln_2w),
+                CREATE_TRY(hipFuncSetAttribute((const void*)lane_kernel_for(ctx->ln_swm, Bh, ctx->dp.paired != 0, lane_ext(ctx->dp)),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, ctx->ln_lds.total * 4));
         }
     }
@@ -999,7 +896,7 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
         CREATE_TRY(hipMalloc((void**)&ctx->d_bitmap, bytes));
         CREATE_TRY(hipMemsetAsync(ctx->d_bitmap, 0, bytes, ctx->stream));
     }
-    if (env_int("FASTP_GPU_PHASE_TIMING", 0)) {
+    if (sw.phase_timing) {
         CREATE_TRY(hipMalloc((void**)&ctx->d_phase, 16 * sizeof(u64)));
         CREATE_TRY(hipMemsetAsync(ctx->d_phase, 0, 16 * sizeof(u64), ctx->stream));
     }
@@ -1018,23 +915,8 @@ extern "C" int fastp_gpu_debug_phase_cycles(fastp_gpu_ctx* ctx, uint64_t* out16)
     return FASTP_GPU_OK;
 }
 
-// make `st` wait for what the aux stream still has in flight (duplicate flags, counters, bitmap)
-static int join_aux(fastp_gpu_ctx* ctx, hipStream_t st) {
-    if (!ctx->aux_pending) return 0;
-    HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_dup[ctx->aux_last], 0));
-    if (st == ctx->stream) ctx->aux_pending = false;
-    return 0;
-}
-static int sync_main(fastp_gpu_ctx* ctx) {
-    int rc = join_aux(ctx, ctx->stream);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
 static int ensure(fastp_gpu_ctx* ctx, void** buf, size_t* cap, size_t need) {
     if (*cap >= need) return 0;
-    if (*buf && ctx->aux_pending) { int rj = join_aux(ctx, ctx->stream); if (rj) return rj; }
     if (*buf) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); HIP_TRY(ctx, hipFree(*buf)); *buf = nullptr; *cap = 0; }
     size_t want = need + need / 4;
     HIP_TRY(ctx, hipMalloc(buf, want));
@@ -1103,24 +985,6 @@ static int launch_overrep(fastp_gpu_ctx* ctx, const KernelArgs& a, int n, hipStr
         }
         o.ctr = ctx->d_ctr;
         for (int k = 0; k < 4; k++) { o.o_count[k] = cl.overrep_count[k]; o.o_dist[k] = cl.overrep_dist[k]; }
-        int diff_rows = 0;
-        // mOverRepSeqDist as a difference array (OvrArgs::dist_diff): measured, no gain - configs[4] 4.90 ms without, 5.11 ms with
-        // (the fold's 130 lanes walk 251 positions each; profiles/r05_ovr_diff_ab.txt) - off unless asked for
-        if (env_int("FASTP_GPU_OVR_DIFF", 0)) {
-            size_t words = 0;
-            for (int k = 0; k < 4; k++) words += (size_t)o.mate[k >> 1].n_seeds * (size_t)(o.mate[k >> 1].eval_len + 1);
-            const size_t had = ctx->ovr_diff_cap;
-            rc = ensure(ctx, (void**)&ctx->d_ovr_diff, &ctx->ovr_diff_cap, words * 4 + 4);
-            if (rc) return rc;
-            if (ctx->ovr_diff_cap != had) HIP_TRY(ctx, hipMemsetAsync(ctx->d_ovr_diff, 0, ctx->ovr_diff_cap, st));   // (a new buffer: the fold leaves it zero)
-            size_t at = 0;
-            for (int k = 0; k < 4; k++) {
-                const OvrMate& M = o.mate[k >> 1];
-                o.dist_diff[k] = M.n_seeds ? ctx->d_ovr_diff + at : nullptr;
-                at += (size_t)M.n_seeds * (size_t)(M.eval_len + 1);
-                diff_rows += M.n_seeds;
-            }
-        }
         // the post-filtering Stats analyse the corrected reads: from the engine's own list of this launch where it keeps one (-c with
         // the Stats kernel as its own launch: sized for an edit at every base, it cannot overflow), else from the caller's
         // (a launch with units for the text kernel: that kernel's edits are in the caller's list only - it counts its units' POST
@@ -1169,10 +1033,6 @@ static int launch_overrep(fastp_gpu_ctx* ctx, const KernelArgs& a, int n, hipStr
             hipLaunchKernelGGL(fq_ovr_count_kernel, dim3((task_cap + OVR_TPB - 1) / OVR_TPB), dim3(OVR_BLOCK), (size_t)lds_bytes, st, o);
         }
         HIP_TRY(ctx, hipGetLastError());
-        if (diff_rows > 0) {
-            hipLaunchKernelGGL(fq_ovr_dist_kernel, dim3((diff_rows + 63) / 64), dim3(64), 0, st, o);
-            HIP_TRY(ctx, hipGetLastError());
-        }
     }
     ctx->units_seen += (uint64_t)n;
     return FASTP_GPU_OK;
@@ -1190,6 +1050,7 @@ enum ChunkMode {
 
 static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first, int n, const fastp_gpu_results* res,
                         hipStream_t st, ChunkMode mode = CHUNK_STREAM, u8* scan_state = nullptr) {
+    const Switches& sw = ctx->sw;
     KernelArgs a;
     memset(&a, 0, sizeof(a));
     a.p = ctx->dp;
@@ -1205,17 +1066,14 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
     a.magic_sw = magic_for((u32)ctx->L.SW);
     a.magic_qwg = magic_for((u32)ctx->dp.qw_g);
     a.magic_swg = magic_for((u32)ctx->dp.sw_g);
-    {   // vector (16-byte) tile copies + register prefetch need aligned rows and a tile that fits the registers
+    {   // vector (16-byte) tile copies need aligned rows and a tile that fits the registers
         const size_t qchunks = (size_t)ctx->L.NR * ctx->dp.qw_g / 4, schunks = (size_t)ctx->L.NR * ctx->dp.sw_g / 4;
-        const size_t tile_threads = (size_t)ctx->cfg.threads / ctx->L.halves;   // the waves that stage one tile
+        const size_t tile_threads = (size_t)ctx->cfg.threads;
         bool ok = (ctx->L.P % 2 == 0) && (first % 2 == 0) && qchunks <= (size_t)PF_Q * tile_threads &&
-                  schunks <= (size_t)PF_S * tile_threads && (size_t)ctx->L.NR <= tile_threads &&
-                  !env_int("FASTP_GPU_NO_PREFETCH", 0);
+                  schunks <= (size_t)PF_S * tile_threads && (size_t)ctx->L.NR <= tile_threads;
         const void* ptrs[4] = {b->seq1, b->qual1, ctx->dp.paired ? b->seq2 : b->seq1, ctx->dp.paired ? b->qual2 : b->qual1};
         for (const void* q : ptrs) ok = ok && (((uintptr_t)q & 15u) == 0);
-        // the L2 warm-up of the next tile (tile_warm) is off by default: it paid while the tile fetch waited per chunk,
-        // now it costs 2.5 % and makes every line cross HBM 1.35 times (profiles/r02p_prefetch_ab.txt)
-        a.prefetch = ok ? (env_int("FASTP_GPU_PREFETCH_AHEAD", 0) ? 1 : 2) : 0;
+        a.prefetch = ok ? 2 : 0;
     }
     a.n = n;
     a.first = first;
@@ -1266,7 +1124,7 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
         }
         // the lane plan runs the text kernel BESIDE its kernels: the lane kernel is told which units not to write (xskip)
         u8* skip = nullptr;
-        if (ctx->lane && ctx->split && ctx->tail && mode == CHUNK_STREAM && !ctx->dp.dedup) {
+        if (ctx->lane && mode == CHUNK_STREAM && !ctx->dp.dedup) {
             rx = ensure(ctx, (void**)&ctx->d_x_skip, &ctx->x_skip_cap, (size_t)n);
             if (rx) return rx;
             skip = ctx->d_x_skip;
@@ -1288,31 +1146,11 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
     // scan state of the whole batch: positions [b->n][B] u64, then masks [b->n] u8
     u64* scan_pos = scan_state ? (u64*)scan_state + (size_t)first * ctx->dp.dup_bufnum : nullptr;
     u8* scan_mask = scan_state ? scan_state + (size_t)b->n * ctx->dp.dup_bufnum * 8 + first : nullptr;
-    // the worker loop on the context's own streams: Duplicate's kernels go to the aux stream and overlap the next launch
-    const bool piped = ctx->aux && st == ctx->stream && mode == CHUNK_STREAM && ctx->dp.dup_enabled && !ctx->dp.dedup && !exact;
-    const int par = (int)(ctx->launch_seq & 1);
-    if (!piped) {
-        int rj = join_aux(ctx, st);
-        if (rj) return rj;
-    }
     u64* dup_pos_buf = nullptr;
     if (ctx->dp.dup_enabled && mode != CHUNK_OVERREP) {
-        if (piped) {
-            // this buffer was last read by the resolve of launch k - 2
-            if (ctx->ev_dup_set[par]) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_dup[par], 0));
-            int rc = ensure(ctx, (void**)&ctx->d_dup_pos2[par], &ctx->dup_pos2_cap[par], (size_t)n * ctx->dp.dup_bufnum * 8);
-            if (rc) return rc;
-            dup_pos_buf = ctx->d_dup_pos2[par];
-            // the resolve of launch k - 1 ORs duplicate flags into its result rows: wait for it if this launch writes the same rows
-            const char* lo = (const char*)a.res[0];
-            const char* hi = lo + (size_t)n * sizeof(fastp_gpu_read_result);
-            if (ctx->aux_pending && ctx->ev_dup_set[par ^ 1] && lo < (const char*)ctx->last_res[1] && (const char*)ctx->last_res[0] < hi)
-                HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_dup[par ^ 1], 0));
-        } else {
-            int rc = ensure(ctx, (void**)&ctx->d_dup_pos, &ctx->dup_pos_cap, (size_t)n * ctx->dp.dup_bufnum * 8);
-            if (rc) return rc;
-            dup_pos_buf = ctx->d_dup_pos;
-        }
+        int rc = ensure(ctx, (void**)&ctx->d_dup_pos, &ctx->dup_pos_cap, (size_t)n * ctx->dp.dup_bufnum * 8);
+        if (rc) return rc;
+        dup_pos_buf = ctx->d_dup_pos;
         a.dup_pos = dup_pos_buf;
     }
     a.split = ctx->split ? 1 : 0;
@@ -1347,20 +1185,15 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
     // floors under profiles/) exists only in a library built with -DFQ_PROFILE_ABLATION (tools/build_ablation.sh).  Bit 512 is a TEST
     // switch that leaves every result as it is (each merged read's second part counted by the lane kernel, fq_lane.h).
 #ifdef FQ_PROFILE_ABLATION
-    a.debug_skip = (u32)env_int("FASTP_GPU_DEBUG_SKIP", 0) & ~512u;
+    a.debug_skip = (u32)sw.debug_skip & ~512u;
 #else
     a.debug_skip = 0;
 #endif
-    if (env_int("FASTP_GPU_TEST_MERGE_SLOW", 0)) a.debug_skip |= 512u;
+    if (sw.test_merge_slow) a.debug_skip |= 512u;
     a.slabs = ctx->d_slabs;
     a.slab_dwords = ctx->slab_dwords;
     a.tiles = (n + ctx->L.P - 1) / ctx->L.P;
-    a.half_skew = env_int("FASTP_GPU_HALF_SKEW", 6);
-    a.half_naps = env_int("FASTP_GPU_HALF_NAPS", 1);
-    const int wg_tiles = (a.tiles + ctx->L.halves - 1) / ctx->L.halves;   // tiles are dealt to workgroups `halves` at a time
-    const int grid = wg_tiles < ctx->blocks ? wg_tiles : ctx->blocks;
-    // the stage + hash pre-pass of --dedup runs the whole workgroup on one tile at a time
-    auto whole = [](KernelArgs k) { k.L.halves = 1; return k; };
+    const int grid = a.tiles < ctx->blocks ? a.tiles : ctx->blocks;
     hipStream_t st_main = st;
     const fastp_gpu_counter_layout& cl = ctx->cl;
     int rc;
@@ -1387,18 +1220,18 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
     // --dedup without the hash pre-pass (round 5, lane plan, plain stream mode): the lane kernel hashes and claims as without
     // --dedup, Duplicate's tail decides, fq_dedup_apply_kernel takes the duplicates out again before the Stats kernel counts
     // (not in merge mode: a pair that merges is written out whatever Duplicate says, peprocessor.cpp:523-535)
-    const bool dedup_folded = ctx->dp.dedup && use_lane && mode == CHUNK_STREAM && !piped && !exact && !env_int("FASTP_GPU_DUP_TABLE", 0) &&
-                              !ctx->dp.merge_lane && env_int("FASTP_GPU_DEDUP_FOLD", 1) &&
-                              env_int("FASTP_GPU_CLAIM_FUSED", 1);   // (the fold IS the fused claim: without it the hash pre-pass decides)
+    const bool dedup_folded = ctx->dp.dedup && use_lane && mode == CHUNK_STREAM && !exact && !sw.dup_table &&
+                              !ctx->dp.merge_lane && sw.dedup_fold &&
+                              sw.claim_fused;   // (the fold IS the fused claim: without it the hash pre-pass decides)
     // the claim step inside the fused kernel: plain stream mode, one or two bloom buffers (the lane kernel: four as well), the
     // context's own stream order
     // ... and a launch with units for the text kernel when that kernel runs beside the lane kernel (exact_early below): the lane kernel
     // claims nothing for such a unit (KernelArgs::xskip), the text kernel claims its units' bits itself (fq_text.h t_claim) and
     // Duplicate's tail - which orders the claims by unit index, whoever fired them first - runs behind both
-    const bool exact_early = exact && use_lane && a.xskip != nullptr && !piped && env_int("FASTP_GPU_EXACT_EARLY", 1) != 0;
-    const bool claim_fused = ctx->dp.dup_enabled && (!ctx->dp.dedup || dedup_folded) && mode == CHUNK_STREAM && !piped &&
-                             (ctx->dp.dup_bufnum <= 2 || dedup_folded) && !env_int("FASTP_GPU_DUP_TABLE", 0) && env_int("FASTP_GPU_CLAIM_FUSED", 1) &&
-                             (!exact || (exact_early && env_int("FASTP_GPU_EXACT_CLAIM", 1)));
+    const bool exact_early = exact && use_lane && a.xskip != nullptr;
+    const bool claim_fused = ctx->dp.dup_enabled && (!ctx->dp.dedup || dedup_folded) && mode == CHUNK_STREAM &&
+                             (ctx->dp.dup_bufnum <= 2 || dedup_folded) && !sw.dup_table && sw.claim_fused &&
+                             (!exact || exact_early);
     // the text kernel (fq_text.h): a wavefront per listed unit, its texts in the wavefront's stretch of LDS, Stats' per-base
     // counters in the workgroup's LDS tables (added to d_ctr once), everything else straight into d_ctr
     auto launch_exact = [&](int hash_only, hipStream_t xst = nullptr) -> int {
@@ -1430,18 +1263,17 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
         const size_t text_bytes = (size_t)TEXT_WAVES * text_wave_bytes(e.ML);
         const int slot_dwords = 34 * (int)c.cycles + 1024 + 128;
         const int slots = !ctx->dp.paired ? 2 : ctx->dp.merge ? 3 : 4;   // the Stats objects a unit can reach
-        const bool lds_tables = !hash_only && (size_t)slots * slot_dwords * 4 + text_bytes <= (size_t)aux_lds_cap(ctx) && env_int("FASTP_GPU_EXACT_LDS", 1);
+        const bool lds_tables = !hash_only && (size_t)slots * slot_dwords * 4 + text_bytes <= (size_t)aux_lds_cap(ctx);
         e.lds_slot_dwords = lds_tables ? slot_dwords : 0;
         e.lds_slots = lds_tables ? slots : 0;
-        const int blocks = std::max(1, std::min((e.x_count + TEXT_WAVES - 1) / TEXT_WAVES, env_int("FASTP_GPU_EXACT_BLOCKS", ctx->cus)));
+        const int blocks = std::max(1, std::min((e.x_count + TEXT_WAVES - 1) / TEXT_WAVES, ctx->cus));
         hipLaunchKernelGGL(fq_text_kernel, dim3(blocks), dim3(64 * TEXT_WAVES), (size_t)e.lds_slots * e.lds_slot_dwords * 4 + text_bytes, st, e);
         HIP_TRY(ctx, hipGetLastError());
         return 0;
     };
     bool dup_prepared = false;
     auto launch_dup = [&](u8* dupflag, bool scan = false, hipStream_t st = nullptr, int stage = 0) -> int {
-        // stage 0: everything; 1: only the buffers + clears (before a fused kernel that claims); 2: what follows that kernel;
-        // 3: of that only fq_dup_losers_kernel, 4: only the two kernels behind it (the two on different streams, launch_chunk)
+        // stage 0: everything; 1: only the buffers + clears (before a fused kernel that claims); 2: what follows that kernel
         if (!st) st = st_main;
         DupArgs d;
         memset(&d, 0, sizeof(d));
@@ -1472,10 +1304,10 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
         // Stage 1's clears (128 MB of table for 4 Mi pairs: 21 + 6 us) are needed by the kernels of stage 2 only, not by the kernel
         // that claims: where stage 2 will run on the tail stream they go there, beside the per-read kernel instead of in front of it
         // (that stream is past the previous launch's tail by then; the launch stream joins it at the end of every launch)
-        hipStream_t cst = (stage == 1 && ctx->split && ctx->tail && !dedup_folded && n > 0 && env_int("FASTP_GPU_DUP_CLEAR_TAIL", 1)) ? ctx->tail : st;
+        hipStream_t cst = (stage == 1 && ctx->split && !dedup_folded && n > 0) ? ctx->tail : st;
         if (stage < 2) HIP_TRY(ctx, hipMemsetAsync(d.table, 0xFF, (size_t)8 << lg, cst));
         const int g2 = std::max(1, (n + 255) / 256);  // one unit per lane: the kernels are chains of dependent random accesses
-        if (env_int("FASTP_GPU_DUP_TABLE", 0)) {      // the first form: probe (read + table insert for every unit) -> resolve
+        if (sw.dup_table) {      // the first form: probe (read + table insert for every unit) -> resolve
             hipLaunchKernelGGL(fq_dup_probe_kernel, dim3(g2), dim3(256), 0, st, d);
             HIP_TRY(ctx, hipGetLastError());
             hipLaunchKernelGGL(fq_dup_resolve_kernel, dim3(std::max(1, (n + 1023) / 1024)), dim3(1024), 16, st, d);
@@ -1495,10 +1327,9 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
             dup_prepared = true;
             return 0;
         }
-        if (stage == 2 || stage == 3) hipLaunchKernelGGL(fq_dup_losers_kernel, dim3(g2), dim3(256), 0, st, d);
-        else if (stage != 4) hipLaunchKernelGGL(fq_dup_claim_kernel, dim3(g2), dim3(256), 0, st, d);
+        if (stage == 2) hipLaunchKernelGGL(fq_dup_losers_kernel, dim3(g2), dim3(256), 0, st, d);
+        else hipLaunchKernelGGL(fq_dup_claim_kernel, dim3(g2), dim3(256), 0, st, d);
         HIP_TRY(ctx, hipGetLastError());
-        if (stage == 3) return 0;
         hipLaunchKernelGGL(fq_dup_winners_kernel, dim3(g2), dim3(256), 0, st, d);
         HIP_TRY(ctx, hipGetLastError());
         hipLaunchKernelGGL(fq_dup_finish_kernel, dim3(std::max(1, (n + 1023) / 1024)), dim3(1024), 16, st, d);
@@ -1507,7 +1338,7 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
     };
 
     if (mode == CHUNK_PASS1 && ctx->dp.dedup) {
-        hipLaunchKernelGGL(fq_hash_kernel, dim3(grid), dim3(ctx->cfg.threads), (size_t)ctx->L.total * 4, st, whole(a));
+        hipLaunchKernelGGL(fq_hash_kernel, dim3(grid), dim3(ctx->cfg.threads), (size_t)ctx->L.total * 4, st, a);
         HIP_TRY(ctx, hipGetLastError());
         if (exact) {
             rc = launch_exact(1);
@@ -1552,7 +1383,7 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
         // --dedup: hash pass -> duplicate decision -> fused kernel reads the decision
         rc = ensure(ctx, (void**)&ctx->d_dupflag, &ctx->dupflag_cap, (size_t)n);
         if (rc) return rc;
-        hipLaunchKernelGGL(fq_hash_kernel, dim3(grid), dim3(ctx->cfg.threads), (size_t)ctx->L.total * 4, st, whole(a));
+        hipLaunchKernelGGL(fq_hash_kernel, dim3(grid), dim3(ctx->cfg.threads), (size_t)ctx->L.total * 4, st, a);
         HIP_TRY(ctx, hipGetLastError());
         if (exact) {
             rc = launch_exact(1);
@@ -1584,52 +1415,37 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
     rc = get_events(ctx, &e0, &e1);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(e0, st));
-    {
-        FusedArgs fa;
-        fa.h[0] = a;
-        fa.h[1] = a;
-        fa.h[1].L = layout_for_half(a.L, 1);
-        if (use_lane) {
-            LaneArgs la;
-            la.k = a;
-            la.k.slabs = ctx->d_ln_slabs;
-            la.k.slab_dwords = ctx->ln_lds.n_misc;
-            la.l = ctx->ln_lds;
-            la.chunk_ctr = ctx->d_ln_ctr;
-            la.glds = ctx->ln_glds;
-            la.prefetch = ctx->ln_prefetch;
-            la.grab = ctx->ln_grab;
-            la.local_ctr = env_int("FASTP_GPU_LANE_DYNAMIC", 2) == 2 ? 1 : 0;
-            la.pool = 0;
-            la.pool_base = 0;
-            la.pool_grab = 1;
-            if (la.local_ctr && la.chunk_ctr) {   // the chunks no workgroup owns (LaneArgs::pool)
-                // A/B, off: profiles/r06_x_lane_chunk_pool_ab.txt, r06_y_*: an 8th of the chunks -2 %, a 16th 0, a 32nd .. a 128th +0.2 % on the
-                // headline (noise), the single-end lines, -c and configs[4] 0.4 - 2 % SLOWER - the CUs' equal shares already end
-                // together; the asks of the pool cost what little imbalance there is
-                const int lg = env_int("FASTP_GPU_LANE_POOL_LOG2", 0);
-                const int chunks = (n + 63) >> 6;
-                la.pool = lg > 0 && lg < 31 ? chunks >> lg : 0;
-                if (ctx->ln_pool_base > 0x60000000) {   // (the counter only counts up: back to zero long before it could wrap)
-                    HIP_TRY(ctx, hipMemsetAsync(la.chunk_ctr, 0, sizeof(int), st));
-                    ctx->ln_pool_base = 0;
-                }
-                la.pool_base = ctx->ln_pool_base;
-                la.pool_grab = std::max(1, la.pool >> 11);   // at most ~2 k asks per launch
-                // every wavefront asks once more than it gets: the counter ends at most (asks that get chunks) + wavefronts beyond the base
-                ctx->ln_pool_base += (la.pool + la.pool_grab - 1) / la.pool_grab + ctx->ln_blocks * (ctx->ln_threads >> 6) + 64;
-            }
-            la.post1 = ctx->d_ctr + cl.stats[1];
-            la.st_qual_hist = cl.st_qual_hist; la.st_kmer = cl.st_kmer; la.st_cycle = cl.st_cycle; la.cycles = cl.cycles;
-            if (la.chunk_ctr && !la.local_ctr) HIP_TRY(ctx, hipMemsetAsync(la.chunk_ctr, 0, sizeof(int), st));
-            const int Bh = (ctx->dp.dup_enabled && (a.dup_pos || a.claim_won) && !(a.debug_skip & 2u)) ? ctx->dp.dup_bufnum : 0;
-            lane_kernel_fn fn = lane_kernel_for(ctx->ln_swm, Bh, ctx->dp.paired != 0, lane_ext(ctx->dp), ctx->ln_2w);
-            ln_grid = std::max(1, std::min(ctx->ln_blocks, (n + 255) / 256));
-            hipLaunchKernelGGL(fn, dim3(ln_grid), dim3(ctx->ln_threads), (size_t)ctx->ln_lds.total * 4, st, la);
-        } else if (ctx->split && ctx->cfg.threads > 256) hipLaunchKernelGGL(fq_scan_wide_kernel, dim3(grid), dim3(ctx->cfg.threads), (size_t)ctx->L.total * 4, st, fa);
-        else if (ctx->split) hipLaunchKernelGGL(fq_scan_kernel, dim3(grid), dim3(ctx->cfg.threads), (size_t)ctx->L.total * 4, st, fa);
-        else hipLaunchKernelGGL(fq_fused_kernel, dim3(grid), dim3(ctx->cfg.threads), (size_t)ctx->L.total * 4, st, fa);
-    }
+    if (use_lane) {
+        LaneArgs la;
+        la.k = a;
+        la.k.slabs = ctx->d_ln_slabs;
+        la.k.slab_dwords = ctx->ln_lds.n_misc;
+        la.l = ctx->ln_lds;
+        la.chunk_ctr = ctx->d_ln_ctr;
+        // the chunks no workgroup owns (LaneArgs::pool)
+        // A/B, off: profiles/r06_x_lane_chunk_pool_ab.txt, r06_y_*: an 8th of the chunks -2 %, a 16th 0, a 32nd .. a 128th +0.2 % on the
+        // headline (noise), the single-end lines, -c and configs[4] 0.4 - 2 % SLOWER - the CUs' equal shares already end
+        // together; the asks of the pool cost what little imbalance there is
+        const int lg = sw.lane_pool_log2;
+        const int chunks = (n + 63) >> 6;
+        la.pool = lg > 0 && lg < 31 ? chunks >> lg : 0;
+        if (ctx->ln_pool_base > 0x60000000) {   // (the counter only counts up: back to zero long before it could wrap)
+            HIP_TRY(ctx, hipMemsetAsync(la.chunk_ctr, 0, sizeof(int), st));
+            ctx->ln_pool_base = 0;
+        }
+        la.pool_base = ctx->ln_pool_base;
+        la.pool_grab = std::max(1, la.pool >> 11);   // at most ~2 k asks per launch
+        // every wavefront asks once more than it gets: the counter ends at most (asks that get chunks) + wavefronts beyond the base
+        ctx->ln_pool_base += (la.pool + la.pool_grab - 1) / la.pool_grab + ctx->ln_blocks * (ctx->ln_threads >> 6) + 64;
+        la.post1 = ctx->d_ctr + cl.stats[1];
+        la.st_qual_hist = cl.st_qual_hist; la.st_kmer = cl.st_kmer; la.st_cycle = cl.st_cycle; la.cycles = cl.cycles;
+        const int Bh = (ctx->dp.dup_enabled && (a.dup_pos || a.claim_won) && !(a.debug_skip & 2u)) ? ctx->dp.dup_bufnum : 0;
+        lane_kernel_fn fn = lane_kernel_for(ctx->ln_swm, Bh, ctx->dp.paired != 0, lane_ext(ctx->dp));
+        ln_grid = std::max(1, std::min(ctx->ln_blocks, (n + 255) / 256));
+        hipLaunchKernelGGL(fn, dim3(ln_grid), dim3(ctx->ln_threads), (size_t)ctx->ln_lds.total * 4, st, la);
+    } else if (ctx->split && ctx->cfg.threads > 256) hipLaunchKernelGGL(fq_scan_wide_kernel, dim3(grid), dim3(ctx->cfg.threads), (size_t)ctx->L.total * 4, st, a);
+    else if (ctx->split) hipLaunchKernelGGL(fq_scan_kernel, dim3(grid), dim3(ctx->cfg.threads), (size_t)ctx->L.total * 4, st, a);
+    else hipLaunchKernelGGL(fq_fused_kernel, dim3(grid), dim3(ctx->cfg.threads), (size_t)ctx->L.total * 4, st, a);
     HIP_TRY(ctx, hipGetLastError());
     // The text kernel of the units with letters outside ACGTN runs behind the plan's kernel (the records and hash values of its
     // units are overwritten) - and, in the split plans, BESIDE the Stats kernel (round 5): the Stats kernel needs nothing of it
@@ -1641,7 +1457,7 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
         HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, st));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->tail, ctx->ev_k1, 0));
         exact_on_tail = true;
-    } else if (exact && ctx->split && ctx->tail && mode == CHUNK_STREAM && !piped && !ctx->dp.dedup && n > 0 && env_int("FASTP_GPU_EXACT_TAIL", 1)) {
+    } else if (exact && ctx->split && mode == CHUNK_STREAM && !ctx->dp.dedup && n > 0) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, st));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->tail, ctx->ev_k1, 0));
         rc = launch_exact(0, ctx->tail);
@@ -1702,37 +1518,22 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
         hipLaunchKernelGGL(fq_dedup_apply_kernel, dim3((n + 255) / 256), dim3(256), 16, st, da);
         HIP_TRY(ctx, hipGetLastError());
         dedup_applied = true;
-    } else if (ctx->split && ctx->tail && dup_prepared && n > 0) {
+    } else if (ctx->split && dup_prepared && n > 0) {
         // The Stats kernel's workgroups own every CU (a 1024-lane workgroup at 128 VGPRs is the whole register file): a kernel on
         // the tail stream gets through when one of the Stats kernel's two rounds of workgroups ends, ONE kernel per such moment
         // (profiles/r06_s_step_timeline.txt, r06_t_step_timeline.txt: each tail kernel "takes" 0.43 - 0.50 ms, 0.01 - 0.03 alone).
-        // A/B, FASTP_GPU_DUP_LOSERS_FIRST=1: fq_dup_losers_kernel on the launch stream IN FRONT of the Stats kernel, so that
-        // winners gets through between the rounds - measured SLOWER (profiles/r06_u_losers_first_ab.txt: step 2.409 -> 2.440 ms):
-        // winners is then dispatched together with the Stats kernel's first round and shares the CUs with it from the start (the
-        // Stats kernel 0.89 -> 0.95 ms), finish still waits for its end.  Off.
-        // (never with units for the text kernel on the tail stream: the Stats kernel would wait for that kernel too)
-        const bool losers_first = env_int("FASTP_GPU_DUP_LOSERS_FIRST", 0) != 0 && mode != CHUNK_PASS1 && !exact;
-        if (losers_first) {
-            // (the tail stream holds the clears of this launch's table and filter: the launch stream waits for them first)
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_tail, ctx->tail));
-            HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_tail, 0));
-            rc = launch_dup(nullptr, false, st, 3);
-            if (rc) return rc;
-        }
         HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, st));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->tail, ctx->ev_k1, 0));
         // The MISC_* fold needs the per-read kernel only: FIRST on the tail stream.  Behind Duplicate's kernels - which the Stats
         // kernel's workgroups starve until its last round ends (profiles/r06_s_step_timeline.txt: losers 0.45 ms, winners 0.50 ms
         // beside it, 0.01 / 0.03 alone) - it was 27 + 9 us at the very end of every step, with nothing else on the chip.
-        if (env_int("FASTP_GPU_MISC_FOLD_FIRST", losers_first ? 0 : 1)) {
-            r.slabs = use_lane ? ctx->d_ln_slabs : ctx->d_slabs;
-            r.slab_dwords = use_lane ? ctx->ln_lds.n_misc : ctx->slab_dwords;
-            r.off_misc = use_lane ? 0 : ctx->L.acc_misc - ctx->L.acc_cyc;
-            rc = fold(2, use_lane ? ln_grid : grid, ctx->tail);
-            if (rc) return rc;
-            misc_folded = true;
-        }
-        rc = launch_dup(nullptr, mode == CHUNK_PASS1, ctx->tail, losers_first ? 4 : 2);
+        r.slabs = use_lane ? ctx->d_ln_slabs : ctx->d_slabs;
+        r.slab_dwords = use_lane ? ctx->ln_lds.n_misc : ctx->slab_dwords;
+        r.off_misc = use_lane ? 0 : ctx->L.acc_misc - ctx->L.acc_cyc;
+        rc = fold(2, use_lane ? ln_grid : grid, ctx->tail);
+        if (rc) return rc;
+        misc_folded = true;
+        rc = launch_dup(nullptr, mode == CHUNK_PASS1, ctx->tail, 2);
         if (rc) return rc;
         HIP_TRY(ctx, hipEventRecord(ctx->ev_tail, ctx->tail));
         dup_tail_launched = true;
@@ -1748,8 +1549,7 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
     // The overrepresentation analysis needs the records (and --dedup's decisions), nothing of the Stats kernel: on the tail stream
     // BESIDE it (round 5; behind Duplicate's tail / the text kernel when they are there - they write record flags), joined at the end
     bool ovr_early = false;
-    if (ctx->dp.overrep && !(b->flags & FASTP_GPU_BATCH_DEFER_OVERREP) && ctx->split && ctx->tail && mode == CHUNK_STREAM && !piped && n > 0 &&
-        env_int("FASTP_GPU_OVR_TAIL", 1)) {
+    if (ctx->dp.overrep && !(b->flags & FASTP_GPU_BATCH_DEFER_OVERREP) && ctx->split && mode == CHUNK_STREAM && n > 0) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, st));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->tail, ctx->ev_k1, 0));
         rc = overrep(ctx->tail);
@@ -1778,7 +1578,6 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
         sa.units_per_block = upb;
         st_grid = (n + upb - 1) / upb;
         if (st_grid > ctx->st_max_grid) return fail(ctx, FASTP_GPU_E_INVALID, "launch too large for the Stats kernel's slabs");
-        sa.form = ctx->st_form;
         sa.kc = ctx->st_kc;
         if (ctx->dp.front_lane) { sa.front[0] = ctx->dp.lane_front1; sa.front[1] = ctx->dp.lane_front2; }
         sa.merge = ctx->dp.merge_lane;
@@ -1909,19 +1708,7 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
         if (rc) return rc;
     }
 
-    if (piped) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_fused[par], st));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fused[par], 0));
-        rc = launch_dup(nullptr, false, ctx->aux);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_dup[par], ctx->aux));
-        ctx->ev_dup_set[par] = true;
-        ctx->aux_pending = true;
-        ctx->aux_last = par;
-        ctx->last_res[0] = a.res[0];
-        ctx->last_res[1] = (const char*)a.res[0] + (size_t)n * sizeof(fastp_gpu_read_result);
-        ctx->launch_seq++;
-    } else if (dup_tail_launched) {
+    if (dup_tail_launched) {
         HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_tail, 0));
     } else if (dedup_applied) {
         // (Duplicate's tail ran in front of the Stats kernel)
@@ -1929,7 +1716,7 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
         rc = launch_dup(nullptr, mode == CHUNK_PASS1, nullptr, dup_prepared ? 2 : 0);
         if (rc) return rc;
     }
-    if (ovr_early && !dup_tail_launched && !piped) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_tail, 0));
+    if (ovr_early && !dup_tail_launched) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_tail, 0));
     if ((b->flags & FASTP_GPU_BATCH_DEFER_OVERREP) || ovr_early) return FASTP_GPU_OK;
     return overrep();
 }
@@ -2024,9 +1811,8 @@ extern "C" int fastp_gpu_dup_bitmap_export(fastp_gpu_ctx* ctx, void* dst_device)
     if (bytes == 0) return FASTP_GPU_OK;
     if (!dst_device) return fail(ctx, FASTP_GPU_E_INVALID, "null argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rj_ = join_aux(ctx, ctx->stream); if (rj_) return rj_; }
     HIP_TRY(ctx, hipMemcpyAsync(dst_device, ctx->d_bitmap, (size_t)bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    { int rs_ = sync_main(ctx); if (rs_) return rs_; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return FASTP_GPU_OK;
 }
 
@@ -2038,9 +1824,8 @@ extern "C" int fastp_gpu_dup_bitmap_import(fastp_gpu_ctx* ctx, const void* src_d
     if (bytes == 0) return FASTP_GPU_OK;
     if (!src_device) return fail(ctx, FASTP_GPU_E_INVALID, "null argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rj_ = join_aux(ctx, ctx->stream); if (rj_) return rj_; }
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bitmap, src_device, (size_t)bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    { int rs_ = sync_main(ctx); if (rs_) return rs_; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return FASTP_GPU_OK;
 }
 
@@ -2063,7 +1848,7 @@ extern "C" int fastp_gpu_dup_prefix_set(fastp_gpu_ctx* ctx, const void* images_d
     o.n_images = n_images;
     hipLaunchKernelGGL(fq_or_images_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream, o);
     HIP_TRY(ctx, hipGetLastError());
-    { int rs_ = sync_main(ctx); if (rs_) return rs_; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->has_prefix = true;
     return FASTP_GPU_OK;
 }
@@ -2080,7 +1865,7 @@ extern "C" int fastp_gpu_prefix_or_images(fastp_gpu_ctx* ctx, void* images_devic
     o.n_images = n_images;
     hipLaunchKernelGGL(fq_or_images_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream, o);
     HIP_TRY(ctx, hipGetLastError());
-    { int rs_ = sync_main(ctx); if (rs_) return rs_; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return FASTP_GPU_OK;
 }
 
@@ -2105,7 +1890,7 @@ extern "C" int fastp_gpu_phred64_to_33(fastp_gpu_ctx* ctx, int32_t n, uint8_t* t
     a.qual = qual_rows;
     hipLaunchKernelGGL(fq_phred64_kernel, dim3(std::min((n + 3) / 4, ctx->cus * 32)), dim3(256), 0, ctx->stream, a);
     HIP_TRY(ctx, hipGetLastError());
-    { int rs_ = sync_main(ctx); if (rs_) return rs_; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return FASTP_GPU_OK;
 }
 
@@ -2116,7 +1901,7 @@ extern "C" int fastp_gpu_stream_set_origin(fastp_gpu_ctx* ctx, int64_t units_bef
     const u64 v = (u64)post_reads_before;
     if (!ctx->d_post_seen) return FASTP_GPU_OK;  // no overrepresentation analysis: nothing else reads positions
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_post_seen, &v, sizeof(v), hipMemcpyHostToDevice, ctx->stream));
-    { int rs_ = sync_main(ctx); if (rs_) return rs_; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return FASTP_GPU_OK;
 }
 
@@ -2288,10 +2073,10 @@ extern "C" int fastp_gpu_inflate_bgzf(fastp_gpu_ctx* ctx, const uint8_t* comp, i
     // one wavefront per block (fq_inflate_wave.h: 4.6 ms per launch whatever the size, 2 blocks per CU in flight) up to
     // 6144 blocks; beyond that blocks in flight decide and one lane per block (fq_inflate.h: ~50 ms per launch, 64 blocks
     // per wavefront) overtakes it (profiles/r02l_inflate.txt).  FASTP_GPU_INFLATE=lane|wave forces one.
-    const char* how = getenv("FASTP_GPU_INFLATE");
+    const int how = ctx->sw.inflate;   // 0: by size, 1: lane, 2: wave
     const bool wave_fits = (int)sizeof(IwLds) <= ctx->lds_bytes;
-    if (how && !strcmp(how, "wave") && !wave_fits) return fail(ctx, FASTP_GPU_E_INVALID, "FASTP_GPU_INFLATE=wave: the wave kernel's LDS does not fit this device");
-    const bool lane_kernel = how ? !strcmp(how, "lane") || !wave_fits : n_blocks > 6144 || !wave_fits;
+    if (how == 2 && !wave_fits) return fail(ctx, FASTP_GPU_E_INVALID, "FASTP_GPU_INFLATE=wave: the wave kernel's LDS does not fit this device");
+    const bool lane_kernel = how ? how == 1 || !wave_fits : n_blocks > 6144 || !wave_fits;
     if (lane_kernel) {
         const int lds_bytes = INF_ENTRIES * INF_LANES * 2 + INF_SBUF * INF_LANES * 4;
         hipLaunchKernelGGL(fq_inflate_kernel, dim3((n_blocks + INF_LANES - 1) / INF_LANES), dim3(INF_LANES), lds_bytes, st, a);
@@ -2484,7 +2269,7 @@ static int eval_admit(fastp_gpu_ctx* ctx, const uint16_t* len, int32_t n, int64_
     lens.resize(take);
     if (take) {
         HIP_TRY(ctx, hipMemcpyAsync(lens.data(), len, take * 2, hipMemcpyDeviceToHost, ctx->stream));
-        { int rs_ = sync_main(ctx); if (rs_) return rs_; }
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     int64_t bases = 0;
     size_t used = 0;
@@ -2710,7 +2495,7 @@ extern "C" int fastp_gpu_device_free(fastp_gpu_ctx* ctx, void* dev_ptr) {
     if (!ctx) return FASTP_GPU_E_INVALID;
     if (!dev_ptr) return FASTP_GPU_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rs_ = sync_main(ctx); if (rs_) return rs_; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipFree(dev_ptr));
     return FASTP_GPU_OK;
 }
@@ -2719,23 +2504,22 @@ extern "C" int fastp_gpu_device_upload(fastp_gpu_ctx* ctx, void* dst_dev, const 
     if (bytes == 0) return FASTP_GPU_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipMemcpyAsync(dst_dev, src_host, (size_t)bytes, hipMemcpyHostToDevice, ctx->stream));
-    { int rs_ = sync_main(ctx); if (rs_) return rs_; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return FASTP_GPU_OK;
 }
 extern "C" int fastp_gpu_device_download(fastp_gpu_ctx* ctx, void* dst_host, const void* src_dev, int64_t bytes) {
     if (!ctx || bytes < 0 || (bytes > 0 && (!dst_host || !src_dev))) return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
     if (bytes == 0) return FASTP_GPU_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rj_ = join_aux(ctx, ctx->stream); if (rj_) return rj_; }
     HIP_TRY(ctx, hipMemcpyAsync(dst_host, src_dev, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
-    { int rs_ = sync_main(ctx); if (rs_) return rs_; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return FASTP_GPU_OK;
 }
 
 extern "C" int fastp_gpu_synchronize(fastp_gpu_ctx* ctx) {
     if (!ctx) return FASTP_GPU_E_INVALID;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rs_ = sync_main(ctx); if (rs_) return rs_; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return FASTP_GPU_OK;
 }
 
@@ -2812,7 +2596,6 @@ extern "C" int fastp_gpu_submit_host(fastp_gpu_ctx* ctx, const fastp_gpu_batch* 
     dr.n_adapter_events = (int32_t*)take(sizeof(int32_t));
     rc = stage_exotic(ctx, b, &db, st);
     if (!rc) rc = fastp_gpu_submit_device(ctx, &db, &dr, st);
-    if (!rc) rc = join_aux(ctx, st);   // the duplicate flags of the last launch
     if (rc) {   // copies from the caller's pinned buffers are queued: they must have drained before the caller may reuse them
         (void)hipStreamSynchronize(st);
         return rc;
@@ -2915,7 +2698,6 @@ extern "C" int fastp_gpu_submit_host_async(fastp_gpu_ctx* ctx, const fastp_gpu_b
     dr.n_adapter_events = (int32_t*)take(sizeof(int32_t));
     rc = stage_exotic(ctx, b, &db, st);
     if (!rc) rc = fastp_gpu_submit_device(ctx, &db, &dr, st);
-    if (!rc) rc = join_aux(ctx, st);   // the duplicate flags of the last launch
     if (rc) {   // copies from the caller's pinned buffers are queued: they must have drained before the caller may reuse them
         (void)hipStreamSynchronize(st);
         return rc;
@@ -3047,7 +2829,7 @@ extern "C" int fastp_gpu_reset(fastp_gpu_ctx* ctx) {
     if (ctx->d_post_seen) HIP_TRY(ctx, hipMemsetAsync(ctx->d_post_seen, 0, sizeof(u64), ctx->stream));
     ctx->units_seen = 0;
     ctx->has_prefix = false;
-    { int rs_ = sync_main(ctx); if (rs_) return rs_; }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return FASTP_GPU_OK;
 }
 

@@ -70,13 +70,6 @@ FQ_DEV u32* lds_nmk(const LdsLayout& L, u32* lds, int R) { return lds + L.nmk + 
 FQ_DEV u32* lds_qual(const LdsLayout& L, u32* lds, int R) { return lds + L.qual + rowoff(R, L.QW); }
 FQ_DEV int* lds_i(u32* lds, int off) { return (int*)(lds + off); }
 
-// barrier over the wavefronts that work on one tile: the whole workgroup, or - two tiles in flight - the half that
-// owns the tile (`lds` is that half's LDS base, `tid` / `nthreads` its view of itself)
-FQ_DEV void tile_sync(const KernelArgs& a, u32* lds, int nthreads) {
-    if (a.L.halves == 2) half_sync(lds + a.L.bar, thread_id() >= nthreads ? 1 : 0, nthreads, a.half_naps);
-    else block_sync();
-}
-
 FQ_DEV u32 code_at(const u32* srow, int j) { return (srow[j >> 4] >> ((j & 15) * 2)) & 3u; }
 FQ_DEV u32 qchar_at(const u8* q, int j) { return q[j] & 0x7Fu; }
 FQ_DEV bool isn_at(const u8* q, int j) { return (q[j] & 0x80u) != 0; }
@@ -206,25 +199,6 @@ FQ_DEV void tile_stage(const KernelArgs& a, u32* lds, int tile_first, int tid, i
         const int ci = tid + i * nthreads;
         if (ci < nq) *(v4u*)(lds + L.qual + 4 * ci) = q[i];
     }
-}
-
-// one dword of every 128-byte line of the tile that starts at unit tile_first (rows that exist only): pulls the
-// tile into L2 / the Infinity Cache while the current one is processed.  Returns the touch's register (touch_done).
-FQ_DEV u32 tile_warm(const KernelArgs& a, int tile_first, int tid) {
-    const LdsLayout& L = a.L;
-    const int rows = imax(0, imin(L.P, a.n - tile_first));
-    const int ql = (rows * L.QW * 4 + 127) >> 7, sl = (rows * L.SW * 4 + 127) >> 7;   // lines per mate
-    const int per = ql + sl;
-    const int lines = a.p.paired ? 2 * per : per;
-    const u32* q0 = scalar_ptr(a.qual[0]) + (size_t)tile_first * L.QW;
-    const u32* s0 = scalar_ptr(a.seq[0]) + (size_t)tile_first * L.SW;
-    const u32* q1 = a.p.paired ? scalar_ptr(a.qual[1]) + (size_t)tile_first * L.QW : q0;
-    const u32* s1 = a.p.paired ? scalar_ptr(a.seq[1]) + (size_t)tile_first * L.SW : s0;
-    const int t = imin(tid, lines - 1);    // lanes past the last line touch it again: no branch around the load
-    const int m = t >= per ? 1 : 0;
-    const int k = t - (m ? per : 0);
-    const u32* p = k < ql ? (m ? q1 : q0) + 32 * k : (m ? s1 : s0) + 32 * (k - ql);
-    return touch_begin(lines > 0 ? p : q0);
 }
 
 // total quality (N flag masked off) of the windows [4c+k, 4c+k+w), k = 0..3, of one row:
@@ -643,7 +617,7 @@ FQ_DEV void phase_stats_both(const KernelArgs& a, u32* lds, int n_valid, int tid
         for (int sh = 1; sh < 64; sh <<= 1) agg_cnt += shfl_xor(agg_cnt, sh);
         if (lane == 0 && agg_cnt) lds_add_u32((u32*)(ldsw + (int)mode_ta + QT_COUNT * 4), agg_cnt);
     }
-    tile_sync(a, lds, nthreads);
+    block_sync();
     // the queued items, all through the general path
     const int nw = (int)imin((int)*wl_count, L.wl_cap);
     for (int base = tid - lane; base < nw; base += nthreads) {
@@ -1317,7 +1291,7 @@ FQ_DEV void phase_overlap(const KernelArgs& a, u32* lds, int tid, int nthreads, 
         if (dir) overlap_scan<1>(a, lds, u >> 2, u & 3, exact);
         else overlap_scan<0>(a, lds, u >> 2, u & 3, exact);
     }
-    tile_sync(a, lds, nthreads);
+    block_sync();
     // pass 2: lane = candidate
     const int nc = imin((int)lds[L.cand], L.cand_cap);
     for (int i = tid; i < nc; i += nthreads) {
@@ -1328,7 +1302,7 @@ FQ_DEV void phase_overlap(const KernelArgs& a, u32* lds, int tid, int nthreads, 
         if (e & 0x400u) overlap_check<1>(L, lds, v, pr, o, exact);
         else overlap_check<0>(L, lds, v, pr, o, exact);
     }
-    tile_sync(a, lds, nthreads);
+    block_sync();
     if (tid == 0) lds[L.cand] = 0;   // ready for the next use (merge mode analyzes twice per tile)
 }
 
@@ -2187,12 +2161,6 @@ FQ_DEV void phase_filter_se(const KernelArgs& a, u32* lds, int tile_first, int t
 // ---------------------------------------------------------------------------
 // The fused kernel: persistent workgroups, grid-stride over tiles.
 // ---------------------------------------------------------------------------
-// Two tiles are in flight per workgroup: waves [0, W/2) own tile slot 0, waves [W/2, W) slot 1, each with its own
-// barrier (tile_sync) and its own copy of the argument block (same but for the LDS layout, LdsLayout::halves).
-// The halves run the same phase sequence half a tile apart (half 1 starts late), so that while one sits in a phase
-// bound by the LDS pipe (Stats), by latency (the per-read / per-pair phases, the barriers) or by memory (staging),
-// the other one's VALU-bound phases (overlap, hash, masks, metrics) have the SIMDs.  The accumulators are shared:
-// both halves add to the same LDS counters.
 // Duplicate's claim step (see dup_claim_body) issued from inside the fused kernel: the unit's thread fires the
 // atomic_or of its one or two bloom bits at the start of the metrics phase and looks at what they returned only after
 // the filter phase, so the device-scope atomics' latency hides behind two phases of other work.  `raw` keeps the
@@ -2232,38 +2200,34 @@ FQ_DEV void dup_claim_collect(const KernelArgs& a, int tile_first, int tid, cons
 
 // SPLIT: the per-read kernel of the split plan (KernelArgs::split is set; no Stats code in this instantiation)
 template <bool SPLIT>
-FQ_DEV void fused_body(const FusedArgs& fa, u32* lds0) {
-    const int tid0 = thread_id(), nt0 = block_threads();
-    const KernelArgs& a0 = fa.h[0];
-    {   // one-time per workgroup, all waves, slot 0's view: clear the accumulators, stage LUTs / primes / adapters
-        const LdsLayout& L = a0.L;
-        u32* lds = lds0;
-        const int tid = tid0, nt = nt0;
+FQ_DEV void fused_body(const KernelArgs& a, u32* lds) {
+    const int tid = thread_id(), nt = block_threads();
+    const LdsLayout& L = a.L;
+    {   // one-time per workgroup: clear the accumulators, stage LUTs / primes / adapters
         for (int i = tid; i < L.acc_end - L.acc_cyc; i += nt) lds[L.acc_cyc + i] = 0;
-        const int lw = (a0.p.cycles + 2) / 2;  // u16 tables of cycles+1 entries, in dwords
-        const u32* g0 = (const u32*)a0.lut.ov_limit;
-        const u32* g1 = (const u32*)a0.lut.lowq_limit;
-        const u32* g2 = (const u32*)a0.lut.cplx_min;
+        const int lw = (a.p.cycles + 2) / 2;  // u16 tables of cycles+1 entries, in dwords
+        const u32* g0 = (const u32*)a.lut.ov_limit;
+        const u32* g1 = (const u32*)a.lut.lowq_limit;
+        const u32* g2 = (const u32*)a.lut.cplx_min;
         for (int i = tid; i < lw; i += nt) {
             lds[L.lut_ov + i] = g0[i];
             lds[L.lut_lowq + i] = g1[i];
             lds[L.lut_cplx + i] = g2[i];
         }
-        stage_primes(a0, lds, tid, nt);
+        stage_primes(a, lds, tid, nt);
         for (int i = tid; i < 2 * ADAPT_WORDS; i += nt) {
             const int which = i >= ADAPT_WORDS ? 1 : 0;
             const int w = i - which * ADAPT_WORDS;
             u32 v = 0;
-            if (w < MAX_ADAPTER_WORDS) v = which ? a0.p.a2w[w] : a0.p.a1w[w];
+            if (w < MAX_ADAPTER_WORDS) v = which ? a.p.a2w[w] : a.p.a1w[w];
             lds[L.adapt + i] = v;
         }
-        if (a0.p.dup_enabled)
+        if (a.p.dup_enabled)
             for (int i = tid; i < 256; i += nt) {  // duplicate.cpp:92-109: A=7 T=222 C=74 G=31 (codes A0 T1 C2 G3)
                 u32 v = 0;
                 for (int k = 0; k < 4; k++) v |= ((0x1F4ADE07u >> (((i >> (2 * k)) & 3) * 8)) & 0xFFu) << (8 * k);
                 lds[L.val4_lut + i] = v;
             }
-        if (tid < 2 * L.halves) lds[L.bar + (tid >> 1) * L.tile_stride + (tid & 1)] = 0;   // the halves' barrier words
         block_sync();
         for (int i = tid; i < (SPLIT ? 0 : 4 * 128); i += nt) {  // quality table constants (the counters in between stay zero)
             const int q = i & 127;
@@ -2278,26 +2242,12 @@ FQ_DEV void fused_body(const FusedArgs& fa, u32* lds0) {
         }
         block_sync();
     }
-    // from here on each half is its own little workgroup
-    const int nh = a0.L.halves;
-    const int nt = nt0 / nh;
-    const int half = nh == 2 ? (int)uniform((u32)(tid0 >= nt ? 1 : 0)) : 0;
-    const int tid = tid0 - half * nt;
-    const KernelArgs& a = fa.h[half];
-    const LdsLayout& L = a.L;
-    u32* lds = lds0 + half * a0.L.tile_stride;
-    const int vblock = block_id() * nh + half, vgrid = grid_blocks() * nh;
-    if (half) for (int i = 0; i < a.half_skew; i++) nap();
+    const int vblock = block_id(), vgrid = grid_blocks();
     const bool timing_on = a.phase_cycles != nullptr;  // uniform
-    const bool timing = timing_on && tid0 == 0;
+    const bool timing = timing_on && tid == 0;
     u64 tacc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const bool vec = a.prefetch != 0;       // uniform: 16-byte tile copies
-    const bool prefetch = a.prefetch == 1;  // ... issued one tile ahead
-    // Only full tiles take the vector path.  The tile is fetched (all chunks in flight, one wait) when the loop
-    // reaches it; what runs ahead is a one-dword-per-cache-line touch of the NEXT tile (tile_warm: one register for
-    // the length of the N-mask pass instead of the 17 a register-held prefetch keeps for a whole tile - under the
-    // 128-register cap of a 1024-lane workgroup those were spilled, and a spill behind a load is a wait for it),
-    // so the fetch hits L2 / the Infinity Cache.
+    // Only full tiles take the vector path: the tile is fetched (all chunks in flight, one wait) when the loop reaches it.
     for (int tile = vblock; tile < a.tiles; tile += vgrid) {
         const int tile_first = tile * L.P;
         const int n_valid = imin(L.P, a.n - tile_first);
@@ -2308,14 +2258,9 @@ FQ_DEV void fused_body(const FusedArgs& fa, u32* lds0) {
         } else {
             phase_load(a, lds, tile_first, tid, nt);
         }
-        tile_sync(a, lds, nt);
-        const int next = tile + vgrid;
-        const bool touch = prefetch && next < a.tiles;   // uniform
-        u32 warm = 0;
-        if (touch) warm = tile_warm(a, next * L.P, tid);
+        block_sync();
         phase_nmask(a, lds, tid, nt);
-        if (touch) touch_done(warm);
-        tile_sync(a, lds, nt);
+        block_sync();
         FQ_STAMP(0)
 #ifdef FQ_PROFILE_ABLATION
         const u32 skip = a.debug_skip;   // profiling build only: 0 in any real run
@@ -2327,9 +2272,9 @@ FQ_DEV void fused_body(const FusedArgs& fa, u32* lds0) {
             phase_masks(a, lds, n_valid, tid, nt);
             phase_rc(a, lds, tid, nt);
         }
-        if (timing_on) { tile_sync(a, lds, nt); FQ_STAMP(8) }
+        if (timing_on) { block_sync(); FQ_STAMP(8) }
         if (!(skip & 2u)) phase_hash(a, lds, tid, nt);
-        tile_sync(a, lds, nt);
+        block_sync();
         FQ_STAMP(1)
         // Duplicate's claim: fired here by threads that idle through the thin phases (trim runs on the first NR lanes), the
         // hash values are final since the last barrier; collected after the filter phase
@@ -2338,39 +2283,39 @@ FQ_DEV void fused_body(const FusedArgs& fa, u32* lds0) {
         const int claim_unit = tid - (nt >= 2 * L.NR ? nt - L.P : 0);
         if (a.claim_won) dup_claim_issue(a, lds, tile_first, claim_unit, claim);
         if (!(skip & 32u)) phase_trim(a, lds, tile_first, tid, nt);
-        tile_sync(a, lds, nt);
+        block_sync();
         FQ_STAMP(2)
         if (a.p.poly_g) {
             phase_polyg(a, lds, tid, nt);
-            tile_sync(a, lds, nt);
+            block_sync();
         }
         FQ_STAMP(3)
         if (!(skip & 4u)) phase_overlap(a, lds, tid, nt);
         if (a.p.allow_gap) {
             phase_overlap_gap(a, lds, tid, nt);
-            tile_sync(a, lds, nt);
+            block_sync();
         }
         FQ_STAMP(4)
         if (!(skip & 32u)) {
             if (a.p.paired) phase_decide_pe(a, lds, tile_first, tid, nt);
             else phase_decide_se(a, lds, tile_first, tid, nt);
         }
-        tile_sync(a, lds, nt);
+        block_sync();
         if (a.p.overlapped_out) {   // :488-495, in front of merge mode's own analysis (:518) as in the reference
             phase_ovout_begin(a, lds, tile_first, tid, nt);
-            tile_sync(a, lds, nt);
+            block_sync();
             phase_overlap(a, lds, tid, nt, true);
             phase_ovout_end(a, lds, tile_first, tid, nt);
-            tile_sync(a, lds, nt);
+            block_sync();
         }
         if (a.p.merge) {
             phase_overlap(a, lds, tid, nt);
             phase_merge(a, lds, tile_first, tid, nt);
-            tile_sync(a, lds, nt);
+            block_sync();
         }
         FQ_STAMP(5)
         if (!(skip & 8u)) phase_metrics(a, lds, tid, nt);
-        tile_sync(a, lds, nt);
+        block_sync();
         FQ_STAMP(9)
         if (!(skip & 32u)) {
             if (a.p.paired && !a.p.merge) phase_filter_pe_plain(a, lds, tile_first, tid, nt);
@@ -2378,7 +2323,7 @@ FQ_DEV void fused_body(const FusedArgs& fa, u32* lds0) {
             else phase_filter_se(a, lds, tile_first, tid, nt);
         }
         if (a.claim_won) dup_claim_collect(a, tile_first, claim_unit, claim);
-        tile_sync(a, lds, nt);
+        block_sync();
         FQ_STAMP(6)
         // Stats::statRead on what is written out (+ on the original reads in one-pass mode)
         if (!SPLIT && !(skip & 16u)) {
@@ -2386,16 +2331,16 @@ FQ_DEV void fused_body(const FusedArgs& fa, u32* lds0) {
             else if (a.p.merge) phase_stats<ST_POST, true>(a, lds, n_valid, tid, nt);
             else phase_stats<ST_POST, false>(a, lds, n_valid, tid, nt);
         }
-        if (!SPLIT) tile_sync(a, lds, nt);   // split: the barrier behind the filter phase already closed the tile
+        if (!SPLIT) block_sync();   // split: the barrier behind the filter phase already closed the tile
         FQ_STAMP(7)
 #undef FQ_STAMP
     }
     if (timing)
         for (int k = 0; k < 10; k++) g_atomic_add_u64(&a.phase_cycles[k], tacc[k]);
-    // both halves are done: flush this workgroup's accumulators to its slab (plain coalesced stores)
+    // flush this workgroup's accumulators to its slab (plain coalesced stores)
     block_sync();
-    u32* slab = a0.slabs + (size_t)block_id() * a0.slab_dwords;
-    for (int i = tid0; i < a0.slab_dwords; i += nt0) slab[i] = lds0[a0.L.acc_cyc + i];
+    u32* slab = a.slabs + (size_t)block_id() * a.slab_dwords;
+    for (int i = tid; i < a.slab_dwords; i += nt) slab[i] = lds[L.acc_cyc + i];
 }
 
 // ---------------------------------------------------------------------------
@@ -3528,16 +3473,7 @@ FQ_DEV void ovr_count_body(const OvrArgs& o, u32* lds) {
             if (hit >= 0) {  // mOverRepSeq[seq]++, the covered positions of mOverRepSeqDist, i += step (:279-284)
                 const int at = i + hit_b;
                 g_atomic_add_i64(&cnt[hit], 1);
-                if (o.dist_diff[slot]) {
-                    const int e0 = imin(at, M.eval_len), e1 = imin(at + L, M.eval_len);
-                    if (e0 < e1) {
-                        int* dd = o.dist_diff[slot] + (size_t)hit * (M.eval_len + 1);
-                        g_atomic_add_i32(&dd[e0], 1);
-                        g_atomic_add_i32(&dd[e1], -1);
-                    }
-                } else {
-                    for (int pp = at; pp < at + L && pp < M.eval_len; pp++) g_atomic_add_i64(&dist[(size_t)hit * M.eval_len + pp], 1);
-                }
+                for (int pp = at; pp < at + L && pp < M.eval_len; pp++) g_atomic_add_i64(&dist[(size_t)hit * M.eval_len + pp], 1);
                 i = at + L + 1;
                 fresh = true;
             } else {  // the window has slid by nb bases
@@ -3601,16 +3537,7 @@ FQ_DEV void ovr_count_body(const OvrArgs& o, u32* lds) {
             if (hit >= 0) {  // mOverRepSeq[seq]++, the covered positions of mOverRepSeqDist, i += step (:279-284)
                 const int at = i + hit_b;
                 g_atomic_add_i64(&cnt[hit], 1);
-                if (o.dist_diff[slot]) {
-                    const int e0 = imin(at, M.eval_len), e1 = imin(at + L, M.eval_len);
-                    if (e0 < e1) {
-                        int* dd = o.dist_diff[slot] + (size_t)hit * (M.eval_len + 1);
-                        g_atomic_add_i32(&dd[e0], 1);
-                        g_atomic_add_i32(&dd[e1], -1);
-                    }
-                } else {
-                    for (int pp = at; pp < at + L && pp < M.eval_len; pp++) g_atomic_add_i64(&dist[(size_t)hit * M.eval_len + pp], 1);
-                }
+                for (int pp = at; pp < at + L && pp < M.eval_len; pp++) g_atomic_add_i64(&dist[(size_t)hit * M.eval_len + pp], 1);
                 i = at + L + 1;
                 fresh = true;
             } else {  // the window has slid by nb bases
@@ -3622,28 +3549,6 @@ FQ_DEV void ovr_count_body(const OvrArgs& o, u32* lds) {
 }
 #undef OVR_SYM
 
-
-// one lane per (slot, seed) row of the difference arrays: running sums -> mOverRepSeqDist in the counter block, array cleared
-FQ_DEV void ovr_dist_body(const OvrArgs& o) {
-    int t = block_id() * block_threads() + thread_id();
-    for (int slot = 0; slot < 4; slot++) {
-        const OvrMate& M = o.mate[slot >> 1];
-        if (!o.dist_diff[slot]) continue;
-        if (t >= 0 && t < M.n_seeds) {
-            int* dd = o.dist_diff[slot] + (size_t)t * (M.eval_len + 1);
-            int64_t* dist = o.ctr + o.o_dist[slot] + (size_t)t * M.eval_len;
-            int run = 0;
-            for (int p = 0; p < M.eval_len; p++) {
-                const int v = dd[p];
-                if (v) dd[p] = 0;
-                run += v;
-                if (run) g_atomic_add_i64(&dist[p], (int64_t)run);
-            }
-            dd[M.eval_len] = 0;
-        }
-        t -= M.n_seeds;
-    }
-}
 
 // ---------------------------------------------------------------------------
 // FASTQ text -> packed batch: FastqReader::getLine / read

@@ -314,10 +314,8 @@ static int imin_i(int a, int b) { return a < b ? a : b; }
 
 int compute_lds_layout(const DevParams& p, TileConfig& cfg, LdsLayout& L, std::string& err, int hp_nq) {
     const int mates = p.paired ? 2 : 1;
-    const int halves = cfg.halves == 2 ? 2 : 1;
     auto build = [&](int P, LdsLayout& out) {
         memset(&out, 0, sizeof(out));
-        out.halves = halves;
         out.P = P;
         out.NR = mates * P;
         out.SW = p.sw_g;
@@ -326,7 +324,7 @@ int compute_lds_layout(const DevParams& p, TileConfig& cfg, LdsLayout& L, std::s
         out.Cp = (p.cycles + 3) / 4 * 4;
         int o = 0;
         auto take = [&](int n) { int at = o; o += n; return at; };
-        // ---- shared by the tiles in flight: accumulators first (u64 part 8-byte aligned at offset 0), tables ----
+        // ---- shared part: accumulators first (u64 part 8-byte aligned at offset 0), tables ----
         out.acc_cyc = take(cfg.split ? 0 : 4 * N_CLS * out.Cp * 2);
         out.acc_kmer = take(cfg.split ? 0 : 4 * KMER_BINS);
         out.acc_qh = take(cfg.split ? 0 : 4 * 128 * QT_DWORDS);
@@ -354,7 +352,7 @@ int compute_lds_layout(const DevParams& p, TileConfig& cfg, LdsLayout& L, std::s
         o = (o + 3) & ~3;
         out.tile_begin = o;
         // ---- per tile ----
-        out.bar = take(2);
+        take(2);   // (two dwords that stay reserved: the tile arrays keep the offsets the launch geometry tests pin)
         if (o & 1) o++;
         out.hash = take(out.NR * (p.dup_bufnum > 0 ? p.dup_bufnum : 0) * 2);
         {   // trimAndCut predicate masks, only those the options need
@@ -402,7 +400,7 @@ int compute_lds_layout(const DevParams& p, TileConfig& cfg, LdsLayout& L, std::s
         out.ov_flags = take(P);
         o = (o + 3) & ~3;
         out.tile_stride = o - out.tile_begin;
-        out.total = out.tile_begin + halves * out.tile_stride;
+        out.total = out.tile_begin + out.tile_stride;
     };
     if (cfg.P > 0) {
         build(cfg.P, L);
@@ -421,16 +419,6 @@ int compute_lds_layout(const DevParams& p, TileConfig& cfg, LdsLayout& L, std::s
     cfg.P = best;
     build(best, L);
     return FASTP_GPU_OK;
-}
-
-// the layout half h of a workgroup works with: its LDS base sits h * tile_stride dwords higher, so the offsets of
-// everything SHARED between the tiles move down by that much; per-tile offsets stay
-LdsLayout layout_for_half(const LdsLayout& L, int h) {
-    LdsLayout o = L;
-    const int d = h * L.tile_stride;
-    o.acc_cyc -= d; o.acc_kmer -= d; o.acc_qh -= d; o.acc_misc -= d; o.acc_end -= d;
-    o.val4_lut -= d; o.adapt -= d; o.lut_ov -= d; o.lut_lowq -= d; o.lut_cplx -= d; o.hp -= d; o.primes -= d;
-    return o;
 }
 
 }  // namespace fq

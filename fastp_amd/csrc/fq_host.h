@@ -33,7 +33,6 @@ struct TileConfig {
     int threads;      // workgroup size (multiple of 64)
     int P;            // pairs / reads per tile
     int lds_budget;   // bytes of LDS one workgroup may use
-    int halves;       // tiles in flight per workgroup: 2 = each half of the waves owns one (fused_body), 1 = one tile
     int split;        // split plan: no per-cycle / k-mer / histogram accumulators in this kernel's LDS (fq_stats.h)
 };
 
@@ -44,7 +43,6 @@ int build_dev_params(const fastp_gpu_params& in, DevParams& out, HostLuts& luts,
 // hp_nq = HostLuts::dup_nq (0: no byte-plane prime table, the generic hash path is used)
 int compute_lds_layout(const DevParams& p, TileConfig& cfg, LdsLayout& L, std::string& err, int hp_nq = 0);
 
-LdsLayout layout_for_half(const LdsLayout& L, int h);   // see LdsLayout::halves
 
 u32 magic_for(u32 d);  // ceil(2^32 / d)
 

@@ -43,52 +43,6 @@ template <class T> FQ_DEV const T* scalar_ptr(const T* p) {
 #endif
 }
 
-// Touch one dword so that its cache line is pulled into L2 / the Infinity Cache: a load the compiler does not
-// see as one (no wait is scheduled for it).  The destination register belongs to the load until touch_done()
-// has waited for it - call that before the value's register can be given to anything else.
-FQ_DEV u32 touch_begin(const u32* p) {
-#ifdef FQ_HOSTSIM
-    return *p;
-#else
-    u32 v;
-    asm volatile("global_load_dword %0, %1, off" : "=v"(v) : "v"(p) : "memory");
-    return v;
-#endif
-}
-FQ_DEV void touch_done(u32 v) {
-#ifdef FQ_HOSTSIM
-    (void)v;
-#else
-    asm volatile("s_waitcnt vmcnt(0)\n; touched %0" : : "v"(v) : "memory");
-#endif
-}
-
-// 16 bytes per lane from global memory straight into LDS (global_load_lds_dwordx4: no VGPR, asynchronous - counted by vmcnt).
-// The LDS destination is wave-uniform base + lane * 16 whatever the lane asks for, so `lds_wave_base` must be uniform and the
-// image lane-linear.  glds_wait() before anything reads the image.
-FQ_DEV void glds16(const void* g, void* lds_wave_base, int lane) {
-#ifdef FQ_HOSTSIM
-    memcpy((char*)lds_wave_base + 16 * lane, g, 16);
-#else
-    (void)lane;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-#endif
-}
-// 4 bytes per lane the same way (global_load_lds_dword): what a line prefetch needs - the data is never read
-FQ_DEV void glds4(const void* g, void* lds_wave_base, int lane) {
-#ifdef FQ_HOSTSIM
-    memcpy((char*)lds_wave_base + 4 * lane, g, 4);
-#else
-    (void)lane;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)lds_wave_base, 4, 0, 0);
-#endif
-}
-FQ_DEV void glds_wait() {
-#ifndef FQ_HOSTSIM
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-}
-
 // a value that is the same in every lane of the wavefront, moved to a scalar register
 FQ_DEV u32 uniform(u32 v) {
 #ifdef FQ_HOSTSIM
@@ -98,40 +52,6 @@ FQ_DEV u32 uniform(u32 v) {
 #endif
 }
 FQ_DEV void block_sync() { __syncthreads(); }
-// Barrier over ONE HALF of the workgroup's wavefronts (the waves that share a tile): an arrival counter and a
-// generation word in LDS, lane 0 of each wave arrives and then polls the generation with s_sleep between polls.
-// gfx950 has one hardware barrier per workgroup; the two halves must be able to wait independently.
-FQ_DEV void half_sync(u32* bar, int group, int nthreads, int naps) {
-#ifdef FQ_HOSTSIM
-    (void)bar;
-    (void)naps;
-    sim::group_barrier(group, nthreads);
-#else
-    (void)group;
-    const u32 nwaves = (u32)nthreads >> 6;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // this wave's LDS writes are done before it arrives
-    if ((threadIdx.x & 63) == 0) {
-        const u32 gen = __hip_atomic_load(&bar[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        const u32 arrived = __hip_atomic_fetch_add(&bar[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (arrived == nwaves - 1u) {   // last one: reset the count, then open the next generation (LDS executes a wave's operations in order)
-            __hip_atomic_store(&bar[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_fetch_add(&bar[1], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        } else {
-            // poll rarely: every poll is an LDS instruction and a few VALU ones taken from the other half's phases
-            while (__hip_atomic_load(&bar[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == gen) {
-                if (naps <= 0) __builtin_amdgcn_s_sleep(1);
-                else if (naps == 1) __builtin_amdgcn_s_sleep(4);
-                else if (naps == 2) __builtin_amdgcn_s_sleep(16);
-                else __builtin_amdgcn_s_sleep(64);
-            }
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-#endif
-}
-FQ_DEV void nap() {   // ~3 us
-    __builtin_amdgcn_s_sleep(127);
-}
 FQ_DEV u64 cycle_counter() { return (u64)clock64(); }
 FQ_DEV void g_atomic_add_u64(u64* p, u64 v) {
     __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -26,13 +26,17 @@
 #ifndef FQ_LANE_METRICS      // A/B switch: 2 = read 1 from the load sweep's partial sums + the one cut word, the last-staged read straight from the
 #define FQ_LANE_METRICS 2    // stage (default); 0 = round 3's second staging of the quality rows with every dword masked by the window
 #endif
-#ifdef FQ_LANE_NO_FENCE      // A/B switch (tools/gpu_lane_ab3.sh)
+#ifdef FQ_LANE_NO_FENCE      // A/B switch
 #define FQ_LANE_FENCE() ((void)0)
 #else
 #define FQ_LANE_FENCE() sched_fence()
 #endif
 
 namespace fq {
+
+// behind the wavefronts' stretches of LDS: the workgroup's chunk counter, and 64 dwords that stay reserved (a retired prefetch's
+// sink: handing them back changes how many wavefronts fit at the LDS edges that tests/test_launch_geometry.py pins)
+enum { LANE_CTR_DWORDS = 4, LANE_RESERVED_DWORDS = 64 };
 
 // LDS of the lane kernel (dwords from the start of dynamic LDS)
 struct LaneLds {
@@ -50,8 +54,7 @@ struct LaneLds {
     int part_dwords;    // conflict-free; registers do not hold them - ten more live VGPRs spilled 270 dwords at the cap of 168)
     int clist;      // -c on the lane plan, per wavefront: the positions of read 1 that BaseCorrector edited, one bit per base,
     int clist_dwords;   // [SWM / 2 words][lane]: read 1's rows are gone when countQualityMetrics runs (lane_apply_corrected)
-    int ctr;        // the workgroup's own chunk counter (LaneArgs::local_ctr)
-    int sink;       // 64 dwords every wavefront's row prefetches are written to (never read): global_load_lds needs a destination
+    int ctr;        // the workgroup's own chunk counter (LANE_CTR_DWORDS)
     int jkmer;      // --merge on the lane plan (DevParams::merge_lane): [KMER_BINS] behind the MISC_* counters (inside n_misc, so in the
                     // slab) - the merged reads' 5-mers that straddle the junction of the two parts (fastp's index: earliest base high)
     int total;
@@ -60,15 +63,10 @@ struct LaneLds {
 struct LaneArgs {
     KernelArgs k;   // parameters, batch, result arrays (the LDS layout inside is not used)
     LaneLds l;
-    int* chunk_ctr; // zero at launch: chunks beyond every wave's first are handed out by this counter (a static stride
-                    // leaves a third of the waves one chunk short at 21.3 chunks per wave); nullptr = static stride
-    int glds;       // read 2's quality rows come into the stage by global_load_lds while read 1 is hashed (FASTP_GPU_LANE_GLDS, A/B)
-    int local_ctr;  // round 6, the default (FASTP_GPU_LANE_DYNAMIC=2): a workgroup owns a contiguous share of the launch's chunks and
-                    // hands them to its wavefronts from a counter in ITS LDS - the balance of a shared counter inside a CU, none of
-                    // its traffic: the kernel's loads-only skeleton takes 0.58 ms with a static stride, 0.92 with one returning
-                    // global atomic per chunk on one word, 0.78 with one per four chunks (profiles/r06_e_*)
-    int grab;       // FASTP_GPU_LANE_GRAB (round 6): chunks a wavefront takes from the counter at a time
-    int pool;       // with local_ctr: the launch's LAST `pool` chunks belong to no workgroup - a wavefront whose workgroup's share is
+    // A workgroup owns a contiguous share of the launch's chunks and hands them to its wavefronts from a counter in ITS LDS
+    // (LaneLds::ctr): the balance of a shared counter inside a CU, none of its traffic.
+    int* chunk_ctr; // the pool's counter in HBM (never null)
+    int pool;       // the launch's LAST `pool` chunks belong to no workgroup - a wavefront whose workgroup's share is
                     // used up takes them one at a time from chunk_ctr (a word that only ever counts up: a chunk's number in the pool
                     // is what the atomic returns minus pool_base, the host adds `pool` to pool_base per launch - no reset between
                     // launches).  The shares are equal, the work per chunk is not (overlap verifications, trims): the kernel ended
@@ -76,10 +74,6 @@ struct LaneArgs {
     int pool_base;
     int pool_grab;  // chunks per ask of the pool (>= 1): a launch of many small chunks (single-end runs: 156 k of them) would otherwise
                     // put ten thousand returning atomics on the one word while its last part runs
-    int prefetch;   // FASTP_GPU_LANE_PREFETCH (round 6), bit mask: 1 = read 2's rows of the chunk are pulled into L2 while read 1 is
-                    // staged and swept, 2 = read 1's rows of the wavefront's NEXT chunk while read 2 is - one dword per 128-byte line
-                    // by global_load_lds into a sink (no register, no wait): the four row stagings of a chunk then find their lines
-                    // in L2 / the Infinity Cache instead of paying a trip to HBM each
     // --merge with -c: the POST Stats object of read 1 in the counter block, for the (rare) merged read whose tail holds an edited
     // base - the lane that has the corrected tail in registers counts it itself (lane_merge_tail_slow)
     int64_t* post1;
@@ -261,29 +255,6 @@ FQ_DEV void lane_stage_rows(u32* buf, const u32* src, int rows, int stride, int 
         for (int k = 0; k < NB; k++)
             if (base + 64 * k < n16) d4[base + 64 * k] = v[k];
     }
-    if ((bytes & 8) && lane == 0) ((u64*)buf)[2 * n16] = ((const u64*)src)[2 * n16];
-    wave_order();
-}
-
-// Pull `bytes` bytes behind `src` into L2: one dword of every 128-byte line by global_load_lds_dword into `sink` (64 dwords of LDS
-// nobody reads).  Nothing waits for it; the later loads of the same lines by lane_stage_rows are L2 hits.
-FQ_DEV void lane_prefetch_lines(u32* sink, const u32* src, int bytes, int lane, int step) {
-    for (int off = lane * step; off < bytes; off += 64 * step) glds4((const char*)src + off, (char*)sink, lane);
-}
-
-// The same copy without registers (round 5): global_load_lds_dwordx4, 16 bytes per lane straight into the stage, asynchronous.
-// Issued for read 2's quality rows as soon as read 1 is done with the stage; Duplicate's hash of read 1 runs while they are on
-// their way (lane_body); lane_stage_rows_done() before the sweep.  The image is the same flat copy (lane-linear: piece k of the
-// wave = vectors 64 k .. 64 k + 63).
-FQ_DEV void lane_stage_rows_async(u32* buf, const u32* src, int rows, int stride, int lane) {
-    wave_order();   // the buffer's previous contents have been read
-    const int n16 = (rows * stride * 4) >> 4;
-    for (int base = 0; base < n16; base += 64)
-        if (base + lane < n16) glds16((const char*)src + 16 * (size_t)(base + lane), (char*)buf + 16 * (size_t)base, lane);
-}
-FQ_DEV void lane_stage_rows_done(u32* buf, const u32* src, int rows, int stride, int lane) {
-    glds_wait();
-    const int bytes = rows * stride * 4, n16 = bytes >> 4;
     if ((bytes & 8) && lane == 0) ((u64*)buf)[2 * n16] = ((const u64*)src)[2 * n16];
     wave_order();
 }
@@ -1131,7 +1102,7 @@ FQ_DEV void lane_emit_corrections(const KernelArgs& a, int lane, int gp, int whi
     if (a.corrections && which >= 0 && cb + rank < a.corr_capacity) { a.corrections[2 * (cb + rank)] = w0; a.corrections[2 * (cb + rank) + 1] = w1; }
 }
 #ifndef FQ_CORR_FLUSH
-#define FQ_CORR_FLUSH 1   // (A/B: 0 = a list entry per round, tools/gpu_r6_n.sh)
+#define FQ_CORR_FLUSH 1   // (A/B: 0 = a list entry per round)
 #endif
 // The same for a whole chunk: a lane keeps its first two edits (the list's second word each; which read: bits 2 / 3 of `st`, how
 // many: its low two bits) and the wavefront takes the slots of all of them with ONE atomic per list when the rounds are over.
@@ -1552,21 +1523,15 @@ FQ_DEV void lane_body(const LaneArgs& la, u32* lds) {
     const u32 thr4 = (u32)p.qual_thr * 0x01010101u;
     const int chunks = (a.n + 63) >> 6;
     const int wpb = nt >> 6;
-    const int nstatic = grid_blocks() * wpb;
-    // Chunks beyond a wavefront's first come from the counter, `grab` at a time while the end of the launch is far (one returning atomic
-    // per chunk is 62 500 of them on ONE word per 4 Mi pairs: a word takes ~88 per microsecond - MI355X_MICROARCH.md, "dequeue" - which
-    // bounds the kernel at 0.7 ms whatever else it does), one at a time over the last chunks so that the wavefronts still end together
-    int nx = 0, gsz = 1;
-    const bool LC = la.local_ctr != 0;                          // (uniform)
-    const int grab = (la.chunk_ctr && !LC) ? imax(1, la.grab) : 1;
-    // the workgroup's share of the chunks (local_ctr): the first (chunks % workgroups) workgroups take one more
-    const int pool = (LC && la.chunk_ctr) ? imin(la.pool, chunks) : 0;   // (uniform) the chunks behind the workgroups' shares
+    int nx = 0;
+    // the workgroup's share of the chunks: the first (chunks % workgroups) workgroups take one more
+    const int pool = imin(la.pool, chunks);   // (uniform) the chunks behind the workgroups' shares
     const int shared = chunks - pool;
     const int pg = imax(1, la.pool_grab), pgroups = (pool + pg - 1) / pg;
     const int sq = shared / grid_blocks(), sr = shared - sq * grid_blocks();
-    const int share_lo = LC ? block_id() * sq + imin(block_id(), sr) : 0;
-    const int share_hi = LC ? share_lo + sq + (block_id() < sr ? 1 : 0) : chunks;
-    int chunk_end = (LC ? share_lo + (tid >> 6) : block_id() * wpb + (tid >> 6)) + 1;   // (the range in hand: [chunk, chunk_end))
+    const int share_lo = block_id() * sq + imin(block_id(), sr);
+    const int share_hi = share_lo + sq + (block_id() < sr ? 1 : 0);
+    int chunk_end = share_lo + (tid >> 6) + 1;   // (the range in hand: [chunk, chunk_end))
     int chunk0 = chunk_end - 1;
     bool in_pool = false;                                       // (uniform)
     if (pool && chunk0 >= share_hi) {                           // a share smaller than the workgroup: straight to the pool
@@ -1577,14 +1542,9 @@ FQ_DEV void lane_body(const LaneArgs& la, u32* lds) {
     }
     for (int chunk = chunk0; chunk < (in_pool ? chunks : share_hi);) {       // wave-uniform
         const bool last_in_hand = chunk + 1 == chunk_end;
-        if (LC) {
-            if (in_pool) {   // (the pool's next range is asked for here as well, when the one in hand ends with this chunk)
-                if (last_in_hand && lane == 0) nx = g_atomic_add_i32(la.chunk_ctr, 1) - la.pool_base;
-            } else if (lane == 0) nx = (int)lds_add_ret_u32(&lds[ll.ctr], 1u);   // the workgroup's next chunk, looked at at the loop's end
-        } else if (la.chunk_ctr && last_in_hand) {
-            gsz = (chunk + 4 * grab * nstatic < chunks) ? grab : 1;   // (uniform)
-            if (lane == 0) nx = g_atomic_add_i32(la.chunk_ctr, gsz);   // the next range's first chunk, looked at at the loop's end
-        }
+        if (in_pool) {   // (the pool's next range is asked for here as well, when the one in hand ends with this chunk)
+            if (last_in_hand && lane == 0) nx = g_atomic_add_i32(la.chunk_ctr, 1) - la.pool_base;
+        } else if (lane == 0) nx = (int)lds_add_ret_u32(&lds[ll.ctr], 1u);   // the workgroup's next chunk, looked at at the loop's end
         const int gp = chunk * 64 + lane;
         const bool valid = gp < a.n;
         const int rows = imin(64, a.n - chunk * 64);
@@ -1606,41 +1566,13 @@ FQ_DEV void lane_body(const LaneArgs& la, u32* lds) {
         // each read is trimmed (Filter::trimAndCut) as soon as it is loaded: its window predicate is dead after that
         // DevParams::front_lane (EXT): fr = the read's front in the row (UMI + -f), ft = trimAndCut's part of it (frontTrimmed)
         int fr1 = 0, ft1 = 0, fr2 = 0, ft2 = 0;
-        if (PAIRED && (la.prefetch & 1)) {   // (uniform) read 2's rows on their way to L2 while read 1 is staged and swept
-            const int step = 128 >> ((la.prefetch >> 2) & 3);   // (A/B: bits 2-3 = a dword every 128 / 64 / 32 bytes)
-            lane_prefetch_lines(lds + ll.sink, a.seq[1] + (size_t)(chunk * 64) * p.sw_g, rows * p.sw_g * 4, lane, step);
-            lane_prefetch_lines(lds + ll.sink, a.qual[1] + (size_t)(chunk * 64) * p.qw_g, rows * p.qw_g * 4, lane, step);
-        }
         lane_load_read<SWM, PAIRED>(a, stage, part, a.seq[0], a.qual[0], a.len[0], chunk * 64, rows, lane, valid, win, thr, thr4, r1);
         if (FR) {
             if (valid) lane_front_trim<SWM>(a, r1, (const u8*)(stage + lane * p.qw_g), p.umi_len1, p.trim_front1, p.trim_tail1, fr1, ft1);
         } else if (valid && !lane_trim_and_cut<SWM>(a, r1, (const u8*)(stage + lane * p.qw_g), p.trim_tail1, r1.len)) r1.flags |= RS_NULL;
         sched_fence();
-        if ((la.prefetch & 2) && (la.chunk_ctr || LC)) {   // (uniform) the next chunk's read 1 (its number came back long ago)
-            const int nxc = LC ? share_lo + wpb + (int)uniform((u32)nx) : last_in_hand ? nstatic + (int)uniform((u32)nx) : chunk + 1;
-            if (nxc < share_hi) {
-                const int nrows = imin(64, a.n - nxc * 64);
-                const int step = 128 >> ((la.prefetch >> 2) & 3);
-                lane_prefetch_lines(lds + ll.sink, a.seq[0] + (size_t)(nxc * 64) * p.sw_g, nrows * p.sw_g * 4, lane, step);
-                lane_prefetch_lines(lds + ll.sink, a.qual[0] + (size_t)(nxc * 64) * p.qw_g, nrows * p.qw_g * 4, lane, step);
-            }
-        }
-        // Duplicate::seq2intvector of read 1 in front of read 2's sweep (B > 0, the asynchronous stage): what it needs of read 1
-        // is final, and it covers the round trip of read 2's quality rows
-        const bool GL = PAIRED && B > 0 && la.glds != 0;   // (uniform)
-        u64 hs_early[B > 0 ? B : 1];
         if (PAIRED) {
-            if (GL) {
-                if constexpr (B > 0) {
-                    lane_load_bases<SWM>(a, stage, a.seq[1], a.len[1], chunk * 64, rows, lane, valid, r2);
-                    lane_stage_rows_async(stage, a.qual[1] + (size_t)(chunk * 64) * p.qw_g, rows, p.qw_g, lane);
-                    lane_hash<SWM, B, NPL>(a, lds, ll, r1, 0, hs_early);
-                    lane_stage_rows_done(stage, a.qual[1] + (size_t)(chunk * 64) * p.qw_g, rows, p.qw_g, lane);
-                    lane_sweep_quality<SWM, false>(a, stage, part, lane, win, thr, thr4, r2);
-                }
-            } else {
-                lane_load_read<SWM, false>(a, stage, part, a.seq[1], a.qual[1], a.len[1], chunk * 64, rows, lane, valid, win, thr, thr4, r2);
-            }
+            lane_load_read<SWM, false>(a, stage, part, a.seq[1], a.qual[1], a.len[1], chunk * 64, rows, lane, valid, win, thr, thr4, r2);
             if (FR) {
                 if (valid) lane_front_trim<SWM>(a, r2, (const u8*)(stage + lane * p.qw_g), p.umi_len2, p.trim_front2, p.trim_tail2, fr2, ft2);
             } else if (valid && !lane_trim_and_cut<SWM>(a, r2, (const u8*)(stage + lane * p.qw_g), p.trim_tail2, r2.len)) r2.flags |= RS_NULL;
@@ -1655,12 +1587,7 @@ FQ_DEV void lane_body(const LaneArgs& la, u32* lds) {
         const bool claim = B > 0 && a.claim_won != nullptr;
         if constexpr (B > 0) {
             u64 hs[B], h2[B];
-            if (GL) {
-#pragma unroll
-                for (int i = 0; i < B; i++) hs[i] = hs_early[i];
-            } else {
-                lane_hash<SWM, B, NPL>(a, lds, ll, r1, 0, hs);
-            }
+            lane_hash<SWM, B, NPL>(a, lds, ll, r1, 0, hs);
             if (PAIRED) {
                 lane_hash<SWM, B, NPL>(a, lds, ll, r2, r1.rl0, h2);
 #pragma unroll
@@ -1995,23 +1922,18 @@ FQ_DEV void lane_body(const LaneArgs& la, u32* lds) {
                 if (claim) a.claim_won[g] = (u8)won;
             }
         }
-        // the next chunk: the range in hand, then the counter's (or the static stride's) next range
-        if (LC) {
-            if (in_pool && !last_in_hand) chunk++;
-            else {
-                if (!in_pool) { chunk = share_lo + wpb + (int)shfl((u32)nx, 0); chunk_end = chunk + 1; }
-                if (pool && (in_pool || chunk >= share_hi)) {   // the share is used up: the pool's next chunks (a global atomic, few of them)
-                    int gx = in_pool ? (int)shfl((u32)nx, 0) : -1;   // (asked for at the loop's head; the first one here)
-                    if (gx < 0) gx = lane_pool_take(la, lane);
-                    in_pool = true;
-                    chunk = gx < pgroups ? shared + gx * pg : chunks;
-                    chunk_end = imin(chunk + pg, chunks);
-                }
+        // the next chunk: the range in hand, then the counter's next one
+        if (in_pool && !last_in_hand) chunk++;
+        else {
+            if (!in_pool) { chunk = share_lo + wpb + (int)shfl((u32)nx, 0); chunk_end = chunk + 1; }
+            if (pool && (in_pool || chunk >= share_hi)) {   // the share is used up: the pool's next chunks (a global atomic, few of them)
+                int gx = in_pool ? (int)shfl((u32)nx, 0) : -1;   // (asked for at the loop's head; the first one here)
+                if (gx < 0) gx = lane_pool_take(la, lane);
+                in_pool = true;
+                chunk = gx < pgroups ? shared + gx * pg : chunks;
+                chunk_end = imin(chunk + pg, chunks);
             }
         }
-        else if (!last_in_hand) chunk++;
-        else if (la.chunk_ctr) { chunk = nstatic + (int)shfl((u32)nx, 0); chunk_end = chunk + gsz; }
-        else { chunk += nstatic; chunk_end = chunk + 1; }
     }
     block_sync();
     u32* slab = a.slabs + (size_t)block_id() * a.slab_dwords;

@@ -48,7 +48,6 @@ struct StatsArgs {
     u32* slabs;
     int slab_dwords;
     u32 debug_skip;         // profiling only: 64 no per-cycle atomics, 128 no k-mer atomics, 256 no histogram atomics
-    int form;               // 4: u32 cells, one mate's tables at a time (stats_body4, round 5); 3: round 3's packed u64 cells (stats_body)
     int kc;                 // form 4: copies of the 5-mer table (1, 2 or 4)
     int merge;              // form 4, DevParams::merge_lane: read 2 has no POST Stats object of its own - every base of it is "dropped" in its
                             // pass; a third pass (stats4_tail_pass) counts what swin[1] marks as kept once more into slot 3, the merged
@@ -102,169 +101,9 @@ FQ_DEV void stats_fetch(const StatsArgs& a, const u32* qual, const u32* seq, con
     s.act = tv && 8 * s.h < s.rl0;
 }
 
-// an item with an N among its 8 bases or the 4 before: base by base (dense pass over the work list)
-FQ_DEV void stats_item_general(const StatsArgs* ap, u32* lds, int m, int h, int rl0, int lk, u32 q0, u32 q1, u32 qp, u32 codes, u32 prev8,
-                               int lane) {
-    const StatsArgs& a = *ap;
-    u64* cyc = (u64*)(lds + a.l_cyc);
-    const u32 nb0 = (q0 >> 7) & 0x01010101u, nb1 = (q1 >> 7) & 0x01010101u, nbp = (qp >> 7) & 0x01010101u;
-    // bit i = base j0 - 4 + i is N (before the read start: "invalid" as in the reference, which needs 5 bases)
-    u32 n12 = ((nbp | (nbp >> 7) | (nbp >> 14) | (nbp >> 21)) & 0xFu) | (((nb0 | (nb0 >> 7) | (nb0 >> 14) | (nb0 >> 21)) & 0xFu) << 4) |
-              (((nb1 | (nb1 >> 7) | (nb1 >> 14) | (nb1 >> 21)) & 0xFu) << 8);
-    if (h == 0) n12 |= 0xFu;
-    const u32 c24 = prev8 | (codes << 8);
-    const int j0 = 8 * h;
-    u32* qh = lds + a.l_qh + (lane & (ST_QH_COPIES - 1));
-    for (int k = 0; k < 8; k++) {
-        const int j = j0 + k;
-        if (j >= rl0) break;
-        const u32 q = ((k < 4 ? q0 : q1) >> (8 * (k & 3))) & 0x7Fu;
-        const bool isn = ((n12 >> (4 + k)) & 1u) != 0;
-        const int cls = isn ? (int)CLS_N : (int)((codes >> (2 * k)) & 3u);
-        const int slot = 2 * m + (j < lk ? 1 : 0);
-        lds_add_u64(&cyc[((slot * 8 + k) * N_CLS + cls) * a.Hs + h], stats_inc_of(q));
-        lds_add_u32(&qh[(slot * 128 + (int)q) * ST_QH_COPIES], 1u);
-        if (((n12 >> k) & 0x1Fu) == 0u) lds_add_u32(&lds[a.l_kmer + slot * KMER_BINS + (int)((c24 >> (2 * k)) & 0x3FFu)], 1u);
-    }
-}
-
-FQ_DEV void stats_body(const StatsArgs& a, u32* lds) {
-    const int tid = thread_id(), nt = block_threads(), lane = tid & 63;
-    const int H = a.H;
-    const u32 H8 = (u32)a.Hs * 8u;            // bytes between the classes of one (slot, k)
-    const u32 K8 = (u32)N_CLS * H8;           // bytes between the k of one slot
-    const u32 S8 = 8u * K8;                   // bytes between slots
-    // ---- clear the accumulators, build the character table ----
-    for (int i = tid; i < a.l_total; i += nt) lds[i] = 0;
-    block_sync();
-    for (int e = tid; e < 256; e += nt) {
-        const u32 q = (u32)e & 0x7Fu, kept = (u32)e >> 7;
-        // characters below '!' never occur in a read (the packers refuse them): 0 stands for "no base here" and adds nothing
-        const u64 inc = q < 33u ? 0ull : stats_inc_of(q);
-        u32* t = lds + a.l_lut + 4 * e;
-        t[0] = (u32)inc;
-        t[1] = (u32)(inc >> 32);
-        t[2] = kept ? S8 : 0u;
-        t[3] = kept ? (u32)(KMER_BINS * 4) : 0u;   // k-mer slot offset; "this is a base" = bit 0 of the increment (its count field)
-    }
-    for (int i = tid; i < 9; i += nt) {
-        lds[a.l_mt + 2 * i] = lowmask32(8 * imin(i, 4));
-        lds[a.l_mt + 2 * i + 1] = lowmask32(8 * imax(0, i - 4));
-    }
-    block_sync();
-    const int u0 = block_id() * a.units_per_block;
-    const int nu = imax(0, imin(a.units_per_block, a.n - u0));
-    const int per_mate = nu * H;
-    u8* ldsw = (u8*)lds;
-    const u32x4* lut = (const u32x4*)__builtin_assume_aligned(lds + a.l_lut, 16);
-    u32* wl = lds + a.l_wl;
-    const u32x2* mt = (const u32x2*)__builtin_assume_aligned(lds + a.l_mt, 8);
-    for (int m = 0; m < (a.paired ? 2 : 1); m++) {   // uniform: a mate's arrays and accumulator bases sit in scalar registers
-        const u32* qual = a.qual[m] + (size_t)u0 * a.qw_g;
-        const u32* seq = a.seq[m] + (size_t)u0 * a.sw_g;
-        const u32* swin = a.swin[m] + u0;
-        const u32 slot_d = 2u * (u32)m;       // dropped bases -> the PRE slot, kept ones -> the POST slot (+1)
-        const u32 cyc_m = (u32)a.l_cyc * 4u + slot_d * S8;
-        const u32 kmer_m = (u32)a.l_kmer * 4u + slot_d * (KMER_BINS * 4);
-        const u32 qh_m = (u32)a.l_qh * 4u + slot_d * (512u * ST_QH_COPIES) + (u32)(lane & (ST_QH_COPIES - 1)) * 4u;
-        // The wavefront's mode = the character (with its kept bit) of the first item's first base, fixed at its first
-        // appearance: bases that hit it are counted per lane and added once at the end - most characters of a run are
-        // one value, and as LDS atomics they would all land on one address and serialise.
-        u32 mode_e = 0xFFFFFFFFu;
-        u32 agg_cnt = 0;
-        for (int base = tid - lane; base < per_mate; base += nt) {   // wave-uniform trip count (ballots inside)
-            const int it = base + lane;
-            StatsItem s;
-            stats_fetch(a, qual, seq, swin, it, it < per_mate, s);
-            const u32 nany = (s.q0 | s.q1 | s.qp) & 0x80808080u;   // an N among the 8 bases or the 4 before
-            const bool plain = s.act && nany == 0u;
-            if (s.act && !plain) {                                  // rare: queued for the base-by-base pass
-                const u32 slot = lds_add_ret_u32(wl, 1u);
-                if (slot < (u32)a.wl_cap) wl[1 + slot] = (u32)it | ((u32)m << 31);
-                else stats_item_general(&a, lds, m, s.h, s.rl0, s.lk, s.q0, s.q1, s.qp, s.codes, s.prev8, lane);   // list full: here and now
-            }
-            // bytes of the item that hold a base, and which of those are kept: bit 7 of a quality byte (free: no N
-            // here) becomes "kept", a byte past the read's end becomes character 0 = "no base": it adds nothing
-            const int j0 = 8 * s.h;
-            const int nv = plain ? s.rl0 - j0 : 0, nk = s.lk - j0;   // not plain: eight "no base" characters
-            const u32x2 vm = mt[imax(0, imin(nv, 8))], km = mt[imax(0, imin(nk, 8))];   // byte masks from a 9-row table
-            const u32 v0 = vm.x, v1 = vm.y, k0 = km.x & 0x80808080u, k1 = km.y & 0x80808080u;
-            const u32 e0 = (s.q0 | k0) & v0, e1 = (s.q1 | k1) & v1;
-            if (mode_e == 0xFFFFFFFFu) {                           // wave-uniform
-                const u64 cand = ballot(plain);
-                if (cand) mode_e = shfl(e0 & 0xFFu, ffs64(cand) - 1);
-            }
-            const u32 c24 = s.prev8 | (s.codes << 8);              // bases j0-4 .. j0+7, 2 bits each
-            const u32 cyc0 = cyc_m + (u32)s.h * 8u;
-            const u32 hpos = s.h > 0 ? 1u : 0u;                    // 5-mers need positions >= 4 (stats.cpp:224-266)
-            // the eight table rows first (independent reads, one round trip), then the adds: an add in between would pin
-            // every later read behind it (the compiler cannot tell the table from the counters)
-            // (four at a time: the workgroup's 64 VGPRs per lane do not hold eight rows)
-#pragma unroll
-            for (int kb = 0; kb < 8; kb += 4) {
-                u32x4 t[4];
-#pragma unroll
-                for (int i = 0; i < 4; i++) t[i] = lut[bfe(kb ? e1 : e0, 8 * i, 8)];   // character | kept << 7
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const int k = kb + i;
-                    const u32 e = bfe(kb ? e1 : e0, 8 * i, 8);
-                    lds_add_u64((u64*)(ldsw + mul24(bfe(s.codes, 2 * k, 2), H8) + (cyc0 + t[i].z + (u32)k * K8)), (u64)t[i].x | ((u64)t[i].y << 32));
-                    const u32 one = k < 4 ? (t[i].x & hpos) : (t[i].x & 1u);
-                    lds_add_u32((u32*)(ldsw + ((kmer_m + t[i].w) + (bfe(c24, 2 * k, 10) << 2))), one);
-                    const bool is_mode = e == mode_e;
-                    agg_cnt += is_mode ? 1u : 0u;
-                    // character 0 ("no base") lands in bin 0 of the dropped slot, which the flush leaves out
-                    if (!is_mode) lds_add_u32((u32*)(ldsw + (qh_m + e * (4u * ST_QH_COPIES))), 1u);
-                }
-            }
-        }
-        if (mode_e != 0xFFFFFFFFu) {
-#pragma unroll
-            for (int sh = 1; sh < 64; sh <<= 1) agg_cnt += shfl_xor(agg_cnt, sh);
-            if (lane == 0 && agg_cnt) lds_add_u32(&lds[a.l_qh + (int)(slot_d * 128u + mode_e) * ST_QH_COPIES], agg_cnt);
-        }
-    }
-    block_sync();
-    // ---- the queued items, every lane busy ----
-    const int nw = imin((int)wl[0], a.wl_cap);
-    for (int i = tid; i < nw; i += nt) {
-        const u32 w = wl[1 + i];
-        const int m = (int)(w >> 31);
-        StatsItem s;
-        stats_fetch(a, a.qual[m] + (size_t)u0 * a.qw_g, a.seq[m] + (size_t)u0 * a.sw_g, a.swin[m] + u0, (int)(w & 0x7FFFFFFFu), true, s);
-        stats_item_general(&a, lds, m, s.h, s.rl0, s.lk, s.q0, s.q1, s.qp, s.codes, s.prev8, lane);
-    }
-    block_sync();
-    // ---- flush to this workgroup's slab in the canonical order the slab fold reads ([slot][cycle][class]) ----
-    u32* slab = a.slabs + (size_t)block_id() * a.slab_dwords;
-    const int n_cyc = 4 * a.Cp * N_CLS;
-    for (int i = tid; i < n_cyc; i += nt) {
-        const int slot = i / (a.Cp * N_CLS);
-        const int rem = i - slot * a.Cp * N_CLS;
-        const int pos = rem / N_CLS, cls = rem - pos * N_CLS;
-        const int h = pos >> 3, k = pos & 7;
-        u32 lo = 0, hi = 0;
-        if (h < H) {
-            const int w = a.l_cyc + 2 * (((slot * 8 + k) * N_CLS + cls) * a.Hs + h);
-            lo = lds[w];
-            hi = lds[w + 1];
-        }
-        slab[2 * i] = lo;
-        slab[2 * i + 1] = hi;
-    }
-    for (int i = tid; i < 4 * KMER_BINS; i += nt) slab[2 * n_cyc + i] = lds[a.l_kmer + i];
-    for (int i = tid; i < 4 * 128; i += nt) {
-        u32 v = 0;
-        if (i & 127)   // bin 0 of a slot collects the "no base" characters of the fast path
-            for (int c = 0; c < ST_QH_COPIES; c++) v += lds[a.l_qh + i * ST_QH_COPIES + c];
-        slab[2 * n_cyc + 4 * KMER_BINS + i] = v;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
-// Round 5: the same pass with u32 cells (stats_body4).  What round 3/4's form (stats_body, kept as FASTP_GPU_STATS_V=3)
-// spends on the LDS pipe per base is one table read, one ds_add_u64 into the packed [cnt|q20|q30|qsum] cell (9.2 cycles
+// Form 4: the pass with u32 cells (stats_body4).  What the first form (packed u64 cells for all four slots, retired)
+// spent on the LDS pipe per base was one table read, one ds_add_u64 into the packed [cnt|q20|q30|qsum] cell (9.2 cycles
 // per wave instruction: twice a 32-bit one, profiles/r02c_issue_rate_microbench.txt), one ds_add_u32 into the 5-mer table
 // whose 64 random bins meet in banks (39 % of the pipe's busy cycles, profiles/r04_sq_counters.txt) and the histogram add.
 // Here

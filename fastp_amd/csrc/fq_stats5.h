@@ -27,7 +27,7 @@
 #define FQ_ST5_BOUNDARY 1   // the clean item a trim ends in takes the masked path (a per-base slot) instead of the base-by-base one (A/B: 0.927 -> 0.916 ms, profiles/r06_n_*)
 #endif
 #ifndef FQ_ST5_DEPTH
-#define FQ_ST5_DEPTH 3   // trips whose loads a wavefront keeps in flight (A/B: tools/gpu_r6_c.sh)
+#define FQ_ST5_DEPTH 3   // trips whose loads a wavefront keeps in flight (A/B)
 #endif
 
 namespace fq {

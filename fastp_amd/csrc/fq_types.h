@@ -124,13 +124,9 @@ struct DevLuts {
 
 // LDS layout, all offsets in dwords from the start of dynamic LDS
 struct LdsLayout {
-    // Shared part first (accumulators, tables), then the per-tile arrays: a workgroup stages `halves` tiles at a
-    // time, tile h at +h * tile_stride dwords.  Half h of the workgroup works on an LDS base moved up by that much
-    // and on a copy of this layout whose SHARED offsets are moved down by it (KernelArgs per half).
-    int halves;     // 1 or 2 tiles in flight per workgroup (2: each half of the waves owns one, see fused_body)
+    // Shared part first (accumulators, tables), then the arrays of the tile in flight.
     int tile_begin, tile_stride;   // dwords
-    int bar;        // [2] per tile: arrival count and generation of the half-workgroup barrier
-    int has_hp;     // the byte-plane prime table exists (hp itself may be negative in a half's copy)
+    int has_hp;     // the byte-plane prime table exists
     int P;          // pairs (PE) or reads (SE) per tile
     int NR;         // rows per tile: 2P (PE) or P (SE)
     int SW, QW;     // LDS row strides in dwords = the global row strides: a tile in LDS is a flat copy of
@@ -223,10 +219,6 @@ struct OvrArgs {
     OvrMate mate[2];
     int64_t* ctr;
     int64_t o_count[4], o_dist[4];   // fastp_gpu_counter_layout::overrep_count / overrep_dist
-    // mOverRepSeqDist of a launch as a DIFFERENCE array (round 5): a hit of a seed at `at` covers positions [at, at + L) -
-    // +1 at its start, -1 behind its end, two atomics instead of up to 150; ovr_dist_body takes the running sums into the
-    // int64 block and clears the array.  [slot][n_seeds of the slot's mate][eval_len + 1] i32; nullptr: straight into the block
-    int* dist_diff[4];
     // LDS staging of the counting kernel: the task's symbols ([position][lane] bytes, sym_cap positions) and, when
     // they fit, the seed hash tables (table_lds[m] = dword offset in LDS, or -1: probe the global copy)
     int sym_cap;
@@ -369,8 +361,6 @@ struct KernelArgs {
     u64 dup_bits;       // mBufLenInBits
     const u8* dupflag;  // [n] --dedup: the duplicate decision, taken by the dup kernels BEFORE this launch
     u64* phase_cycles;  // optional [16]: cycles per phase summed over workgroups (debug)
-    int half_skew;      // half 1 starts this many ~3 us sleeps late, so the halves sit in different phases
-    int half_naps;      // poll interval class of the half barrier (0: 64 cycles ... 3: 4096)
     u32 debug_skip;     // profiling only (FASTP_GPU_DEBUG_SKIP): phases left out, results are then meaningless.
                         // 1 masks+rc, 2 hash, 4 overlap, 8 metrics, 16 stats, 32 trim/decide/filter
     // per-workgroup counter slabs: [gridDim][slab_dwords]
@@ -382,11 +372,6 @@ struct KernelArgs {
     // reads and lengths of the four Stats objects itself, and leaves every read's original and kept length in swin_out.
     int split;
     u32* swin_out[2];   // [n] per mate: rlen0 | kept length << 16
-};
-
-// argument block of the fused kernel: one KernelArgs per half-workgroup (identical but for the LDS layout)
-struct FusedArgs {
-    KernelArgs h[2];
 };
 
 }  // namespace fq

@@ -41,7 +41,6 @@ const Idx& grid_dim();
 void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()>& body);
 void syncthreads();
 void wave_barrier();
-void group_barrier(int group, int nthreads);   // barrier over threads [group * nthreads, (group + 1) * nthreads)
 unsigned long long ballot(bool pred);
 int shfl(int v, int src_lane);
 int shfl_xor(int v, int mask);

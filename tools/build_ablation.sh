@@ -1,7 +1,7 @@
 #!/bin/bash
 # The PROFILING build of the library: the same sources with -DFQ_PROFILE_ABLATION, in which FASTP_GPU_DEBUG_SKIP leaves steps out of
 # the kernels (the measured floors under profiles/; results are meaningless then).  The product library (__graft_entry__.build())
-# has no such switch.  Used by the visit scripts through FASTP_GPU_LIB=fastp_amd/libfastp_gpu_abl.so.
+# has no such switch.  Loaded through FASTP_GPU_LIB=fastp_amd/libfastp_gpu_abl.so.
 set -e
 cd "$(dirname "$0")/.."
 C=fastp_amd/csrc

@@ -57,5 +57,4 @@ torch.cuda.synchronize(dev)
 dt = time.perf_counter() - t0
 n = (STEPS // NE) * NE
 print(f"engines {NE} plan {engs[0].plan()} steps {n}: {dt / n * 1e3:.3f} ms per 4 Mi-pair batch, {2 * B * n / dt / 1e6:.1f} Mreads/s "
-      f"(LANE_BLOCKS_PER_CU={os.environ.get('FASTP_GPU_LANE_BLOCKS_PER_CU', '-')} STATS_THREADS={os.environ.get('FASTP_GPU_STATS_THREADS', '-')} "
-      f"STATS_BLOCKS_PER_CU={os.environ.get('FASTP_GPU_STATS_BLOCKS_PER_CU', '-')})", flush=True)
+      f"(STATS_BLOCKS_PER_CU={os.environ.get('FASTP_GPU_STATS_BLOCKS_PER_CU', '-')})", flush=True)
