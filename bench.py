@@ -1,10 +1,16 @@
 #!/usr/bin/env python3
 """bench.py - Mreads/s of the fused per-read path on synthetic 2x150 bp paired-end batches
 resident in HBM (BASELINE.json metric; workload = configs[2]: PE 2x150, auto-adapter via
-overlap + quality-trim), with the kernel's roofline position and the reference's CPU path
-timed beside it.
+overlap + quality-trim), with the kernel's roofline position from the events of the timed steps.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs B] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs B] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: set up, warm up, time the steps, dump the
+outputs if asked, print the JSON line.  --full adds, after the line's own figures and never inside
+the timed region, everything that takes runs of its own: the reference's CPU path on a sample of the
+same workload (`cpu_baseline`), the end-to-end legs on files and their comparison with the reference's
+outputs (`e2e_gpu`, `e2e_dropin`, `e2e_dropin_large`, `e2e_dropin_bgzf`) and the other configurations
+(`other_configs`).
 
 A step = one pass of the hot path (fused kernel + slab fold + duplicate kernels) over one
 batch of B pairs already in HBM.  N > 1: launched by torch.distributed.run, one rank per GPU,
@@ -578,9 +584,12 @@ def main():
     ap.add_argument("--batches", type=int, default=24,
                     help="distinct batches resident per GPU = one run (24 x 4 Mi = 100.7 M pairs: BASELINE configs[2]); steps "
                          "cycle through them and the engine starts a new run (fresh bloom filter, counters) after each cycle")
-    ap.add_argument("--no-extras", action="store_true", help="skip the end-to-end legs and the other configurations")
-    ap.add_argument("--cpu-sample", type=int, default=4_000_000)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what takes runs of its own (single GPU): the CPU baseline, the end-to-end legs "
+                         "against the reference, the other configurations")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the end-to-end legs and the other configurations")
+    ap.add_argument("--cpu-sample", type=int, default=4_000_000, help="with --full: pairs of the sample the CPU baseline and the file legs run on")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline and the legs that need the reference")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
@@ -867,11 +876,12 @@ def main():
             out["compute_roofline"] = compute
         out["config"]["kernel_plan"] = plan
         out["config"]["switches"] = switches   # {} = the library's defaults
-        if world == 1:
+        full = args.full and world == 1
+        if full:
             # the legs below make engines of their own: this one (its streams, bloom filter and the resident batches) is done
             eng.close()
             eng = None
-        if world == 1 and not args.no_cpu:
+        if full and not args.no_cpu:
             resident = None
             torch.cuda.empty_cache()
             have_ref = os.path.exists(os.path.join(ROOT, "oracle", "_ref", "fastp_ref"))
@@ -902,7 +912,7 @@ def main():
                     if big is not None:
                         import shutil
                         shutil.rmtree(big[0], ignore_errors=True)
-        if world == 1 and not args.no_extras:
+        if full and not args.no_extras:
             resident = None
             torch.cuda.empty_cache()
             try:
