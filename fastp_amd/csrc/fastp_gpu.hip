@@ -283,12 +283,19 @@ struct fastp_gpu_ctx {
     // split plan (fq_stats.h): the per-read kernel as small workgroups, Stats::statRead as its own streaming kernel
     bool split = false;
     int st_threads = 0, st_blocks = 0;     // the Stats kernel's workgroup size and the most workgroups it is launched with
-    int st_H = 0, st_Hs = 0, st_lds_dwords = 0, st_slab_dwords = 0;
+    int st_lds_dwords = 0, st_slab_dwords = 0;
     u32* d_corr_int = nullptr; size_t corr_int_cap = 0;      // -c on the lane plan: the launch's corrections (KernelArgs::corr_int) + 1 counter word
     u32* d_corr_chain = nullptr; size_t corr_chain_cap = 0;  // their per-read chains: head[reads] | next[capacity]
-    int st_form = 4, st_kc = 4, st_max_reads = CYC_MAX_READS, st_max_grid = 0;   // the Stats kernel's form: 5 (fq_stats5.h) where it fits, else 4 (fq_stats.h)
-    int st_l_cyc = 0, st_l_kmer = 0, st_l_qh = 0, st_l_lut = 0, st_l_mt = 0, st_l_wl = 0, st_wl_cap = 0;
-    int st_H16 = 0, st_l_ovf = 0;          // form 5 (fq_stats5.h)
+    int st_form = 4, st_max_reads = CYC_MAX_READS, st_max_grid = 0;   // the Stats kernel's form: 5 (fq_stats5.h) where it fits, else 4 (fq_stats.h)
+    // Argument blocks with their constant part filled once (fill_arg_templates, at the end of fastp_gpu_create): a launch copies the
+    // block and sets what differs per launch - pointers, n, first, units per block, debug_skip.  The Stats kernel's geometry (H, Hs,
+    // kc, H16, its LDS offsets) lives in t_stats only: create's sizing writes it there.
+    StatsArgs t_stats = {};
+    ReduceArgs t_reduce = {};
+    TextCtr t_text_ctr = {};
+    LaneArgs t_lane = {};
+    FrontStatsArgs t_front = {};
+    CorrStatsArgs t_corr = {};
     u32* d_st_slabs = nullptr;
     // lane plan (fq_lane.h): one lane per pair, reads in registers - the option family lane_plan_supported() admits
     bool lane = false;
@@ -300,7 +307,7 @@ struct fastp_gpu_ctx {
     // split plans (never null there): Duplicate's losers / winners / finish kernels of a launch run on this stream beside its Stats kernel
     hipStream_t tail = nullptr;
     hipEvent_t ev_k1 = nullptr, ev_tail = nullptr;
-    u32* d_swin[2] = {nullptr, nullptr}; size_t swin_cap = 0;
+    u32* d_swin[2] = {nullptr, nullptr}; size_t swin_cap[2] = {0, 0};
     hipStream_t stream = nullptr;
     // device buffers
     int16_t* d_ov_limit = nullptr;
@@ -534,6 +541,63 @@ static lane_kernel_fn lane_kernel_for(int swm, int B, bool paired, int ext) {
     return ext == 2 ? lane_kernel_pick<2>(swm, B, paired) : ext == 1 ? lane_kernel_pick<1>(swm, B, paired) : lane_kernel_pick<0>(swm, B, paired);
 }
 
+// The constant part of the argument blocks a launch fills (ctx->t_*): the counter layout, the options and the Stats kernel's
+// geometry - nothing of it changes after fastp_gpu_create.
+static void fill_arg_templates(fastp_gpu_ctx* ctx) {
+    const fastp_gpu_counter_layout& cl = ctx->cl;
+    const DevParams& dp = ctx->dp;
+    TextCtr& c = ctx->t_text_ctr;
+    c.filter = cl.filter_stats; c.adapter_reads = cl.adapter_reads; c.adapter_bases = cl.adapter_bases;
+    c.polyx_reads = cl.polyx_reads; c.polyx_bases = cl.polyx_bases; c.correction = cl.correction;
+    c.corrected_reads = cl.corrected_reads; c.merged = cl.merged_pairs; c.isize = cl.isize;
+    for (int k = 0; k < 4; k++) c.stats[k] = cl.stats[k];
+    c.st_reads = cl.st_reads; c.st_length_sum = cl.st_length_sum; c.st_qual_hist = cl.st_qual_hist;
+    c.st_kmer = cl.st_kmer; c.st_cycle = cl.st_cycle; c.cycles = cl.cycles;
+    ReduceArgs& r = ctx->t_reduce;
+    r.L = ctx->L;
+    r.isize_max = dp.isize_max;
+    r.one_pass = dp.stats_one_pass || (ctx->split && (dp.front_lane || dp.corr_lane || dp.merge_lane));
+    r.merge_tail = (ctx->split && dp.merge_lane) ? 1 : 0;
+    if (ctx->split && dp.front_lane) { r.front[0] = dp.lane_front1; r.front[1] = dp.lane_front2; }
+    r.ctr = ctx->d_ctr;
+    r.o_filter = cl.filter_stats; r.o_adapter_reads = cl.adapter_reads; r.o_adapter_bases = cl.adapter_bases;
+    r.o_polyx_reads = cl.polyx_reads; r.o_polyx_bases = cl.polyx_bases; r.o_correction = cl.correction;
+    r.o_corrected_reads = cl.corrected_reads; r.o_merged = cl.merged_pairs; r.o_isize = cl.isize;
+    for (int s = 0; s < 4; s++) r.o_stats[s] = cl.stats[s];
+    r.st_reads = cl.st_reads; r.st_length_sum = cl.st_length_sum; r.st_qual_hist = cl.st_qual_hist;
+    r.st_kmer = cl.st_kmer; r.st_cycle = cl.st_cycle; r.cycles = cl.cycles;
+    if (!ctx->split) return;
+    StatsArgs& sa = ctx->t_stats;   // (H, Hs, kc, H16 and the LDS offsets: set where create chose the kernel's form)
+    sa.paired = dp.paired; sa.sw_g = dp.sw_g; sa.qw_g = dp.qw_g;
+    sa.magic_H = magic_for((u32)sa.H);
+    sa.Cp = ctx->L.Cp;
+    if (dp.front_lane) { sa.front[0] = dp.lane_front1; sa.front[1] = dp.lane_front2; }
+    sa.merge = dp.merge_lane;
+    sa.l_total = ctx->st_lds_dwords;
+    sa.magic_H16 = (ctx->st_form == 5 && sa.Hs) ? magic_for((u32)sa.Hs) : 0u;   // (the magic of the table's columns)
+    sa.front_per_read = dp.front_per_read; sa.fr_stride = dp.front_per_read ? 3 : 0;
+    sa.slabs = ctx->d_st_slabs; sa.slab_dwords = ctx->st_slab_dwords;
+    LaneArgs& la = ctx->t_lane;
+    la.l = ctx->ln_lds;
+    la.chunk_ctr = ctx->d_ln_ctr;
+    la.post1 = ctx->d_ctr + cl.stats[1];
+    la.st_qual_hist = cl.st_qual_hist; la.st_kmer = cl.st_kmer; la.st_cycle = cl.st_cycle; la.cycles = cl.cycles;
+    FrontStatsArgs& fs = ctx->t_front;
+    CorrStatsArgs& cs = ctx->t_corr;
+    fs.paired = cs.paired = dp.paired;
+    fs.sw_g = cs.sw_g = dp.sw_g;
+    fs.qw_g = cs.qw_g = dp.qw_g;
+    for (int m = 0; m < 2; m++) {
+        fs.post[m] = ctx->d_ctr + cl.stats[2 * m + 1];
+        cs.post[m] = ctx->d_ctr + cl.stats[dp.merge_lane ? 1 : 2 * m + 1];
+    }
+    fs.front0[0] = dp.lane_front1; fs.front0[1] = dp.lane_front2;
+    fs.st_cycle = cl.st_cycle; fs.cycles = cl.cycles;
+    cs.merge = dp.merge_lane;
+    cs.front[0] = dp.front_lane ? dp.lane_front1 : 0; cs.front[1] = dp.front_lane ? dp.lane_front2 : 0;
+    cs.st_qual_hist = cl.st_qual_hist; cs.st_kmer = cl.st_kmer; cs.st_cycle = cl.st_cycle; cs.cycles = cl.cycles;
+}
+
 extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fastp_gpu_ctx** out) {
     if (!params || !out) return fail(nullptr, FASTP_GPU_E_INVALID, "null argument");
     *out = nullptr;
@@ -625,47 +689,48 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
     if (tiles_per_block < 1) return fail(nullptr, FASTP_GPU_E_INVALID, "tile too large for the packed counters");
     if (ctx->split) {
         // the Stats kernel: form 5 where its joint table fits the device's LDS and the options allow it (stats5_copies), else form 4
-        ctx->st_H = ctx->dp.qw_g / 2;
+        StatsArgs& sa = ctx->t_stats;
+        sa.H = ctx->dp.qw_g / 2;
         int hb = 0;
         const int kc5 = stats5_copies(ctx->dp, lds_max, &hb);
         if (kc5) {
-            ctx->st_H16 = (ctx->dp.qw_g + 3) / 4;
+            sa.H16 = (ctx->dp.qw_g + 3) / 4;
             // form 5 (fq_stats5.h): the joint table [2][8][4][ST5_QN][H16] of 16-bit cell pairs, KC copies of the mate's 5-mer
             // counters, the packed cells of what the table has no cell for, the histogram of those, a list per wavefront - where it
             // fits one workgroup's LDS (reads of up to 176 bases; merge mode's third pass exists in form 4 only)
             int o = 0;
-            ctx->st_l_cyc = o; o += 2 * 8 * 4 * ST5_QN * hb;
-            ctx->st_l_kmer = o; o += 2 * KMER_BINS * kc5;
+            sa.l_cyc = o; o += 2 * 8 * 4 * ST5_QN * hb;
+            sa.l_kmer = o; o += 2 * KMER_BINS * kc5;
             o = (o + 1) & ~1;
-            ctx->st_l_ovf = o; o += 2 * ctx->L.Cp * N_CLS * 2;
-            ctx->st_l_qh = o; o += 2 * 128;
-            ctx->st_l_wl = o; o += (1024 / 64) * 2 * ST5_WL / 2;   // (u16 entries)
+            sa.l_ovf = o; o += 2 * ctx->L.Cp * N_CLS * 2;
+            sa.l_qh = o; o += 2 * 128;
+            sa.l_wl = o; o += (1024 / 64) * 2 * ST5_WL / 2;   // (u16 entries)
             ctx->st_form = 5;
-            ctx->st_kc = kc5;
-            ctx->st_Hs = hb;                     // the table's columns: all of a read's (st_H16), or a block of them
+            sa.kc = kc5;
+            sa.Hs = hb;                     // the table's columns: all of a read's (H16), or a block of them
             ctx->st_lds_dwords = o;
             ctx->st_max_reads = CYC_MAX_READS;   // (a list entry holds the trip in 10 bits: 16 wavefronts x (64 / hb >= 4) units per trip, <= 256 trips)
         } else {
             // form 4 (fq_stats.h): [2][8][ST4_ROWS][Hs] u32 per-cycle cells of ONE mate, four copies of its 5-mer counters, its histogram;
             // the class stride padded to 32 items (= all 64 banks)
             ctx->st_form = 4;
-            ctx->st_kc = 4;
-            ctx->st_Hs = ctx->st_H < 32 ? 32 : ctx->st_H;
+            sa.kc = 4;
+            sa.Hs = sa.H < 32 ? 32 : sa.H;
             ctx->st_max_reads = ST4_MAX_READS;
             for (;;) {
-                ctx->st_wl_cap = 511;
+                sa.wl_cap = 511;
                 int o = 0;
-                ctx->st_l_cyc = o; o += 2 * 8 * ST4_ROWS * ctx->st_Hs;
-                ctx->st_l_kmer = o; o += 2 * KMER_BINS * ctx->st_kc;
-                ctx->st_l_qh = o; o += ST_QH_COPIES * 2 * 128;
+                sa.l_cyc = o; o += 2 * 8 * ST4_ROWS * sa.Hs;
+                sa.l_kmer = o; o += 2 * KMER_BINS * sa.kc;
+                sa.l_qh = o; o += ST_QH_COPIES * 2 * 128;
                 o = (o + 3) & ~3;
-                ctx->st_l_lut = o; o += 4 * 256;
-                ctx->st_l_mt = o; o += 18 + 2;
-                ctx->st_l_wl = o; o += 1 + ctx->st_wl_cap;
+                sa.l_lut = o; o += 4 * 256;
+                sa.l_mt = o; o += 18 + 2;
+                sa.l_wl = o; o += 1 + sa.wl_cap;
                 ctx->st_lds_dwords = o;
                 if (2 * o * 4 <= lds_max) break;                          // two workgroups per CU
-                if (ctx->st_Hs > ctx->st_H) ctx->st_Hs = ctx->st_H;       // first the padding,
-                else if (ctx->st_kc > 1) ctx->st_kc /= 2;                 // then the copies
+                if (sa.Hs > sa.H) sa.Hs = sa.H;       // first the padding,
+                else if (sa.kc > 1) sa.kc /= 2;                 // then the copies
                 else break;
             }
         }
@@ -759,7 +824,7 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
             if (cap_tiles > 0) mp = std::min(mp, (long long)ctx->blocks * cap_tiles * ctx->L.P);
         }
         if (mp > (1ll << DUP_IDX_BITS) - 1) mp = (1ll << DUP_IDX_BITS) - 1;
-        if (ctx->split && ctx->dp.corr_lane) {   // the launch's correction list (launch_chunk): an entry for every base of every pair
+        if (ctx->split && ctx->dp.corr_lane) {   // the launch's correction list (fill_launch_buffers): an entry for every base of every pair
             // 2^29 entries (6 GiB with the chains) - or, on a card with 64 GiB to spare, just under 2^30: a -c / --merge step of 4 Mi
             // pairs of 2x150 is then ONE launch instead of two (2 * index + 1 still fits an int)
             long long entries = 1ll << 29;
@@ -901,6 +966,7 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
         CREATE_TRY(hipMemsetAsync(ctx->d_phase, 0, 16 * sizeof(u64), ctx->stream));
     }
     CREATE_TRY(hipStreamSynchronize(ctx->stream));
+    fill_arg_templates(ctx);
     fq::timeline("create: end (tables uploaded, bloom filter cleared)");
     return FASTP_GPU_OK;
 }
@@ -1048,10 +1114,164 @@ enum ChunkMode {
     CHUNK_OVERREP,   // the deferred overrepresentation analysis only
 };
 
-static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first, int n, const fastp_gpu_results* res,
-                        hipStream_t st, ChunkMode mode = CHUNK_STREAM, u8* scan_state = nullptr) {
+// the four row arrays of a launch (read 1's twice for single reads) on 16-byte boundaries: what 16-byte row copies need
+static bool rows_aligned16(bool paired, const void* seq1, const void* qual1, const void* seq2, const void* qual2) {
+    const void* ptrs[4] = {seq1, qual1, paired ? seq2 : seq1, paired ? qual2 : qual1};
+    for (const void* q : ptrs)
+        if ((uintptr_t)q & 15u) return false;
+    return true;
+}
+
+enum PerReadKernel { K_LANE, K_SCAN_WIDE, K_SCAN, K_FUSED };
+enum TextPlace { TEXT_NONE, TEXT_BESIDE_LANE, TEXT_BEHIND_ON_TAIL, TEXT_INLINE };
+enum DupPlace { DUP_NOWHERE, DUP_BEFORE_STATS, DUP_ON_TAIL, DUP_AT_END };
+enum MiscFold { MISC_WITH_STATS, MISC_FIRST_ON_TAIL, MISC_LAST_ON_TAIL, MISC_ON_LAUNCH_STREAM };
+enum OvrPlace { OVR_EARLY_ON_TAIL, OVR_AT_END, OVR_DEFERRED };
+
+// Every decision of one launch: what runs, in which form and on which of the two streams (the launch stream - the caller's or
+// the context's own - and ctx->tail).  plan_launch decides once, from the context, the mode and the batch; launch_chunk is the
+// schedule that reads it, and nothing is decided after it.
+struct LaunchPlan {
+    ChunkMode mode = CHUNK_STREAM;
+    // Units with letters outside ACGTN (fastp_gpu_batch::exotic_*; FASTP_GPU_EXACT=1: every unit) take the text kernel
+    // (fq_text.h).  The plan's kernels still run over the whole launch, on a copy of the length arrays in which those units
+    // are EMPTY; the text kernel then runs once over the listed units: it takes back what an empty unit added to the
+    // counters (the same loop on an empty unit, sign -1), adds the real unit, and overwrites the unit's records and hash
+    // values.  Duplicate's kernels run once over the whole launch afterwards: input order holds across both kinds.
+    bool exact = false;
+    int xk0 = 0, xk1 = 0;      // the launch's entries of the batch's list
+    bool xskip = false;        // the lane plan runs the text kernel BESIDE its kernels: the units not to write are listed (KernelArgs::xskip)
+    // the lane kernel copies rows with 16-byte accesses: a batch whose arrays are not 16-byte aligned takes the tile kernel -
+    // but --merge has this plan only in its lane form: there the launch's rows move to 16-byte aligned arrays of the engine
+    PerReadKernel kernel = K_FUSED;
+    bool align_rows = false;
+    // the text kernel of the listed units in front of Duplicate's hash pre-pass as well: it leaves their hash values, nothing else
+    bool text_prepass = false;
+    // TEXT_BESIDE_LANE (round 5): on the tail stream from in front of the lane kernel on, BESIDE the lane kernel (which counts such a
+    // unit as the empty unit it sees and writes nothing of it, KernelArgs::xskip) and the Stats kernel (to which it is an empty
+    // read); Duplicate's kernels wait for both.  A launch with a handful of such units used to wait 2.6 - 3.1 ms for one lane's
+    // walk between the two kernels.
+    // TEXT_BEHIND_ON_TAIL: behind the plan's kernel (the records and hash values of its units are overwritten) - and, in the split
+    // plans, BESIDE the Stats kernel (round 5): the Stats kernel needs nothing of it (the listed units are empty reads to it, the
+    // text kernel adds their Stats itself), only Duplicate's kernels do, so both go to the tail stream.
+    // TEXT_INLINE: behind the plan's kernel on the launch stream.
+    TextPlace text = TEXT_NONE;
+    // the engine's own correction list of this launch (fill_launch_buffers)
+    bool corr_list = false;
+    // Duplicate::checkPair/checkRead over this chunk, in input order.
+    // dedup_prepass: --dedup: hash pass -> duplicate decision -> the per-read kernel reads the decision
+    // dedup_folded: --dedup without the hash pre-pass (round 5, lane plan, plain stream mode): the lane kernel hashes and claims as
+    // without --dedup, Duplicate's tail decides, fq_dedup_apply_kernel takes the duplicates out again before the Stats kernel counts
+    // (not in merge mode: a pair that merges is written out whatever Duplicate says, peprocessor.cpp:523-535)
+    bool dedup_prepass = false, dedup_folded = false;
+    // the claim step inside the per-read kernel (dup_prepare in front of it, dup_tail behind it; otherwise dup_claim_chain, in the
+    // table form - FASTP_GPU_DUP_TABLE - probe + resolve): plain stream mode, one or two bloom buffers (the lane kernel: four as
+    // well), the context's own stream order
+    // ... and a launch with units for the text kernel when that kernel runs beside the lane kernel (TEXT_BESIDE_LANE): the lane kernel
+    // claims nothing for such a unit (KernelArgs::xskip), the text kernel claims its units' bits itself (fq_text.h t_claim) and
+    // Duplicate's tail - which orders the claims by unit index, whoever fired them first - runs behind both
+    bool claim_fused = false;
+    // dup_prepare's clears (128 MB of table for 4 Mi pairs: 21 + 6 us) are needed by the kernels of dup_tail only, not by the kernel
+    // that claims: where dup_tail will run on the tail stream they go there, beside the per-read kernel instead of in front of it
+    // (that stream is past the previous launch's tail by then; the launch stream joins it at the end of every launch)
+    bool clears_on_tail = false;
+    // where what is left of Duplicate behind the per-read kernel runs (dup_tail with the claim fused, else dup_claim_chain):
+    // DUP_BEFORE_STATS: --dedup folded: the decisions are needed before the Stats kernel classifies a base as kept - on the launch stream,
+    //   dedup_apply behind it
+    // DUP_ON_TAIL: the claim ran inside the per-read kernel: what is left of Duplicate (losers / winners / finish) needs nothing of
+    //   the Stats kernel and runs beside it on its own stream; the launch stream joins it before anything else touches the records.
+    //   Or: behind the text kernel, on its stream (the claim is not fused into a launch that has such units inline or behind).
+    // DUP_AT_END: on the launch stream behind the folds (the fused plan; the forms that do not use the tail stream)
+    DupPlace dup_place = DUP_NOWHERE;
+    // the tail stream carries Duplicate's kernels or the text kernel: it records ev_tail, the launch stream waits for it at the end
+    bool join_tail = false;
+    // the slab folds.  The Stats fold: behind the Stats kernel on the launch stream.  The per-read kernel's MISC_* fold needs that
+    // kernel only:
+    // MISC_WITH_STATS: the fused plan has one set of slabs, one fold
+    // MISC_FIRST_ON_TAIL: FIRST on the tail stream.  The Stats kernel's workgroups own every CU (a 1024-lane workgroup at 128 VGPRs is
+    //   the whole register file): a kernel on the tail stream gets through when one of the Stats kernel's two rounds of workgroups
+    //   ends, ONE kernel per such moment (profiles/r06_s_step_timeline.txt, r06_t_step_timeline.txt: each tail kernel "takes" 0.43 -
+    //   0.50 ms, 0.01 - 0.03 alone).  Behind Duplicate's kernels - which the Stats kernel's workgroups starve until its last round
+    //   ends (profiles/r06_s_step_timeline.txt: losers 0.45 ms, winners 0.50 ms beside it, 0.01 / 0.03 alone) - it was 27 + 9 us at
+    //   the very end of every step, with nothing else on the chip.
+    // MISC_LAST_ON_TAIL: beside the Stats kernel, behind Duplicate's chain / the text kernel, when that stream is in use
+    // MISC_ON_LAUNCH_STREAM: behind the Stats fold
+    MiscFold misc_fold = MISC_WITH_STATS;
+    // The overrepresentation analysis needs the records (and --dedup's decisions), nothing of the Stats kernel: OVR_EARLY_ON_TAIL, on
+    // the tail stream BESIDE it (round 5; behind Duplicate's tail / the text kernel when they are there - they write record flags),
+    // joined at the end; OVR_AT_END: the last thing on the launch stream; OVR_DEFERRED: the caller asks for it later
+    // (FASTP_GPU_BATCH_DEFER_OVERREP, fastp_gpu_overrep_device)
+    OvrPlace overrep = OVR_AT_END;
+    bool stats = false;         // the Stats kernel as its own launch
+    bool front_stats = false;   // --cut_front on the lane plan: the reads whose own front is beyond the mate's common one (fq_stats5.h, front_stats_body)
+    bool corr_stats = false;    // -c: the corrected positions' share of the POST Stats moves from the original base / quality to the corrected one
+    // scan state of the whole batch: positions [b->n][B] u64, then masks [b->n] u8
+    u64* scan_pos = nullptr;
+    u8* scan_mask = nullptr;
+};
+
+static LaunchPlan plan_launch(const fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first, int n, ChunkMode mode, u8* scan_state) {
     const Switches& sw = ctx->sw;
+    const DevParams& dp = ctx->dp;
+    const bool stream = mode == CHUNK_STREAM;
+    LaunchPlan p;
+    p.mode = mode;
+    if (b->n_exotic > 0) {
+        p.xk0 = (int)(std::lower_bound(b->exotic_unit, b->exotic_unit + b->n_exotic, first) - b->exotic_unit);
+        p.xk1 = (int)(std::lower_bound(b->exotic_unit, b->exotic_unit + b->n_exotic, first + n) - b->exotic_unit);
+    }
+    p.exact = n > 0 && (ctx->exact_all || p.xk1 > p.xk0);
+    p.xskip = p.exact && ctx->lane && stream && !dp.dedup;
+    const size_t so = (size_t)first * dp.sw_g * 4, qo = (size_t)first * dp.qw_g * 4;
+    const bool aligned = rows_aligned16(dp.paired, (const char*)b->seq1 + so, (const char*)b->qual1 + qo, (const char*)b->seq2 + so, (const char*)b->qual2 + qo);
+    p.align_rows = ctx->lane && !aligned && dp.merge_lane;
+    const bool use_lane = ctx->lane && (aligned || p.align_rows);
+    p.kernel = use_lane ? K_LANE : !ctx->split ? K_FUSED : ctx->cfg.threads > 256 ? K_SCAN_WIDE : K_SCAN;
+    p.dedup_folded = dp.dedup && use_lane && stream && !p.exact && !sw.dup_table && !dp.merge_lane && sw.dedup_fold &&
+                     sw.claim_fused;   // (the fold IS the fused claim: without it the hash pre-pass decides)
+    p.dedup_prepass = dp.dedup && !p.dedup_folded && stream;
+    p.text_prepass = p.exact && (p.dedup_prepass || (mode == CHUNK_PASS1 && dp.dedup));
+    const bool exact_early = p.xskip && use_lane;
+    p.text = !p.exact ? TEXT_NONE : exact_early ? TEXT_BESIDE_LANE : (ctx->split && stream && !dp.dedup) ? TEXT_BEHIND_ON_TAIL : TEXT_INLINE;
+    const bool text_on_tail = p.text == TEXT_BESIDE_LANE || p.text == TEXT_BEHIND_ON_TAIL;
+    p.corr_list = ctx->split && dp.corr_lane && mode != CHUNK_OVERREP && !(mode == CHUNK_PASS1 && dp.dedup);
+    p.claim_fused = dp.dup_enabled && (!dp.dedup || p.dedup_folded) && stream && (dp.dup_bufnum <= 2 || p.dedup_folded) && !sw.dup_table &&
+                    sw.claim_fused && (!p.exact || exact_early);
+    p.clears_on_tail = ctx->split && !p.dedup_folded && n > 0;
+    if (p.dedup_folded && p.claim_fused && n > 0) p.dup_place = DUP_BEFORE_STATS;
+    else if (ctx->split && p.claim_fused && n > 0) p.dup_place = DUP_ON_TAIL;
+    else if (text_on_tail) p.dup_place = dp.dup_enabled ? DUP_ON_TAIL : DUP_NOWHERE;
+    else if (dp.dup_enabled && !dp.dedup) p.dup_place = DUP_AT_END;
+    p.join_tail = p.dup_place == DUP_ON_TAIL || (text_on_tail && p.dup_place == DUP_NOWHERE);
+    p.misc_fold = !ctx->split ? MISC_WITH_STATS : !p.join_tail ? MISC_ON_LAUNCH_STREAM : (p.claim_fused ? MISC_FIRST_ON_TAIL : MISC_LAST_ON_TAIL);
+    p.overrep = (dp.overrep && !(b->flags & FASTP_GPU_BATCH_DEFER_OVERREP) && ctx->split && stream && n > 0) ? OVR_EARLY_ON_TAIL
+                : (b->flags & FASTP_GPU_BATCH_DEFER_OVERREP) ? OVR_DEFERRED : OVR_AT_END;
+    p.stats = ctx->split && n > 0;
+    p.front_stats = p.stats && dp.front_per_read && ctx->lane;
+    p.corr_stats = p.stats && p.corr_list;
+    if (scan_state) {
+        p.scan_pos = (u64*)scan_state + (size_t)first * dp.dup_bufnum;
+        p.scan_mask = scan_state + (size_t)b->n * dp.dup_bufnum * 8 + first;
+    }
+    return p;
+}
+
+struct Launch {   // one launch: what its stage functions share
+    fastp_gpu_ctx* ctx;
+    const fastp_gpu_batch* b;
+    int first, n;
+    hipStream_t st;              // the launch stream (ctx->tail is the other one)
+    const LaunchPlan p;
     KernelArgs a;
+    const u16* true_len[2];      // a.len[] before the text kernel's units were emptied in it
+    int grid, ln_grid, st_grid;  // workgroups (= slabs to fold) of the tile kernel, the lane kernel, the Stats kernel
+};
+
+static int fill_kernel_args(Launch& l, const fastp_gpu_results* res) {
+    fastp_gpu_ctx* ctx = l.ctx;
+    const fastp_gpu_batch* b = l.b;
+    const int first = l.first;
+    KernelArgs& a = l.a;
     memset(&a, 0, sizeof(a));
     a.p = ctx->dp;
     a.lut.ov_limit = (const u16*)ctx->d_ov_limit;
@@ -1069,13 +1289,12 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
     {   // vector (16-byte) tile copies need aligned rows and a tile that fits the registers
         const size_t qchunks = (size_t)ctx->L.NR * ctx->dp.qw_g / 4, schunks = (size_t)ctx->L.NR * ctx->dp.sw_g / 4;
         const size_t tile_threads = (size_t)ctx->cfg.threads;
-        bool ok = (ctx->L.P % 2 == 0) && (first % 2 == 0) && qchunks <= (size_t)PF_Q * tile_threads &&
-                  schunks <= (size_t)PF_S * tile_threads && (size_t)ctx->L.NR <= tile_threads;
-        const void* ptrs[4] = {b->seq1, b->qual1, ctx->dp.paired ? b->seq2 : b->seq1, ctx->dp.paired ? b->qual2 : b->qual1};
-        for (const void* q : ptrs) ok = ok && (((uintptr_t)q & 15u) == 0);
+        const bool ok = (ctx->L.P % 2 == 0) && (first % 2 == 0) && qchunks <= (size_t)PF_Q * tile_threads &&
+                        schunks <= (size_t)PF_S * tile_threads && (size_t)ctx->L.NR <= tile_threads &&
+                        rows_aligned16(ctx->dp.paired, b->seq1, b->qual1, b->seq2, b->qual2);
         a.prefetch = ok ? 2 : 0;
     }
-    a.n = n;
+    a.n = l.n;
     a.first = first;
     a.batch_flags = b->flags;
     const size_t swg = ctx->dp.sw_g, qwg = ctx->dp.qw_g;
@@ -1100,333 +1319,299 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
         a.adapter_events_capacity = res->adapter_events_capacity;
         a.n_adapter_events = res->n_adapter_events;
     }
-    // Units with letters outside ACGTN (fastp_gpu_batch::exotic_*; FASTP_GPU_EXACT=1: every unit) take the text kernel
-    // (fq_text.h).  The plan's kernels still run over the whole launch, on a copy of the length arrays in which those units
-    // are EMPTY; the text kernel then runs once over the listed units: it takes back what an empty unit added to the
-    // counters (the same loop on an empty unit, sign -1), adds the real unit, and overwrites the unit's records and hash
-    // values.  Duplicate's kernels run once over the whole launch afterwards: input order holds across both kinds.
-    int xk0 = 0, xk1 = 0;
-    if (b->n_exotic > 0) {
-        xk0 = (int)(std::lower_bound(b->exotic_unit, b->exotic_unit + b->n_exotic, first) - b->exotic_unit);
-        xk1 = (int)(std::lower_bound(b->exotic_unit, b->exotic_unit + b->n_exotic, first + n) - b->exotic_unit);
-    }
-    const bool exact = n > 0 && (ctx->exact_all || xk1 > xk0);
-    const u16* true_len[2] = {a.len[0], a.len[1]};
-    if (exact) {
-        const int mates = ctx->dp.paired ? 2 : 1;
-        int rx = ensure(ctx, (void**)&ctx->d_x_len, &ctx->x_len_cap, (size_t)2 * n * sizeof(u16));
-        if (rx) return rx;
-        for (int m = 0; m < mates; m++) {
-            u16* copy = ctx->d_x_len + (size_t)m * n;
-            if (ctx->exact_all) HIP_TRY(ctx, hipMemsetAsync(copy, 0, (size_t)n * sizeof(u16), st));
-            else HIP_TRY(ctx, hipMemcpyAsync(copy, a.len[m], (size_t)n * sizeof(u16), hipMemcpyDeviceToDevice, st));
-            a.len[m] = copy;
-        }
-        // the lane plan runs the text kernel BESIDE its kernels: the lane kernel is told which units not to write (xskip)
-        u8* skip = nullptr;
-        if (ctx->lane && mode == CHUNK_STREAM && !ctx->dp.dedup) {
-            rx = ensure(ctx, (void**)&ctx->d_x_skip, &ctx->x_skip_cap, (size_t)n);
-            if (rx) return rx;
-            skip = ctx->d_x_skip;
-            HIP_TRY(ctx, hipMemsetAsync(skip, ctx->exact_all ? 1 : 0, (size_t)n, st));
-            a.xskip = skip;
-        }
-        if (!ctx->exact_all) {
-            TextMaskArgs mk;
-            mk.units = ctx->d_x_unit + xk0;
-            mk.count = xk1 - xk0;
-            mk.first = first;
-            mk.skip = skip;
-            mk.len[0] = ctx->d_x_len;
-            mk.len[1] = mates == 2 ? ctx->d_x_len + n : nullptr;
-            hipLaunchKernelGGL(fq_text_mask_kernel, dim3((mk.count + 255) / 256), dim3(256), 0, st, mk);
-            HIP_TRY(ctx, hipGetLastError());
-        }
-    }
-    // scan state of the whole batch: positions [b->n][B] u64, then masks [b->n] u8
-    u64* scan_pos = scan_state ? (u64*)scan_state + (size_t)first * ctx->dp.dup_bufnum : nullptr;
-    u8* scan_mask = scan_state ? scan_state + (size_t)b->n * ctx->dp.dup_bufnum * 8 + first : nullptr;
-    u64* dup_pos_buf = nullptr;
-    if (ctx->dp.dup_enabled && mode != CHUNK_OVERREP) {
-        int rc = ensure(ctx, (void**)&ctx->d_dup_pos, &ctx->dup_pos_cap, (size_t)n * ctx->dp.dup_bufnum * 8);
-        if (rc) return rc;
-        dup_pos_buf = ctx->d_dup_pos;
-        a.dup_pos = dup_pos_buf;
-    }
+    l.true_len[0] = a.len[0];
+    l.true_len[1] = a.len[1];
     a.split = ctx->split ? 1 : 0;
-    const bool corr_lane = ctx->split && ctx->dp.corr_lane && mode != CHUNK_OVERREP && !(mode == CHUNK_PASS1 && ctx->dp.dedup);
-    if (corr_lane) {
-        // the engine's own correction list of this launch.  A pair can have as many edits as its overlap is long (only the first
-        // 50 bases are held to the mismatch limit, overlapanalysis.cpp:34-44): the list is sized for that - it cannot overflow,
-        // and set_launch_size keeps it below 2^29 entries (2^30 where the card has the memory to spare: laid out for 288 GB of HBM)
-        const size_t cap = (size_t)n * (size_t)ctx->dp.max_len;
-        const int rc0 = ensure(ctx, (void**)&ctx->d_corr_int, &ctx->corr_int_cap, (cap * 2 + 4) * 4);
-        if (rc0) return rc0;
-        a.n_corr_int = (int*)ctx->d_corr_int;
-        a.corr_int = ctx->d_corr_int + 4;
-        a.corr_int_cap = (int)std::min<size_t>(cap, 0x7FFFFFFF);
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_corr_int, 0, 16, st));
-    }
-    if (ctx->split) {
-        const size_t need = ((size_t)n * 4 + 255) & ~(size_t)255;
-        if (need > ctx->swin_cap) {
-            for (int m = 0; m < 2; m++) {
-                if (ctx->d_swin[m]) HIP_TRY(ctx, hipFree(ctx->d_swin[m]));
-                ctx->d_swin[m] = nullptr;
-                HIP_TRY(ctx, hipMalloc((void**)&ctx->d_swin[m], need + need / 4));
-            }
-            ctx->swin_cap = need + need / 4;
-        }
-        a.swin_out[0] = ctx->d_swin[0];
-        a.swin_out[1] = ctx->d_swin[1];
-    }
     a.phase_cycles = ctx->d_phase;
     // The product library has no switch that changes a result: FASTP_GPU_DEBUG_SKIP (steps left out of the kernels, for the measured
     // floors under profiles/) exists only in a library built with -DFQ_PROFILE_ABLATION (tools/build_ablation.sh).  Bit 512 is a TEST
     // switch that leaves every result as it is (each merged read's second part counted by the lane kernel, fq_lane.h).
 #ifdef FQ_PROFILE_ABLATION
-    a.debug_skip = (u32)sw.debug_skip & ~512u;
+    a.debug_skip = (u32)ctx->sw.debug_skip & ~512u;
 #else
     a.debug_skip = 0;
 #endif
-    if (sw.test_merge_slow) a.debug_skip |= 512u;
+    if (ctx->sw.test_merge_slow) a.debug_skip |= 512u;
     a.slabs = ctx->d_slabs;
     a.slab_dwords = ctx->slab_dwords;
-    a.tiles = (n + ctx->L.P - 1) / ctx->L.P;
-    const int grid = a.tiles < ctx->blocks ? a.tiles : ctx->blocks;
-    hipStream_t st_main = st;
-    const fastp_gpu_counter_layout& cl = ctx->cl;
-    int rc;
+    a.tiles = (l.n + ctx->L.P - 1) / ctx->L.P;
+    l.grid = a.tiles < ctx->blocks ? a.tiles : ctx->blocks;
+    return 0;
+}
 
-    // the lane kernel copies rows with 16-byte accesses: a batch whose arrays are not 16-byte aligned takes the tile kernel
-    bool use_lane = ctx->lane;
-    {
-        const void* ptrs[4] = {a.seq[0], a.qual[0], ctx->dp.paired ? a.seq[1] : a.seq[0], ctx->dp.paired ? a.qual[1] : a.qual[0]};
-        for (const void* q : ptrs) use_lane = use_lane && (((uintptr_t)q & 15u) == 0);
+// the plan's kernels see the text kernel's units as EMPTY: the launch's copies of the length arrays, and the lane kernel's list of
+// the units not to write
+static int mask_exotic_units(Launch& l) {
+    fastp_gpu_ctx* ctx = l.ctx;
+    const int n = l.n, mates = ctx->dp.paired ? 2 : 1;
+    int rx = ensure(ctx, (void**)&ctx->d_x_len, &ctx->x_len_cap, (size_t)2 * n * sizeof(u16));
+    if (rx) return rx;
+    for (int m = 0; m < mates; m++) {
+        u16* copy = ctx->d_x_len + (size_t)m * n;
+        if (ctx->exact_all) HIP_TRY(ctx, hipMemsetAsync(copy, 0, (size_t)n * sizeof(u16), l.st));
+        else HIP_TRY(ctx, hipMemcpyAsync(copy, l.a.len[m], (size_t)n * sizeof(u16), hipMemcpyDeviceToDevice, l.st));
+        l.a.len[m] = copy;
     }
-    if (ctx->lane && !use_lane && ctx->dp.merge_lane) {
-        // --merge has this plan only in its lane form: the launch's rows move to 16-byte aligned arrays of the engine
+    u8* skip = nullptr;
+    if (l.p.xskip) {
+        rx = ensure(ctx, (void**)&ctx->d_x_skip, &ctx->x_skip_cap, (size_t)n);
+        if (rx) return rx;
+        skip = ctx->d_x_skip;
+        HIP_TRY(ctx, hipMemsetAsync(skip, ctx->exact_all ? 1 : 0, (size_t)n, l.st));
+        if (l.p.text == TEXT_BESIDE_LANE) l.a.xskip = skip;
+    }
+    if (!ctx->exact_all) {
+        TextMaskArgs mk;
+        mk.units = ctx->d_x_unit + l.p.xk0;
+        mk.count = l.p.xk1 - l.p.xk0;
+        mk.first = l.first;
+        mk.skip = skip;
+        mk.len[0] = ctx->d_x_len;
+        mk.len[1] = mates == 2 ? ctx->d_x_len + n : nullptr;
+        hipLaunchKernelGGL(fq_text_mask_kernel, dim3((mk.count + 255) / 256), dim3(256), 0, l.st, mk);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return 0;
+}
+
+// the engine's buffers a launch of n units needs, whatever the mode
+static int fill_launch_buffers(Launch& l) {
+    fastp_gpu_ctx* ctx = l.ctx;
+    KernelArgs& a = l.a;
+    const int n = l.n;
+    int rc;
+    if (ctx->dp.dup_enabled && l.p.mode != CHUNK_OVERREP) {
+        rc = ensure(ctx, (void**)&ctx->d_dup_pos, &ctx->dup_pos_cap, (size_t)n * ctx->dp.dup_bufnum * 8);
+        if (rc) return rc;
+        a.dup_pos = ctx->d_dup_pos;
+    }
+    if (l.p.corr_list) {
+        // the engine's own correction list of this launch.  A pair can have as many edits as its overlap is long (only the first
+        // 50 bases are held to the mismatch limit, overlapanalysis.cpp:34-44): the list is sized for that - it cannot overflow,
+        // and set_launch_size keeps it below 2^29 entries (2^30 where the card has the memory to spare: laid out for 288 GB of HBM)
+        const size_t cap = (size_t)n * (size_t)ctx->dp.max_len;
+        rc = ensure(ctx, (void**)&ctx->d_corr_int, &ctx->corr_int_cap, (cap * 2 + 4) * 4);
+        if (rc) return rc;
+        a.n_corr_int = (int*)ctx->d_corr_int;
+        a.corr_int = ctx->d_corr_int + 4;
+        a.corr_int_cap = (int)std::min<size_t>(cap, 0x7FFFFFFF);
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_corr_int, 0, 16, l.st));
+    }
+    if (ctx->split)
+        for (int m = 0; m < 2; m++) {
+            rc = ensure(ctx, (void**)&ctx->d_swin[m], &ctx->swin_cap[m], ((size_t)n * 4 + 255) & ~(size_t)255);
+            if (rc) return rc;
+            a.swin_out[m] = ctx->d_swin[m];
+        }
+    if (l.p.align_rows)
         for (int k = 0; k < 4; k++) {
             const size_t bytes = (size_t)n * (size_t)((k & 1) ? ctx->dp.qw_g : ctx->dp.sw_g) * 4;
             rc = ensure(ctx, (void**)&ctx->d_al[k], &ctx->al_cap[k], bytes + 256);
             if (rc) return rc;
             const u32* src = (k & 1) ? a.qual[k >> 1] : a.seq[k >> 1];
-            if (bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_al[k], src, bytes, hipMemcpyDeviceToDevice, st));
+            if (bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_al[k], src, bytes, hipMemcpyDeviceToDevice, l.st));
             if (k & 1) a.qual[k >> 1] = ctx->d_al[k]; else a.seq[k >> 1] = ctx->d_al[k];
         }
-        use_lane = true;
-    }
-    // Duplicate::checkPair/checkRead over this chunk, in input order (probe + resolve)
-    // --dedup without the hash pre-pass (round 5, lane plan, plain stream mode): the lane kernel hashes and claims as without
-    // --dedup, Duplicate's tail decides, fq_dedup_apply_kernel takes the duplicates out again before the Stats kernel counts
-    // (not in merge mode: a pair that merges is written out whatever Duplicate says, peprocessor.cpp:523-535)
-    const bool dedup_folded = ctx->dp.dedup && use_lane && mode == CHUNK_STREAM && !exact && !sw.dup_table &&
-                              !ctx->dp.merge_lane && sw.dedup_fold &&
-                              sw.claim_fused;   // (the fold IS the fused claim: without it the hash pre-pass decides)
-    // the claim step inside the fused kernel: plain stream mode, one or two bloom buffers (the lane kernel: four as well), the
-    // context's own stream order
-    // ... and a launch with units for the text kernel when that kernel runs beside the lane kernel (exact_early below): the lane kernel
-    // claims nothing for such a unit (KernelArgs::xskip), the text kernel claims its units' bits itself (fq_text.h t_claim) and
-    // Duplicate's tail - which orders the claims by unit index, whoever fired them first - runs behind both
-    const bool exact_early = exact && use_lane && a.xskip != nullptr;
-    const bool claim_fused = ctx->dp.dup_enabled && (!ctx->dp.dedup || dedup_folded) && mode == CHUNK_STREAM &&
-                             (ctx->dp.dup_bufnum <= 2 || dedup_folded) && !sw.dup_table && sw.claim_fused &&
-                             (!exact || exact_early);
-    // the text kernel (fq_text.h): a wavefront per listed unit, its texts in the wavefront's stretch of LDS, Stats' per-base
-    // counters in the workgroup's LDS tables (added to d_ctr once), everything else straight into d_ctr
-    auto launch_exact = [&](int hash_only, hipStream_t xst = nullptr) -> int {
-        hipStream_t st = xst ? xst : st_main;   // (shadows the launch stream: the text kernel may run beside the Stats kernel)
-        TextArgs e;
-        memset(&e, 0, sizeof(e));
-        e.k = a;
-        const fastp_gpu_counter_layout& c = ctx->cl;
-        e.c.filter = c.filter_stats; e.c.adapter_reads = c.adapter_reads; e.c.adapter_bases = c.adapter_bases;
-        e.c.polyx_reads = c.polyx_reads; e.c.polyx_bases = c.polyx_bases; e.c.correction = c.correction;
-        e.c.corrected_reads = c.corrected_reads; e.c.merged = c.merged_pairs; e.c.isize = c.isize;
-        for (int k = 0; k < 4; k++) e.c.stats[k] = c.stats[k];
-        e.c.st_reads = c.st_reads; e.c.st_length_sum = c.st_length_sum; e.c.st_qual_hist = c.st_qual_hist;
-        e.c.st_kmer = c.st_kmer; e.c.st_cycle = c.st_cycle; e.c.cycles = c.cycles;
-        e.ctr = ctx->d_ctr;
-        e.k.len[0] = true_len[0];
-        e.k.len[1] = true_len[1];
-        e.x_n = b->n_exotic;
-        e.x_unit = ctx->d_x_unit;
-        e.x_all = ctx->exact_all ? 1 : 0;
-        e.x_k0 = xk0;
-        e.x_count = ctx->exact_all ? n : xk1 - xk0;
-        e.x_dense = b->exotic_dense;
-        for (int m = 0; m < 2; m++) { e.x_text[m] = b->exotic_text[m]; e.x_off[m] = b->exotic_off[m]; }
-        e.ML = (ctx->dp.max_len + 8 + 7) & ~7;
-        e.hash_only = hash_only;
-        // Stats' per-base tables of a workgroup in LDS when they fit beside the wavefronts' texts (not the hash pre-pass, which
-        // counts nothing; reads too long for it add to the block with global atomics)
-        const size_t text_bytes = (size_t)TEXT_WAVES * text_wave_bytes(e.ML);
-        const int slot_dwords = 34 * (int)c.cycles + 1024 + 128;
-        const int slots = !ctx->dp.paired ? 2 : ctx->dp.merge ? 3 : 4;   // the Stats objects a unit can reach
-        const bool lds_tables = !hash_only && (size_t)slots * slot_dwords * 4 + text_bytes <= (size_t)aux_lds_cap(ctx);
-        e.lds_slot_dwords = lds_tables ? slot_dwords : 0;
-        e.lds_slots = lds_tables ? slots : 0;
-        const int blocks = std::max(1, std::min((e.x_count + TEXT_WAVES - 1) / TEXT_WAVES, ctx->cus));
-        hipLaunchKernelGGL(fq_text_kernel, dim3(blocks), dim3(64 * TEXT_WAVES), (size_t)e.lds_slots * e.lds_slot_dwords * 4 + text_bytes, st, e);
-        HIP_TRY(ctx, hipGetLastError());
-        return 0;
-    };
-    bool dup_prepared = false;
-    auto launch_dup = [&](u8* dupflag, bool scan = false, hipStream_t st = nullptr, int stage = 0) -> int {
-        // stage 0: everything; 1: only the buffers + clears (before a fused kernel that claims); 2: what follows that kernel
-        if (!st) st = st_main;
-        DupArgs d;
-        memset(&d, 0, sizeof(d));
-        if (scan) { d.scan_pos = scan_pos; d.scan_mask = scan_mask; }
-        d.dup_pos = dup_pos_buf;
-        d.posum = ctx->d_posum;
-        d.len[0] = a.len[0];
-        d.len[1] = a.len[1];
-        d.n = n;
-        d.B = ctx->dp.dup_bufnum;
-        d.bits = ctx->dp.dup_bits;
-        d.bitmap = ctx->d_bitmap;
-        int lg = 10;
-        while ((1ull << lg) < (size_t)n * d.B * 2) lg++;
-        int r2 = ensure(ctx, (void**)&ctx->d_table, &ctx->table_cap, (size_t)8 << lg);
-        if (r2) return r2;
-        r2 = ensure(ctx, (void**)&ctx->d_need, &ctx->need_cap, (size_t)n);
-        if (r2) return r2;
-        d.table = ctx->d_table;
-        d.table_log2 = lg;
-        d.need = ctx->d_need;
-        d.res[0] = a.res[0];
-        d.res[1] = a.res[1];
-        d.dupflag = dupflag;
-        d.paired = ctx->dp.paired;
-        d.ctr_total = ctx->d_ctr + cl.dup_total;
-        d.ctr_dups = ctx->d_ctr + cl.dup_count;
-        // Stage 1's clears (128 MB of table for 4 Mi pairs: 21 + 6 us) are needed by the kernels of stage 2 only, not by the kernel
-        // that claims: where stage 2 will run on the tail stream they go there, beside the per-read kernel instead of in front of it
-        // (that stream is past the previous launch's tail by then; the launch stream joins it at the end of every launch)
-        hipStream_t cst = (stage == 1 && ctx->split && !dedup_folded && n > 0) ? ctx->tail : st;
-        if (stage < 2) HIP_TRY(ctx, hipMemsetAsync(d.table, 0xFF, (size_t)8 << lg, cst));
-        const int g2 = std::max(1, (n + 255) / 256);  // one unit per lane: the kernels are chains of dependent random accesses
-        if (sw.dup_table) {      // the first form: probe (read + table insert for every unit) -> resolve
-            hipLaunchKernelGGL(fq_dup_probe_kernel, dim3(g2), dim3(256), 0, st, d);
-            HIP_TRY(ctx, hipGetLastError());
-            hipLaunchKernelGGL(fq_dup_resolve_kernel, dim3(std::max(1, (n + 1023) / 1024)), dim3(1024), 16, st, d);
-            HIP_TRY(ctx, hipGetLastError());
-            return 0;
-        }
-        r2 = ensure(ctx, (void**)&ctx->d_setw, &ctx->setw_cap, (size_t)n);
-        if (r2) return r2;
-        if (!ctx->d_cfilter) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_cfilter, (size_t)1 << (DUP_CF_LOG2 - 3)));
-        d.setw = ctx->d_setw;
-        d.cfilter = ctx->d_cfilter;
-        if (stage < 2) HIP_TRY(ctx, hipMemsetAsync(d.cfilter, 0, (size_t)1 << (DUP_CF_LOG2 - 3), cst));
-        if (stage == 1) {
-            a.claim_won = ctx->d_need;
-            a.dup_bitmap = ctx->d_bitmap;
-            a.dup_bits = ctx->dp.dup_bits;
-            dup_prepared = true;
-            return 0;
-        }
-        if (stage == 2) hipLaunchKernelGGL(fq_dup_losers_kernel, dim3(g2), dim3(256), 0, st, d);
-        else hipLaunchKernelGGL(fq_dup_claim_kernel, dim3(g2), dim3(256), 0, st, d);
-        HIP_TRY(ctx, hipGetLastError());
-        hipLaunchKernelGGL(fq_dup_winners_kernel, dim3(g2), dim3(256), 0, st, d);
-        HIP_TRY(ctx, hipGetLastError());
-        hipLaunchKernelGGL(fq_dup_finish_kernel, dim3(std::max(1, (n + 1023) / 1024)), dim3(1024), 16, st, d);
-        HIP_TRY(ctx, hipGetLastError());
-        return 0;
-    };
+    return 0;
+}
 
-    if (mode == CHUNK_PASS1 && ctx->dp.dedup) {
-        hipLaunchKernelGGL(fq_hash_kernel, dim3(grid), dim3(ctx->cfg.threads), (size_t)ctx->L.total * 4, st, a);
-        HIP_TRY(ctx, hipGetLastError());
-        if (exact) {
-            rc = launch_exact(1);
-            if (rc) return rc;
-        }
-        return launch_dup(nullptr, true);
-    }
-    // the overrepresentation analysis reads the rows by their TRUE lengths, and the listed units' symbols from their text
-    auto overrep = [&](hipStream_t ost = nullptr) -> int {
-        KernelArgs ao = a;
-        ao.len[0] = true_len[0];
-        ao.len[1] = true_len[1];
-        return launch_overrep(ctx, ao, n, ost ? ost : st, b);
-    };
-    if (mode == CHUNK_OVERREP) return overrep();
-    if (mode == CHUNK_PASS2) {
-        // the decision comes from pass 1's scan state + the preceding shards' bitmaps; nothing is hashed again
-        if (ctx->dp.dedup) {
-            rc = ensure(ctx, (void**)&ctx->d_dupflag, &ctx->dupflag_cap, (size_t)n);
-            if (rc) return rc;
-        }
-        DupFinalArgs d;
-        memset(&d, 0, sizeof(d));
-        d.scan_pos = scan_pos;
-        d.scan_mask = scan_mask;
-        d.prefix = ctx->has_prefix ? ctx->d_prefix : nullptr;
-        d.bits = ctx->dp.dup_bits;
-        d.n = n;
-        d.B = ctx->dp.dup_bufnum;
-        d.dupflag = ctx->dp.dedup ? ctx->d_dupflag : nullptr;
-        d.res[0] = a.res[0];
-        d.res[1] = a.res[1];
-        d.paired = ctx->dp.paired;
-        d.ctr_total = ctx->d_ctr + cl.dup_total;
-        d.ctr_dups = ctx->d_ctr + cl.dup_count;
-        hipLaunchKernelGGL(fq_dup_final_kernel, dim3((n + 255) / 256), dim3(256), 16, st, d);
-        HIP_TRY(ctx, hipGetLastError());
-        if (!ctx->dp.dedup) return FASTP_GPU_OK;  // the records are pass 1's
-        a.dup_pos = nullptr;
-        a.dupflag = ctx->d_dupflag;
-    } else if (ctx->dp.dedup && !dedup_folded) {
-        // --dedup: hash pass -> duplicate decision -> fused kernel reads the decision
-        rc = ensure(ctx, (void**)&ctx->d_dupflag, &ctx->dupflag_cap, (size_t)n);
-        if (rc) return rc;
-        hipLaunchKernelGGL(fq_hash_kernel, dim3(grid), dim3(ctx->cfg.threads), (size_t)ctx->L.total * 4, st, a);
-        HIP_TRY(ctx, hipGetLastError());
-        if (exact) {
-            rc = launch_exact(1);
-            if (rc) return rc;
-        }
-        rc = launch_dup(ctx->d_dupflag);
-        if (rc) return rc;
-        a.dup_pos = nullptr;
-        a.dupflag = ctx->d_dupflag;
-    }
+// the text kernel (fq_text.h): a wavefront per listed unit, its texts in the wavefront's stretch of LDS, Stats' per-base
+// counters in the workgroup's LDS tables (added to d_ctr once), everything else straight into d_ctr
+static int launch_text(Launch& l, int hash_only, hipStream_t st) {
+    fastp_gpu_ctx* ctx = l.ctx;
+    const fastp_gpu_batch* b = l.b;
+    TextArgs e;
+    memset(&e, 0, sizeof(e));
+    e.k = l.a;
+    e.c = ctx->t_text_ctr;
+    e.ctr = ctx->d_ctr;
+    e.k.len[0] = l.true_len[0];
+    e.k.len[1] = l.true_len[1];
+    e.x_n = b->n_exotic;
+    e.x_unit = ctx->d_x_unit;
+    e.x_all = ctx->exact_all ? 1 : 0;
+    e.x_k0 = l.p.xk0;
+    e.x_count = ctx->exact_all ? l.n : l.p.xk1 - l.p.xk0;
+    e.x_dense = b->exotic_dense;
+    for (int m = 0; m < 2; m++) { e.x_text[m] = b->exotic_text[m]; e.x_off[m] = b->exotic_off[m]; }
+    e.ML = (ctx->dp.max_len + 8 + 7) & ~7;
+    e.hash_only = hash_only;
+    // Stats' per-base tables of a workgroup in LDS when they fit beside the wavefronts' texts (not the hash pre-pass, which
+    // counts nothing; reads too long for it add to the block with global atomics)
+    const size_t text_bytes = (size_t)TEXT_WAVES * text_wave_bytes(e.ML);
+    const int slot_dwords = 34 * (int)ctx->cl.cycles + 1024 + 128;
+    const int slots = !ctx->dp.paired ? 2 : ctx->dp.merge ? 3 : 4;   // the Stats objects a unit can reach
+    const bool lds_tables = !hash_only && (size_t)slots * slot_dwords * 4 + text_bytes <= (size_t)aux_lds_cap(ctx);
+    e.lds_slot_dwords = lds_tables ? slot_dwords : 0;
+    e.lds_slots = lds_tables ? slots : 0;
+    const int blocks = std::max(1, std::min((e.x_count + TEXT_WAVES - 1) / TEXT_WAVES, ctx->cus));
+    hipLaunchKernelGGL(fq_text_kernel, dim3(blocks), dim3(64 * TEXT_WAVES), (size_t)e.lds_slots * e.lds_slot_dwords * 4 + text_bytes, st, e);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
 
-    if (claim_fused) {
-        rc = launch_dup(nullptr, false, nullptr, 1);
-        if (rc) return rc;
-    }
-    int ln_grid = 0;
-    // The text kernel of the units with letters outside ACGTN, lane plan (round 5): it runs on the tail stream from here on,
-    // BESIDE the lane kernel (which counts such a unit as the empty unit it sees and writes nothing of it, KernelArgs::xskip)
-    // and the Stats kernel (to which it is an empty read); Duplicate's kernels wait for both.  A launch with a handful of such
-    // units used to wait 2.6 - 3.1 ms for one lane's walk between the two kernels.
-    if (!exact_early) a.xskip = nullptr;
-    if (exact_early) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, st));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->tail, ctx->ev_k1, 0));
-        rc = launch_exact(0, ctx->tail);
-        if (rc) return rc;
-    }
-    hipEvent_t e0, e1;
-    rc = get_events(ctx, &e0, &e1);
+// Duplicate's kernels of a launch share one argument block and the buffers behind it
+static int dup_args(Launch& l, u8* dupflag, bool scan, DupArgs* out) {
+    fastp_gpu_ctx* ctx = l.ctx;
+    DupArgs& d = *out;
+    memset(&d, 0, sizeof(d));
+    if (scan) { d.scan_pos = l.p.scan_pos; d.scan_mask = l.p.scan_mask; }
+    d.dup_pos = ctx->dp.dup_enabled && l.p.mode != CHUNK_OVERREP ? ctx->d_dup_pos : nullptr;
+    d.posum = ctx->d_posum;
+    d.len[0] = l.a.len[0];
+    d.len[1] = l.a.len[1];
+    d.n = l.n;
+    d.B = ctx->dp.dup_bufnum;
+    d.bits = ctx->dp.dup_bits;
+    d.bitmap = ctx->d_bitmap;
+    int lg = 10;
+    while ((1ull << lg) < (size_t)l.n * d.B * 2) lg++;
+    int rc = ensure(ctx, (void**)&ctx->d_table, &ctx->table_cap, (size_t)8 << lg);
     if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(e0, st));
-    if (use_lane) {
-        LaneArgs la;
+    rc = ensure(ctx, (void**)&ctx->d_need, &ctx->need_cap, (size_t)l.n);
+    if (rc) return rc;
+    d.table = ctx->d_table;
+    d.table_log2 = lg;
+    d.need = ctx->d_need;
+    d.res[0] = l.a.res[0];
+    d.res[1] = l.a.res[1];
+    d.dupflag = dupflag;
+    d.paired = ctx->dp.paired;
+    d.ctr_total = ctx->d_ctr + ctx->cl.dup_total;
+    d.ctr_dups = ctx->d_ctr + ctx->cl.dup_count;
+    if (ctx->sw.dup_table) return 0;
+    rc = ensure(ctx, (void**)&ctx->d_setw, &ctx->setw_cap, (size_t)l.n);
+    if (rc) return rc;
+    if (!ctx->d_cfilter) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_cfilter, (size_t)1 << (DUP_CF_LOG2 - 3)));
+    d.setw = ctx->d_setw;
+    d.cfilter = ctx->d_cfilter;
+    return 0;
+}
+// the buffers + clears in front of a per-read kernel that claims
+static int dup_prepare(Launch& l) {
+    fastp_gpu_ctx* ctx = l.ctx;
+    DupArgs d;
+    const int rc = dup_args(l, nullptr, false, &d);
+    if (rc) return rc;
+    hipStream_t cst = l.p.clears_on_tail ? ctx->tail : l.st;
+    HIP_TRY(ctx, hipMemsetAsync(d.table, 0xFF, (size_t)8 << d.table_log2, cst));
+    HIP_TRY(ctx, hipMemsetAsync(d.cfilter, 0, (size_t)1 << (DUP_CF_LOG2 - 3), cst));
+    l.a.claim_won = ctx->d_need;
+    l.a.dup_bitmap = ctx->d_bitmap;
+    l.a.dup_bits = ctx->dp.dup_bits;
+    return 0;
+}
+// losers (behind a per-read kernel that claimed) or claim, then winners and finish
+static int dup_decide(Launch& l, const DupArgs& d, bool claimed, hipStream_t st) {
+    fastp_gpu_ctx* ctx = l.ctx;
+    const int g2 = std::max(1, (l.n + 255) / 256);  // one unit per lane: the kernels are chains of dependent random accesses
+    if (claimed) hipLaunchKernelGGL(fq_dup_losers_kernel, dim3(g2), dim3(256), 0, st, d);
+    else hipLaunchKernelGGL(fq_dup_claim_kernel, dim3(g2), dim3(256), 0, st, d);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(fq_dup_winners_kernel, dim3(g2), dim3(256), 0, st, d);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(fq_dup_finish_kernel, dim3(std::max(1, (l.n + 1023) / 1024)), dim3(1024), 16, st, d);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+// what follows that kernel
+static int dup_tail(Launch& l, u8* dupflag, hipStream_t st) {
+    DupArgs d;
+    const int rc = dup_args(l, dupflag, false, &d);
+    return rc ? rc : dup_decide(l, d, true, st);
+}
+// everything, with the claim as its own kernel (scan: pass 1 of a sharded run keeps the scan state)
+static int dup_claim_chain(Launch& l, u8* dupflag, bool scan, hipStream_t st) {
+    fastp_gpu_ctx* ctx = l.ctx;
+    DupArgs d;
+    const int rc = dup_args(l, dupflag, scan, &d);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(d.table, 0xFF, (size_t)8 << d.table_log2, st));
+    if (ctx->sw.dup_table) {      // the first form: probe (read + table insert for every unit) -> resolve
+        hipLaunchKernelGGL(fq_dup_probe_kernel, dim3(std::max(1, (l.n + 255) / 256)), dim3(256), 0, st, d);
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(fq_dup_resolve_kernel, dim3(std::max(1, (l.n + 1023) / 1024)), dim3(1024), 16, st, d);
+        HIP_TRY(ctx, hipGetLastError());
+        return 0;
+    }
+    HIP_TRY(ctx, hipMemsetAsync(d.cfilter, 0, (size_t)1 << (DUP_CF_LOG2 - 3), st));
+    return dup_decide(l, d, false, st);
+}
+// the hash pass in front of the worker loop -> Duplicate's chain (--dedup: with dupflag, its decisions; pass 1 of a sharded
+// run: the scan state)
+static int hash_prepass(Launch& l, u8* dupflag, bool scan) {
+    fastp_gpu_ctx* ctx = l.ctx;
+    hipLaunchKernelGGL(fq_hash_kernel, dim3(l.grid), dim3(ctx->cfg.threads), (size_t)ctx->L.total * 4, l.st, l.a);
+    HIP_TRY(ctx, hipGetLastError());
+    if (l.p.text_prepass) {
+        const int rc = launch_text(l, 1, l.st);
+        if (rc) return rc;
+    }
+    return dup_claim_chain(l, dupflag, scan, l.st);
+}
+// pass 2 of a sharded run: the decision comes from pass 1's scan state + the preceding shards' bitmaps; nothing is hashed again
+static int pass2_decide(Launch& l) {
+    fastp_gpu_ctx* ctx = l.ctx;
+    DupFinalArgs d;
+    memset(&d, 0, sizeof(d));
+    d.scan_pos = l.p.scan_pos;
+    d.scan_mask = l.p.scan_mask;
+    d.prefix = ctx->has_prefix ? ctx->d_prefix : nullptr;
+    d.bits = ctx->dp.dup_bits;
+    d.n = l.n;
+    d.B = ctx->dp.dup_bufnum;
+    d.dupflag = ctx->dp.dedup ? ctx->d_dupflag : nullptr;
+    d.res[0] = l.a.res[0];
+    d.res[1] = l.a.res[1];
+    d.paired = ctx->dp.paired;
+    d.ctr_total = ctx->d_ctr + ctx->cl.dup_total;
+    d.ctr_dups = ctx->d_ctr + ctx->cl.dup_count;
+    hipLaunchKernelGGL(fq_dup_final_kernel, dim3((l.n + 255) / 256), dim3(256), 16, l.st, d);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+// --dedup folded: Duplicate's decisions taken out of the records and the POST Stats' read counts before the Stats kernel counts
+static int dedup_apply(Launch& l) {
+    fastp_gpu_ctx* ctx = l.ctx;
+    DedupApplyArgs da;
+    memset(&da, 0, sizeof(da));
+    da.n = l.n;
+    da.paired = ctx->dp.paired;
+    da.dupflag = ctx->d_dupflag;
+    for (int m = 0; m < 2; m++) {
+        da.res[m] = l.a.res[m];
+        da.swin[m] = ctx->d_swin[m];
+        da.st_reads[m] = ctx->d_ctr + ctx->cl.stats[2 * m + 1] + ctx->cl.st_reads;
+        da.st_lensum[m] = ctx->d_ctr + ctx->cl.stats[2 * m + 1] + ctx->cl.st_length_sum;
+    }
+    hipLaunchKernelGGL(fq_dedup_apply_kernel, dim3((l.n + 255) / 256), dim3(256), 16, l.st, da);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// the overrepresentation analysis reads the rows by their TRUE lengths, and the listed units' symbols from their text
+static int overrep(Launch& l, hipStream_t st) {
+    KernelArgs ao = l.a;
+    ao.len[0] = l.true_len[0];
+    ao.len[1] = l.true_len[1];
+    return launch_overrep(l.ctx, ao, l.n, st, l.b);
+}
+
+static int launch_per_read(Launch& l) {
+    fastp_gpu_ctx* ctx = l.ctx;
+    const KernelArgs& a = l.a;
+    hipStream_t st = l.st;
+    const int n = l.n;
+    if (l.p.kernel == K_LANE) {
+        LaneArgs la = ctx->t_lane;
         la.k = a;
         la.k.slabs = ctx->d_ln_slabs;
         la.k.slab_dwords = ctx->ln_lds.n_misc;
-        la.l = ctx->ln_lds;
-        la.chunk_ctr = ctx->d_ln_ctr;
         // the chunks no workgroup owns (LaneArgs::pool)
         // A/B, off: profiles/r06_x_lane_chunk_pool_ab.txt, r06_y_*: an 8th of the chunks -2 %, a 16th 0, a 32nd .. a 128th +0.2 % on the
         // headline (noise), the single-end lines, -c and configs[4] 0.4 - 2 % SLOWER - the CUs' equal shares already end
         // together; the asks of the pool cost what little imbalance there is
-        const int lg = sw.lane_pool_log2;
+        const int lg = ctx->sw.lane_pool_log2;
         const int chunks = (n + 63) >> 6;
         la.pool = lg > 0 && lg < 31 ? chunks >> lg : 0;
         if (ctx->ln_pool_base > 0x60000000) {   // (the counter only counts up: back to zero long before it could wrap)
@@ -1437,288 +1622,226 @@ static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first,
         la.pool_grab = std::max(1, la.pool >> 11);   // at most ~2 k asks per launch
         // every wavefront asks once more than it gets: the counter ends at most (asks that get chunks) + wavefronts beyond the base
         ctx->ln_pool_base += (la.pool + la.pool_grab - 1) / la.pool_grab + ctx->ln_blocks * (ctx->ln_threads >> 6) + 64;
-        la.post1 = ctx->d_ctr + cl.stats[1];
-        la.st_qual_hist = cl.st_qual_hist; la.st_kmer = cl.st_kmer; la.st_cycle = cl.st_cycle; la.cycles = cl.cycles;
         const int Bh = (ctx->dp.dup_enabled && (a.dup_pos || a.claim_won) && !(a.debug_skip & 2u)) ? ctx->dp.dup_bufnum : 0;
         lane_kernel_fn fn = lane_kernel_for(ctx->ln_swm, Bh, ctx->dp.paired != 0, lane_ext(ctx->dp));
-        ln_grid = std::max(1, std::min(ctx->ln_blocks, (n + 255) / 256));
-        hipLaunchKernelGGL(fn, dim3(ln_grid), dim3(ctx->ln_threads), (size_t)ctx->ln_lds.total * 4, st, la);
-    } else if (ctx->split && ctx->cfg.threads > 256) hipLaunchKernelGGL(fq_scan_wide_kernel, dim3(grid), dim3(ctx->cfg.threads), (size_t)ctx->L.total * 4, st, a);
-    else if (ctx->split) hipLaunchKernelGGL(fq_scan_kernel, dim3(grid), dim3(ctx->cfg.threads), (size_t)ctx->L.total * 4, st, a);
-    else hipLaunchKernelGGL(fq_fused_kernel, dim3(grid), dim3(ctx->cfg.threads), (size_t)ctx->L.total * 4, st, a);
+        l.ln_grid = std::max(1, std::min(ctx->ln_blocks, (n + 255) / 256));
+        hipLaunchKernelGGL(fn, dim3(l.ln_grid), dim3(ctx->ln_threads), (size_t)ctx->ln_lds.total * 4, st, la);
+    } else if (l.p.kernel == K_SCAN_WIDE) hipLaunchKernelGGL(fq_scan_wide_kernel, dim3(l.grid), dim3(ctx->cfg.threads), (size_t)ctx->L.total * 4, st, a);
+    else if (l.p.kernel == K_SCAN) hipLaunchKernelGGL(fq_scan_kernel, dim3(l.grid), dim3(ctx->cfg.threads), (size_t)ctx->L.total * 4, st, a);
+    else hipLaunchKernelGGL(fq_fused_kernel, dim3(l.grid), dim3(ctx->cfg.threads), (size_t)ctx->L.total * 4, st, a);
     HIP_TRY(ctx, hipGetLastError());
-    // The text kernel of the units with letters outside ACGTN runs behind the plan's kernel (the records and hash values of its
-    // units are overwritten) - and, in the split plans, BESIDE the Stats kernel (round 5): the Stats kernel needs nothing of it
-    // (the listed units are empty reads to it, the text kernel adds their Stats itself), only Duplicate's kernels do, so both go
-    // to the tail stream.  A launch with a handful of such units used to wait 2.6 - 3.1 ms for one lane's walk before anything else ran.
-    bool exact_on_tail = false;
-    if (exact_early) {
-        // (launched in front of the plan's kernel) Duplicate's kernels need that kernel's hash values as well: the tail stream joins it
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, st));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->tail, ctx->ev_k1, 0));
-        exact_on_tail = true;
-    } else if (exact && ctx->split && mode == CHUNK_STREAM && !ctx->dp.dedup && n > 0) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, st));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->tail, ctx->ev_k1, 0));
-        rc = launch_exact(0, ctx->tail);
-        if (rc) return rc;
-        exact_on_tail = true;
-    } else if (exact) {
-        rc = launch_exact(0);
-        if (rc) return rc;
-    }
-    // the slab folds (set up here: the per-read kernel's MISC_* fold may go to the tail stream in front of Duplicate's kernels)
-    ReduceArgs r;
-    memset(&r, 0, sizeof(r));
-    r.L = ctx->L;
-    r.isize_max = ctx->dp.isize_max;
-    r.one_pass = ctx->dp.stats_one_pass || (ctx->split && (ctx->dp.front_lane || ctx->dp.corr_lane || ctx->dp.merge_lane));
-    r.merge_tail = (ctx->split && ctx->dp.merge_lane) ? 1 : 0;
-    if (ctx->split && ctx->dp.front_lane) { r.front[0] = ctx->dp.lane_front1; r.front[1] = ctx->dp.lane_front2; }
-    r.ctr = ctx->d_ctr;
-    r.o_filter = cl.filter_stats; r.o_adapter_reads = cl.adapter_reads; r.o_adapter_bases = cl.adapter_bases;
-    r.o_polyx_reads = cl.polyx_reads; r.o_polyx_bases = cl.polyx_bases; r.o_correction = cl.correction;
-    r.o_corrected_reads = cl.corrected_reads; r.o_merged = cl.merged_pairs; r.o_isize = cl.isize;
-    for (int s = 0; s < 4; s++) r.o_stats[s] = cl.stats[s];
-    r.st_reads = cl.st_reads; r.st_length_sum = cl.st_length_sum; r.st_qual_hist = cl.st_qual_hist;
-    r.st_kmer = cl.st_kmer; r.st_cycle = cl.st_cycle; r.cycles = cl.cycles;
-    const int n_stats = 4 * N_CLS * ctx->L.Cp + 4 * KMER_BINS + 4 * 128, n_misc = MISC_ISIZE + ctx->dp.isize_max + 1 + (r.merge_tail ? (int)KMER_BINS : 0);
-    auto fold = [&](int parts, int nblocks, hipStream_t st) -> int {
-        if (nblocks <= 0) return 0;
-        r.parts = parts;
-        r.nblocks = nblocks;
-        const int items = ((parts & 1) ? n_stats : 0) + ((parts & 2) ? n_misc : 0);
-        const int rgroups = (nblocks + REDUCE_GROUP - 1) / REDUCE_GROUP;
-        hipLaunchKernelGGL(fq_reduce_kernel, dim3(((items + 255) / 256) * rgroups), dim3(256), 0, st, r);
-        HIP_TRY(ctx, hipGetLastError());
-        return 0;
-    };
-    // the claim ran inside that kernel: what is left of Duplicate (losers / winners / finish) needs nothing of the Stats
-    // kernel and runs beside it on its own stream; the launch stream joins it before anything else touches the records
-    bool dup_tail_launched = false;
-    bool dedup_applied = false;
-    bool misc_folded = false;
-    if (dedup_folded && dup_prepared && n > 0) {
-        // --dedup: the decisions are needed before the Stats kernel classifies a base as kept - on the launch stream
-        rc = ensure(ctx, (void**)&ctx->d_dupflag, &ctx->dupflag_cap, (size_t)n);
-        if (rc) return rc;
-        rc = launch_dup(ctx->d_dupflag, false, st, 2);
-        if (rc) return rc;
-        DedupApplyArgs da;
-        memset(&da, 0, sizeof(da));
-        da.n = n;
-        da.paired = ctx->dp.paired;
-        da.dupflag = ctx->d_dupflag;
-        for (int m = 0; m < 2; m++) {
-            da.res[m] = a.res[m];
-            da.swin[m] = ctx->d_swin[m];
-            da.st_reads[m] = ctx->d_ctr + cl.stats[2 * m + 1] + cl.st_reads;
-            da.st_lensum[m] = ctx->d_ctr + cl.stats[2 * m + 1] + cl.st_length_sum;
-        }
-        hipLaunchKernelGGL(fq_dedup_apply_kernel, dim3((n + 255) / 256), dim3(256), 16, st, da);
-        HIP_TRY(ctx, hipGetLastError());
-        dedup_applied = true;
-    } else if (ctx->split && dup_prepared && n > 0) {
-        // The Stats kernel's workgroups own every CU (a 1024-lane workgroup at 128 VGPRs is the whole register file): a kernel on
-        // the tail stream gets through when one of the Stats kernel's two rounds of workgroups ends, ONE kernel per such moment
-        // (profiles/r06_s_step_timeline.txt, r06_t_step_timeline.txt: each tail kernel "takes" 0.43 - 0.50 ms, 0.01 - 0.03 alone).
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, st));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->tail, ctx->ev_k1, 0));
-        // The MISC_* fold needs the per-read kernel only: FIRST on the tail stream.  Behind Duplicate's kernels - which the Stats
-        // kernel's workgroups starve until its last round ends (profiles/r06_s_step_timeline.txt: losers 0.45 ms, winners 0.50 ms
-        // beside it, 0.01 / 0.03 alone) - it was 27 + 9 us at the very end of every step, with nothing else on the chip.
-        r.slabs = use_lane ? ctx->d_ln_slabs : ctx->d_slabs;
-        r.slab_dwords = use_lane ? ctx->ln_lds.n_misc : ctx->slab_dwords;
-        r.off_misc = use_lane ? 0 : ctx->L.acc_misc - ctx->L.acc_cyc;
-        rc = fold(2, use_lane ? ln_grid : grid, ctx->tail);
-        if (rc) return rc;
-        misc_folded = true;
-        rc = launch_dup(nullptr, mode == CHUNK_PASS1, ctx->tail, 2);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_tail, ctx->tail));
-        dup_tail_launched = true;
-    } else if (exact_on_tail) {
-        // Duplicate's kernels behind the text kernel, on its stream (the claim is not fused into a launch that has such units)
-        if (ctx->dp.dup_enabled) {
-            rc = launch_dup(nullptr, false, ctx->tail, 0);
-            if (rc) return rc;
-        }
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_tail, ctx->tail));
-        dup_tail_launched = true;
-    }
-    // The overrepresentation analysis needs the records (and --dedup's decisions), nothing of the Stats kernel: on the tail stream
-    // BESIDE it (round 5; behind Duplicate's tail / the text kernel when they are there - they write record flags), joined at the end
-    bool ovr_early = false;
-    if (ctx->dp.overrep && !(b->flags & FASTP_GPU_BATCH_DEFER_OVERREP) && ctx->split && mode == CHUNK_STREAM && n > 0) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, st));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->tail, ctx->ev_k1, 0));
-        rc = overrep(ctx->tail);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_tail, ctx->tail));
-        ovr_early = true;           // (the launch stream waits for the tail stream below)
-    }
-    int st_grid = 0;
-    if (ctx->split && n > 0) {
-        // Stats::statRead of the launch's units: a workgroup takes a run of consecutive units (at most CYC_MAX_READS:
-        // packed counters; at least 64 so that small launches do not pay a 43 KB slab per handful of reads)
-        StatsArgs sa;
-        memset(&sa, 0, sizeof(sa));
-        sa.n = n;
-        sa.paired = ctx->dp.paired;
-        sa.sw_g = ctx->dp.sw_g;
-        sa.qw_g = ctx->dp.qw_g;
-        sa.H = ctx->st_H; sa.Hs = ctx->st_Hs;
-        sa.magic_H = magic_for((u32)ctx->st_H);
-        sa.Cp = ctx->L.Cp;
-        // whole rounds of the resident workgroups: 4.19 M pairs = 3 rounds of 512 workgroups with 2731 units each in form 4
-        const int rounds = (int)(((long long)n + (long long)ctx->st_blocks * ctx->st_max_reads - 1) / ((long long)ctx->st_blocks * ctx->st_max_reads));
-        int upb = (n + ctx->st_blocks * rounds - 1) / (ctx->st_blocks * rounds);
-        upb = std::max(upb, std::min(n, 64));
-        if (upb > ctx->st_max_reads) return fail(ctx, FASTP_GPU_E_INVALID, "launch too large for the Stats kernel");
-        sa.units_per_block = upb;
-        st_grid = (n + upb - 1) / upb;
-        if (st_grid > ctx->st_max_grid) return fail(ctx, FASTP_GPU_E_INVALID, "launch too large for the Stats kernel's slabs");
-        sa.kc = ctx->st_kc;
-        if (ctx->dp.front_lane) { sa.front[0] = ctx->dp.lane_front1; sa.front[1] = ctx->dp.lane_front2; }
-        sa.merge = ctx->dp.merge_lane;
-        for (int m = 0; m < 2; m++) { sa.seq[m] = a.seq[m]; sa.qual[m] = a.qual[m]; sa.swin[m] = ctx->d_swin[m]; }
-        sa.l_cyc = ctx->st_l_cyc; sa.l_kmer = ctx->st_l_kmer; sa.l_qh = ctx->st_l_qh; sa.l_lut = ctx->st_l_lut; sa.l_mt = ctx->st_l_mt;
-        sa.l_wl = ctx->st_l_wl; sa.wl_cap = ctx->st_wl_cap;
-        sa.l_total = ctx->st_lds_dwords;
-        sa.H16 = ctx->st_H16; sa.magic_H16 = (ctx->st_form == 5 && ctx->st_Hs) ? magic_for((u32)ctx->st_Hs) : 0u; sa.l_ovf = ctx->st_l_ovf;   // (the magic of the table's columns)
-        sa.front_per_read = ctx->dp.front_per_read;
-        sa.fr_stride = ctx->dp.front_per_read ? 3 : 0;
-        for (int m = 0; m < 2; m++) sa.fr_rec[m] = ctx->dp.front_per_read ? (const u32*)a.res[m] : ctx->d_swin[m];
-        sa.slabs = ctx->d_st_slabs;
-        sa.slab_dwords = ctx->st_slab_dwords;
-        sa.debug_skip = a.debug_skip;
-        if (!(a.debug_skip & 16u)) {
-            if (ctx->st_form == 5) hipLaunchKernelGGL(fq_stats5_kernel, dim3(st_grid), dim3(ctx->st_threads), (size_t)ctx->st_lds_dwords * 4, st, sa);
-            else hipLaunchKernelGGL(fq_stats_kernel, dim3(st_grid), dim3(ctx->st_threads), (size_t)ctx->st_lds_dwords * 4, st, sa);
-            HIP_TRY(ctx, hipGetLastError());
-        } else {
-            st_grid = 0;
-        }
-    }
-    if (ctx->dp.front_per_read && ctx->lane && ctx->split && n > 0 && st_grid > 0) {
-        // --cut_front on the lane plan: the reads whose own front is beyond the mate's common one (fq_stats5.h, front_stats_body)
-        FrontStatsArgs fs;
-        memset(&fs, 0, sizeof(fs));
-        fs.n = n;
-        fs.paired = ctx->dp.paired;
-        fs.sw_g = ctx->dp.sw_g;
-        fs.qw_g = ctx->dp.qw_g;
-        for (int m = 0; m < 2; m++) {
-            fs.seq[m] = a.seq[m];
-            fs.qual[m] = a.qual[m];
-            fs.swin[m] = ctx->d_swin[m];
-            fs.rec[m] = (const u32*)a.res[m];
-            fs.post[m] = ctx->d_ctr + ctx->cl.stats[2 * m + 1];
-        }
-        fs.front0[0] = ctx->dp.lane_front1;
-        fs.front0[1] = ctx->dp.lane_front2;
-        fs.st_cycle = ctx->cl.st_cycle;
-        fs.cycles = ctx->cl.cycles;
-        const size_t reads = (size_t)n * (ctx->dp.paired ? 2 : 1);
-        const size_t lds_bytes = (size_t)(ctx->dp.paired ? 2 : 1) * 34 * (size_t)ctx->cl.cycles * 4;
-        const int fgrid = (int)std::max<size_t>(1, std::min<size_t>((size_t)ctx->cus * 4, (reads + 255) / 256));
-        hipLaunchKernelGGL(fq_front_stats_kernel, dim3(fgrid), dim3(256), lds_bytes, st, fs);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    if (corr_lane && ctx->split && n > 0 && st_grid > 0) {
-        // -c: the corrected positions' share of the POST Stats moves from the original base / quality to the corrected one
-        const size_t reads = (size_t)n * (ctx->dp.paired ? 2 : 1);
-        rc = ensure(ctx, (void**)&ctx->d_corr_chain, &ctx->corr_chain_cap, (reads + (size_t)a.corr_int_cap) * 4);
-        if (rc) return rc;
-        OvrArgs lo;
-        memset(&lo, 0, sizeof(lo));
-        lo.n = n;
-        lo.first = a.first;
-        lo.paired = ctx->dp.paired;
-        lo.corr = a.corr_int;
-        lo.n_corr = a.n_corr_int;
-        lo.corr_cap = a.corr_int_cap;
-        lo.corr_head = ctx->d_corr_chain;
-        lo.corr_next = ctx->d_corr_chain + reads;
-        HIP_TRY(ctx, hipMemsetAsync(lo.corr_head, 0, reads * 4, st));
-        // (one lane per possible entry would be n x limit lanes; the list is short - a grid-stride walk over what it holds)
-        hipLaunchKernelGGL(fq_corr_link_kernel, dim3(std::min(4096, (a.corr_int_cap + 255) / 256)), dim3(256), 0, st, lo);
-        HIP_TRY(ctx, hipGetLastError());
-        CorrStatsArgs cs;
-        memset(&cs, 0, sizeof(cs));
-        cs.n = n;
-        cs.paired = ctx->dp.paired;
-        cs.sw_g = ctx->dp.sw_g;
-        cs.qw_g = ctx->dp.qw_g;
-        for (int m = 0; m < 2; m++) {
-            cs.seq[m] = a.seq[m];
-            cs.qual[m] = a.qual[m];
-            cs.swin[m] = ctx->d_swin[m];
-            cs.post[m] = ctx->d_ctr + cl.stats[ctx->dp.merge_lane ? 1 : 2 * m + 1];
-        }
-        cs.merge = ctx->dp.merge_lane;
-        cs.front[0] = ctx->dp.front_lane ? ctx->dp.lane_front1 : 0;
-        cs.front[1] = ctx->dp.front_lane ? ctx->dp.lane_front2 : 0;
-        cs.corr = a.corr_int;
-        cs.corr_head = lo.corr_head;
-        cs.corr_next = lo.corr_next;
-        cs.st_qual_hist = cl.st_qual_hist;
-        cs.st_kmer = cl.st_kmer;
-        cs.st_cycle = cl.st_cycle;
-        cs.cycles = cl.cycles;
-        {   // persistent workgroups: the deltas of a workgroup's reads meet in its LDS tables first (corr_stats_body)
-            const size_t lds_bytes = (size_t)(ctx->dp.paired ? 2 : 1) * (33 * (size_t)cl.cycles + 128 + KMER_BINS) * 4;
-            const int cgrid = (int)std::max<size_t>(1, std::min<size_t>((size_t)ctx->cus * 2, (reads + 1023) / 1024));
-            hipLaunchKernelGGL(fq_corr_stats_kernel, dim3(cgrid), dim3(1024), lds_bytes, st, cs);
-        }
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    HIP_TRY(ctx, hipEventRecord(e1, st));
-    ctx->pending_events.push_back({e0, e1});
+    return 0;
+}
 
-    if (ctx->split) {
-        // the Stats kernel's slabs: per-cycle u64s, k-mer counters, one histogram counter per (slot, character)
+// Stats::statRead of the launch's units: a workgroup takes a run of consecutive units (at most CYC_MAX_READS:
+// packed counters; at least 64 so that small launches do not pay a 43 KB slab per handful of reads)
+static int launch_stats(Launch& l) {
+    fastp_gpu_ctx* ctx = l.ctx;
+    const int n = l.n;
+    StatsArgs sa = ctx->t_stats;
+    sa.n = n;
+    // whole rounds of the resident workgroups: 4.19 M pairs = 3 rounds of 512 workgroups with 2731 units each in form 4
+    const int rounds = (int)(((long long)n + (long long)ctx->st_blocks * ctx->st_max_reads - 1) / ((long long)ctx->st_blocks * ctx->st_max_reads));
+    int upb = (n + ctx->st_blocks * rounds - 1) / (ctx->st_blocks * rounds);
+    upb = std::max(upb, std::min(n, 64));
+    if (upb > ctx->st_max_reads) return fail(ctx, FASTP_GPU_E_INVALID, "launch too large for the Stats kernel");
+    sa.units_per_block = upb;
+    const int st_grid = (n + upb - 1) / upb;
+    if (st_grid > ctx->st_max_grid) return fail(ctx, FASTP_GPU_E_INVALID, "launch too large for the Stats kernel's slabs");
+    for (int m = 0; m < 2; m++) {
+        sa.seq[m] = l.a.seq[m];
+        sa.qual[m] = l.a.qual[m];
+        sa.swin[m] = ctx->d_swin[m];
+        sa.fr_rec[m] = ctx->dp.front_per_read ? (const u32*)l.a.res[m] : ctx->d_swin[m];
+    }
+    sa.debug_skip = l.a.debug_skip;
+    if (l.a.debug_skip & 16u) return 0;   // (profiling builds: no Stats kernel, nothing of it to fold)
+    if (ctx->st_form == 5) hipLaunchKernelGGL(fq_stats5_kernel, dim3(st_grid), dim3(ctx->st_threads), (size_t)ctx->st_lds_dwords * 4, l.st, sa);
+    else hipLaunchKernelGGL(fq_stats_kernel, dim3(st_grid), dim3(ctx->st_threads), (size_t)ctx->st_lds_dwords * 4, l.st, sa);
+    HIP_TRY(ctx, hipGetLastError());
+    l.st_grid = st_grid;
+    return 0;
+}
+
+static int launch_front_stats(Launch& l) {
+    fastp_gpu_ctx* ctx = l.ctx;
+    FrontStatsArgs fs = ctx->t_front;
+    fs.n = l.n;
+    for (int m = 0; m < 2; m++) {
+        fs.seq[m] = l.a.seq[m];
+        fs.qual[m] = l.a.qual[m];
+        fs.swin[m] = ctx->d_swin[m];
+        fs.rec[m] = (const u32*)l.a.res[m];
+    }
+    const size_t reads = (size_t)l.n * (ctx->dp.paired ? 2 : 1);
+    const size_t lds_bytes = (size_t)(ctx->dp.paired ? 2 : 1) * 34 * (size_t)ctx->cl.cycles * 4;
+    const int fgrid = (int)std::max<size_t>(1, std::min<size_t>((size_t)ctx->cus * 4, (reads + 255) / 256));
+    hipLaunchKernelGGL(fq_front_stats_kernel, dim3(fgrid), dim3(256), lds_bytes, l.st, fs);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+static int launch_corr_stats(Launch& l) {
+    fastp_gpu_ctx* ctx = l.ctx;
+    const KernelArgs& a = l.a;
+    const size_t reads = (size_t)l.n * (ctx->dp.paired ? 2 : 1);
+    const int rc = ensure(ctx, (void**)&ctx->d_corr_chain, &ctx->corr_chain_cap, (reads + (size_t)a.corr_int_cap) * 4);
+    if (rc) return rc;
+    OvrArgs lo;
+    memset(&lo, 0, sizeof(lo));
+    lo.n = l.n;
+    lo.first = a.first;
+    lo.paired = ctx->dp.paired;
+    lo.corr = a.corr_int;
+    lo.n_corr = a.n_corr_int;
+    lo.corr_cap = a.corr_int_cap;
+    lo.corr_head = ctx->d_corr_chain;
+    lo.corr_next = ctx->d_corr_chain + reads;
+    HIP_TRY(ctx, hipMemsetAsync(lo.corr_head, 0, reads * 4, l.st));
+    // (one lane per possible entry would be n x limit lanes; the list is short - a grid-stride walk over what it holds)
+    hipLaunchKernelGGL(fq_corr_link_kernel, dim3(std::min(4096, (a.corr_int_cap + 255) / 256)), dim3(256), 0, l.st, lo);
+    HIP_TRY(ctx, hipGetLastError());
+    CorrStatsArgs cs = ctx->t_corr;
+    cs.n = l.n;
+    for (int m = 0; m < 2; m++) { cs.seq[m] = a.seq[m]; cs.qual[m] = a.qual[m]; cs.swin[m] = ctx->d_swin[m]; }
+    cs.corr = a.corr_int;
+    cs.corr_head = lo.corr_head;
+    cs.corr_next = lo.corr_next;
+    // persistent workgroups: the deltas of a workgroup's reads meet in its LDS tables first (corr_stats_body)
+    const size_t lds_bytes = (size_t)(ctx->dp.paired ? 2 : 1) * (33 * (size_t)ctx->cl.cycles + 128 + KMER_BINS) * 4;
+    const int cgrid = (int)std::max<size_t>(1, std::min<size_t>((size_t)ctx->cus * 2, (reads + 1023) / 1024));
+    hipLaunchKernelGGL(fq_corr_stats_kernel, dim3(cgrid), dim3(1024), lds_bytes, l.st, cs);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// The slab folds.  FOLD_STATS in a split plan: the Stats kernel's slabs (per-cycle u64s, k-mer counters, one histogram counter per
+// (slot, character)); FOLD_MISC: the per-read kernel's slabs, the MISC_* counters only; both at once: the fused kernel's slabs
+enum { FOLD_STATS = 1, FOLD_MISC = 2 };
+static int fold(Launch& l, int parts, hipStream_t st) {
+    fastp_gpu_ctx* ctx = l.ctx;
+    const bool lane = l.p.kernel == K_LANE;
+    ReduceArgs r = ctx->t_reduce;
+    r.parts = parts;
+    if (parts == FOLD_STATS) {
         r.slabs = ctx->d_st_slabs;
         r.slab_dwords = ctx->st_slab_dwords;
+        r.nblocks = l.st_grid;
         r.off_kmer = 4 * N_CLS * ctx->L.Cp * 2;
         r.off_qh = r.off_kmer + 4 * KMER_BINS;
         r.qh_stride = 1;
         r.qh_count = 0;
-        rc = fold(1, st_grid, st);
-        if (rc) return rc;
-        // the per-read kernel's slabs: the MISC_* counters only
-        r.slabs = use_lane ? ctx->d_ln_slabs : ctx->d_slabs;
-        r.slab_dwords = use_lane ? ctx->ln_lds.n_misc : ctx->slab_dwords;
-        r.off_misc = use_lane ? 0 : ctx->L.acc_misc - ctx->L.acc_cyc;
-        // (needs nothing of the Stats kernel either: beside it, behind Duplicate's tail, when that stream is in use)
-        if (!misc_folded) {
-            rc = fold(2, use_lane ? ln_grid : grid, dup_tail_launched ? ctx->tail : st);
-            if (rc) return rc;
-        }
-        if (dup_tail_launched) HIP_TRY(ctx, hipEventRecord(ctx->ev_tail, ctx->tail));
     } else {
-        r.slabs = ctx->d_slabs;
-        r.slab_dwords = ctx->slab_dwords;
+        r.slabs = lane ? ctx->d_ln_slabs : ctx->d_slabs;
+        r.slab_dwords = lane ? ctx->ln_lds.n_misc : ctx->slab_dwords;
+        r.nblocks = lane ? l.ln_grid : l.grid;
+        r.off_misc = lane ? 0 : ctx->L.acc_misc - ctx->L.acc_cyc;
         r.off_kmer = ctx->L.acc_kmer - ctx->L.acc_cyc;
         r.off_qh = ctx->L.acc_qh - ctx->L.acc_cyc;
         r.qh_stride = QT_DWORDS;
         r.qh_count = QT_COUNT;
-        r.off_misc = ctx->L.acc_misc - ctx->L.acc_cyc;
-        rc = fold(3, grid, st);
-        if (rc) return rc;
+    }
+    if (r.nblocks <= 0) return 0;
+    const int n_stats = 4 * N_CLS * ctx->L.Cp + 4 * KMER_BINS + 4 * 128, n_misc = MISC_ISIZE + r.isize_max + 1 + (r.merge_tail ? (int)KMER_BINS : 0);
+    const int items = ((parts & FOLD_STATS) ? n_stats : 0) + ((parts & FOLD_MISC) ? n_misc : 0);
+    const int rgroups = (r.nblocks + REDUCE_GROUP - 1) / REDUCE_GROUP;
+    hipLaunchKernelGGL(fq_reduce_kernel, dim3(((items + 255) / 256) * rgroups), dim3(256), 0, st, r);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// the tail stream goes on from where the launch stream is now
+static int tail_follows(Launch& l) {
+    HIP_TRY(l.ctx, hipEventRecord(l.ctx->ev_k1, l.st));
+    HIP_TRY(l.ctx, hipStreamWaitEvent(l.ctx->tail, l.ctx->ev_k1, 0));
+    return 0;
+}
+
+#define STEP(call)              \
+    do {                        \
+        const int rc_ = (call); \
+        if (rc_) return rc_;    \
+    } while (0)
+
+// One launch: the schedule.  What runs, and where, is the plan's (LaunchPlan has the reasons); the order is this function's.
+static int launch_chunk(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, int first, int n, const fastp_gpu_results* res,
+                        hipStream_t st, ChunkMode mode = CHUNK_STREAM, u8* scan_state = nullptr) {
+    Launch l{ctx, b, first, n, st, plan_launch(ctx, b, first, n, mode, scan_state)};
+    const LaunchPlan& p = l.p;
+    // every mode: the argument block, the text kernel's units emptied in it, the launch's buffers
+    STEP(fill_kernel_args(l, res));
+    if (p.exact) STEP(mask_exotic_units(l));
+    STEP(fill_launch_buffers(l));
+
+    // what runs in front of the worker loop, or instead of it
+    if (mode == CHUNK_OVERREP) return overrep(l, st);
+    if (mode == CHUNK_PASS1 && ctx->dp.dedup) return hash_prepass(l, nullptr, true);
+    if (mode == CHUNK_PASS2 || p.dedup_prepass) {
+        if (ctx->dp.dedup) STEP(ensure(ctx, (void**)&ctx->d_dupflag, &ctx->dupflag_cap, (size_t)n));
+        if (mode == CHUNK_PASS2) STEP(pass2_decide(l));
+        else STEP(hash_prepass(l, ctx->d_dupflag, false));
+        if (!ctx->dp.dedup) return FASTP_GPU_OK;  // (pass 2 without --dedup) the records are pass 1's
+        l.a.dup_pos = nullptr;   // --dedup: the per-read kernel reads the decision instead of hashing
+        l.a.dupflag = ctx->d_dupflag;
     }
 
-    if (dup_tail_launched) {
-        HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_tail, 0));
-    } else if (dedup_applied) {
-        // (Duplicate's tail ran in front of the Stats kernel)
-    } else if (ctx->dp.dup_enabled && !ctx->dp.dedup) {
-        rc = launch_dup(nullptr, mode == CHUNK_PASS1, nullptr, dup_prepared ? 2 : 0);
-        if (rc) return rc;
+    // the worker loop: the per-read kernel, the text kernel around it
+    if (p.claim_fused) STEP(dup_prepare(l));
+    if (p.text == TEXT_BESIDE_LANE) {
+        STEP(tail_follows(l));
+        STEP(launch_text(l, 0, ctx->tail));
     }
-    if (ovr_early && !dup_tail_launched) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_tail, 0));
-    if ((b->flags & FASTP_GPU_BATCH_DEFER_OVERREP) || ovr_early) return FASTP_GPU_OK;
-    return overrep();
+    hipEvent_t e0, e1;
+    STEP(get_events(ctx, &e0, &e1));
+    HIP_TRY(ctx, hipEventRecord(e0, st));
+    STEP(launch_per_read(l));
+    if (p.text == TEXT_BESIDE_LANE) {
+        // (launched in front of the plan's kernel) Duplicate's kernels need that kernel's hash values as well: the tail stream joins it
+        STEP(tail_follows(l));
+    } else if (p.text == TEXT_BEHIND_ON_TAIL) {
+        STEP(tail_follows(l));
+        STEP(launch_text(l, 0, ctx->tail));
+    } else if (p.text == TEXT_INLINE) {
+        STEP(launch_text(l, 0, st));
+    }
+
+    // Duplicate behind the per-read kernel, the MISC_* fold, the overrepresentation analysis: beside the Stats kernel where they can be
+    if (p.dup_place == DUP_BEFORE_STATS) {
+        STEP(ensure(ctx, (void**)&ctx->d_dupflag, &ctx->dupflag_cap, (size_t)n));
+        STEP(dup_tail(l, ctx->d_dupflag, st));
+        STEP(dedup_apply(l));
+    }
+    if (p.misc_fold == MISC_FIRST_ON_TAIL) {
+        STEP(tail_follows(l));
+        STEP(fold(l, FOLD_MISC, ctx->tail));
+    }
+    if (p.dup_place == DUP_ON_TAIL) STEP(p.claim_fused ? dup_tail(l, nullptr, ctx->tail) : dup_claim_chain(l, nullptr, false, ctx->tail));
+    if (p.join_tail) HIP_TRY(ctx, hipEventRecord(ctx->ev_tail, ctx->tail));
+    if (p.overrep == OVR_EARLY_ON_TAIL) {
+        STEP(tail_follows(l));
+        STEP(overrep(l, ctx->tail));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_tail, ctx->tail));   // (the launch stream waits for the tail stream below)
+    }
+
+    // the Stats kernel and what corrects its counts
+    if (p.stats) STEP(launch_stats(l));
+    if (p.front_stats && l.st_grid > 0) STEP(launch_front_stats(l));
+    if (p.corr_stats && l.st_grid > 0) STEP(launch_corr_stats(l));
+    HIP_TRY(ctx, hipEventRecord(e1, st));
+    ctx->pending_events.push_back({e0, e1});
+
+    // the folds; the launch stream joins the tail stream
+    if (p.misc_fold == MISC_WITH_STATS) {
+        STEP(fold(l, FOLD_STATS | FOLD_MISC, st));
+    } else {
+        STEP(fold(l, FOLD_STATS, st));
+        if (p.misc_fold != MISC_FIRST_ON_TAIL) STEP(fold(l, FOLD_MISC, p.misc_fold == MISC_LAST_ON_TAIL ? ctx->tail : st));
+        if (p.join_tail) HIP_TRY(ctx, hipEventRecord(ctx->ev_tail, ctx->tail));
+    }
+    if (p.join_tail) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_tail, 0));
+    else if (p.dup_place == DUP_AT_END) STEP(p.claim_fused ? dup_tail(l, nullptr, st) : dup_claim_chain(l, nullptr, mode == CHUNK_PASS1, st));
+    if (p.overrep == OVR_EARLY_ON_TAIL && !p.join_tail) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_tail, 0));
+    return p.overrep == OVR_AT_END ? overrep(l, st) : FASTP_GPU_OK;
 }
 
 

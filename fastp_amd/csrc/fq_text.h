@@ -29,7 +29,7 @@
 //         restarts comes to);
 //   * Stats' per-base counters of a workgroup's units are gathered in LDS tables and added to the int64 block once.
 //
-// How it composes with the plan's kernels (fastp_gpu.hip launch_chunk): those still sweep the whole launch, but on a
+// How it composes with the plan's kernels (fastp_gpu.hip, LaunchPlan::text): those still sweep the whole launch, but on a
 // copy of the length arrays in which the listed units are EMPTY reads.  What an empty unit adds to the counters is
 // exactly what this loop computes for an empty unit - so ONE wavefront of the launch runs the loop on an empty unit with
 // sign -(number of listed units) (the "ghost" pass: counters only; nothing in it depends on which unit it stands for), every

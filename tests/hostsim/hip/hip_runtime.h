@@ -30,6 +30,7 @@ struct dim3 {
     dim3(unsigned x_ = 1, unsigned y_ = 1, unsigned z_ = 1) : x(x_), y(y_), z(z_) {}
 };
 
+struct sim_stream;
 namespace sim {
 struct ThreadState;
 extern ThreadState* cur;
@@ -39,6 +40,7 @@ const Idx& block_idx();
 const Idx& block_dim();
 const Idx& grid_dim();
 void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()>& body);
+void trace_launch(const char* kernel, dim3 grid, dim3 block, size_t shmem, ::sim_stream* stream);
 void syncthreads();
 void wave_barrier();
 unsigned long long ballot(bool pred);
@@ -186,5 +188,6 @@ hipError_t hipGetLastError();
 hipError_t hipPeekAtLastError();
 inline hipError_t hipMemGetInfo(size_t* free_bytes, size_t* total_bytes) { *free_bytes = (size_t)8 << 30; *total_bytes = (size_t)16 << 30; return hipSuccess; }   // (a small card: the emulator keeps the small lists)
 
+// (FASTP_SIM_TRACE=<file>: every launch, async memset / copy, event record and stream wait is appended to the file, sim.cpp)
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-    sim::launch((grid), (block), (shmem), [&]() { kernel(__VA_ARGS__); })
+    (sim::trace_launch(#kernel, (grid), (block), (shmem), (stream)), sim::launch((grid), (block), (shmem), [&]() { kernel(__VA_ARGS__); }))

@@ -2,11 +2,13 @@
 // One ucontext coroutine per GPU thread; blocks run one after another; inside a block the
 // runnable threads are resumed in a shuffled order and run until their next rendezvous
 // (__syncthreads, wave barrier, __ballot, __shfl*) or until they return.
+#include <stdarg.h>
 #include <stdio.h>
 #include <sys/mman.h>
 #include <ucontext.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <mutex>
 #include <vector>
@@ -204,8 +206,33 @@ void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()>& bo
 }  // namespace sim
 
 // ---- fake runtime ---------------------------------------------------------------------
-struct sim_stream { int dummy; };
-struct sim_event { std::chrono::steady_clock::time_point t; };
+// streams and events carry the order of their creation in the process: the labels of the launch trace
+static std::atomic<int> sim_streams_made{0}, sim_events_made{0};
+struct sim_stream { int id = sim_streams_made++; };
+struct sim_event { std::chrono::steady_clock::time_point t; int id = sim_events_made++; };
+
+// The launch trace (tests/test_launch_trace.py).  The emulator runs every launch at once, so a kernel on the wrong stream or a
+// dropped wait changes no result; with FASTP_SIM_TRACE=<file> set, each launch, async memset / copy, event record and stream
+// wait appends one line to the file: what was asked for and on which stream, no addresses.
+// (read at every call: a test sets it once the engine exists, so that the trace starts behind fastp_gpu_create)
+static void sim_trace(const char* fmt, ...) {
+    const char* path = getenv("FASTP_SIM_TRACE");
+    if (!path || !*path) return;
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lock(mu);
+    FILE* f = fopen(path, "a");
+    if (!f) return;
+    va_list ap;
+    va_start(ap, fmt);
+    vfprintf(f, fmt, ap);
+    va_end(ap);
+    fclose(f);
+}
+static int sim_label(hipStream_t s) { return s ? s->id : -1; }   // (-1: the null stream)
+void sim::trace_launch(const char* kernel, dim3 grid, dim3 block, size_t shmem, hipStream_t stream) {
+    // a token that is not a kernel's name is a launch through a pointer (the lane kernel's instantiations)
+    sim_trace("launch %s grid=%u block=%u lds=%zu s%d\n", strncmp(kernel, "fq_", 3) ? "(pointer)" : kernel, grid.x, block.x, shmem, sim_label(stream));
+}
 
 hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 hipError_t hipSetDevice(int) { return hipSuccess; }
@@ -225,7 +252,11 @@ hipError_t hipHostMalloc(void** p, size_t bytes) { *p = calloc(bytes ? bytes : 1
 hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
 hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }   // launches run to completion inside hipLaunchKernelGGL
 hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return hipSuccess; }
-hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memcpy(d, s, n); return hipSuccess; }
+hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t st) {
+    sim_trace("memcpy %s bytes=%zu s%d\n", k == hipMemcpyHostToDevice ? "H2D" : k == hipMemcpyDeviceToHost ? "D2H" : "D2D", n, sim_label(st));
+    memcpy(d, s, n);
+    return hipSuccess;
+}
 hipError_t hipMemcpy2DAsync(void* d, size_t dpitch, const void* s, size_t spitch, size_t width, size_t height, hipMemcpyKind, hipStream_t) {
     if (width > dpitch || width > spitch) return hipErrorUnknown;
     for (size_t r = 0; r < height; r++) memcpy((char*)d + r * dpitch, (const char*)s + r * spitch, width);
@@ -246,18 +277,29 @@ static void sim_fill(void* d, int v, size_t n) {
     }
     memset(d, v, n);
 }
-hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { sim_fill(d, v, n); return hipSuccess; }
+hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st) {
+    sim_trace("memset value=%d bytes=%zu s%d\n", v, n, sim_label(st));
+    sim_fill(d, v, n);
+    return hipSuccess;
+}
 hipError_t hipMemset(void* d, int v, size_t n) { sim_fill(d, v, n); return hipSuccess; }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = new sim_stream(); return hipSuccess; }
 hipError_t hipStreamDestroy(hipStream_t s) { delete s; return hipSuccess; }
 hipError_t hipExtStreamCreateWithCUMask(hipStream_t* s, uint32_t, const uint32_t*) { *s = new sim_stream(); return hipSuccess; }
-hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
+    sim_trace("wait s%d e%d\n", sim_label(s), e->id);
+    return hipSuccess;
+}
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new sim_event(); return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 hipError_t hipDeviceSynchronize() { return hipSuccess; }
 hipError_t hipEventCreate(hipEvent_t* e) { *e = new sim_event(); return hipSuccess; }
 hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
-hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { e->t = std::chrono::steady_clock::now(); return hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
+    sim_trace("record e%d s%d\n", e->id, sim_label(s));
+    e->t = std::chrono::steady_clock::now();
+    return hipSuccess;
+}
 hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
     *ms = std::chrono::duration<float, std::milli>(b->t - a->t).count();
