@@ -2034,6 +2034,7 @@ extern "C" int fastp_gpu_parse_fastq(fastp_gpu_ctx* ctx, const uint8_t* text, in
     if (!ctx || !info || nbytes < 0 || max_records < 0) return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
     memset(info, 0, sizeof(*info));
     info->first_bad = -1;
+    ctx->parse_exotic.clear();  // also when nothing is parsed: fastp_gpu_parse_exotic answers for THIS call
     if (nbytes == 0 || max_records == 0) return FASTP_GPU_OK;
     if (!text || !seq_out || !qual_out || !len_out || !line_off || !line_len) return fail(ctx, FASTP_GPU_E_INVALID, "null buffer");
     if (((uintptr_t)text & 15u) != 0) return fail(ctx, FASTP_GPU_E_INVALID, "text must be 16-byte aligned (and padded to 16 bytes)");
@@ -2067,7 +2068,6 @@ extern "C" int fastp_gpu_parse_fastq(fastp_gpu_ctx* ctx, const uint8_t* text, in
     p.term_len = (u8*)(p.term_pos + p.max_lines);
     p.exotic_list = p.term_pos + p.max_lines + (p.max_lines + 3) / 4 + 1;
     p.exotic_cap = (u32)max_records;
-    ctx->parse_exotic.clear();
     const u32 init[8] = {0, 0xFFFFFFFFu, 0, 0, 0, 0, 0, 0};
     HIP_TRY(ctx, hipMemcpyAsync(p.totals, init, sizeof(init), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(fq_parse_count_kernel, dim3(nblocks), dim3(PARSE_BLOCK), 16, st, p);

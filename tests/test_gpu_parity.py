@@ -813,6 +813,17 @@ def test_gpu_bgzf_inflate_survives_corruption(variant, monkeypatch):
     hs._corruption_case(engines.gpu_engine, format_util.TorchMem(), 3000, 0xff00, 120, 60)
 
 
+@pytest.mark.twin("test_sim_bgzf_inflate_members_with_several_deflate_blocks")
+@pytest.mark.parametrize("variant", ["wave", "lane"])
+def test_gpu_bgzf_inflate_members_with_several_deflate_blocks(variant, monkeypatch):
+    """BGZF members that chain dynamic, fixed, stored and empty stored blocks, with matches across their borders (bgzip writes
+    none, other writers do), through either inflate kernel: the same 50 000-byte text and assertions as on the emulator"""
+    import format_util
+    import test_hostsim_parity as hs
+    monkeypatch.setenv("FASTP_GPU_INFLATE", variant)
+    hs._several_deflate_blocks_case(engines.gpu_engine, format_util.TorchMem())
+
+
 def test_gpu_file_pipeline_reads_bgzf(tmp_path):
     """the same pipeline fed BGZF-compressed inputs (inflated on the device): same output files, same counters"""
     import bgzf_util

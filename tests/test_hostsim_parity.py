@@ -882,14 +882,11 @@ def test_sim_bgzf_inflate_lane_variant(monkeypatch):
     assert rc == 0 and bad == -1 and got == text
 
 
-@pytest.mark.parametrize("variant", ["wave", "lane"])
-def test_sim_bgzf_inflate_members_with_several_deflate_blocks(variant, monkeypatch):
+def _several_deflate_blocks_case(mk_engine, mem):
     """a member whose DEFLATE stream is a chain of blocks of every kind: dynamic, fixed (Z_FIXED pieces), stored (level 0
     pieces), empty stored blocks (sync flushes) - matches that reach back across block borders included"""
     import struct
     import zlib
-    import format_util
-    monkeypatch.setenv("FASTP_GPU_INFLATE", variant)
     text = _se_fastq_text(160, 9)[:50000]
     members = []
     for start in range(0, len(text), 25000):
@@ -916,10 +913,18 @@ def test_sim_bgzf_inflate_members_with_several_deflate_blocks(variant, monkeypat
         hdr = b"\x1f\x8b\x08\x04" + b"\0\0\0\0" + b"\x00\xff" + struct.pack("<H", 6) + b"BC" + struct.pack("<HH", 2, bsize - 1)
         members.append(hdr + payload + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data)))
     comp = b"".join(members)
-    g = engines.sim_engine(abi.default_params(False, 150))
-    info, rc, bad, got = _inflate(g, format_util.NumpyMem(), comp)
+    g = mk_engine(abi.default_params(False, 150))
+    info, rc, bad, got = _inflate(g, mem, comp)
     g.close()
     assert rc == 0 and bad == -1 and got == text and info.n_blocks == 2
+
+
+@pytest.mark.parametrize("variant", ["wave", "lane"])
+def test_sim_bgzf_inflate_members_with_several_deflate_blocks(variant, monkeypatch):
+    """members of several DEFLATE blocks (_several_deflate_blocks_case) through either inflate kernel"""
+    import format_util
+    monkeypatch.setenv("FASTP_GPU_INFLATE", variant)
+    _several_deflate_blocks_case(engines.sim_engine, format_util.NumpyMem())
 
 
 def test_sim_bgzf_index_chunks_and_errors():
