@@ -195,7 +195,12 @@ extern "C" __global__ void __launch_bounds__(64) fq_inflate_wave_kernel(InflateA
 }
 extern "C" __global__ void __launch_bounds__(64) fq_deflate_kernel(DeflateArgs a) {
     extern __shared__ u32 fq_lds[];
-    deflate_body(a, fq_lds);
+    deflate_body<DefLds>(a, fq_lds);
+}
+// levels 5..9: the chain stage of fq_deflate.h (its own LDS layout, its own blocks per CU)
+extern "C" __global__ void __launch_bounds__(64) fq_deflate_chain_kernel(DeflateArgs a) {
+    extern __shared__ u32 fq_lds[];
+    deflate_body<DefChainLds>(a, fq_lds);
 }
 extern "C" __global__ void __launch_bounds__(1024) fq_deflate_scan_kernel(DeflateArgs a) {
     extern __shared__ u32 fq_lds[];
@@ -339,7 +344,7 @@ struct fastp_gpu_ctx {
     int* d_ovr_len[2] = {nullptr, nullptr};
     u64* d_post_seen = nullptr;
     u32* d_ovr_work = nullptr; size_t ovr_work_cap = 0;   // blocksum | blockbase | n_tasks | tasks
-    u8* d_def = nullptr; size_t def_cap = 0;              // deflate scratch: member slots | tokens | sizes | offsets
+    u8* d_def = nullptr; size_t def_cap = 0;              // deflate scratch: member slots | tokens | sizes | offsets | (levels 5..9) chains
     u8* d_eval = nullptr; size_t eval_cap = 0;            // Evaluator pre-pass: census table | hot list | text
     u32* d_ovr_corr = nullptr; size_t ovr_corr_cap = 0;   // correction chains: head[reads] | next[capacity]
     u32* d_parse = nullptr; size_t parse_cap = 0;         // FASTQ parse scratch
@@ -803,6 +808,7 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
         std::vector<std::pair<const char*, long long>> need = {{name, (long long)ctx->L.total * 4}, {"hash kernel", (long long)ctx->L.total * 4},
                                                                {"text kernel", (long long)TEXT_WAVES * text_wave_bytes((ctx->dp.max_len + 8 + 7) & ~7)},
                                                                {"deflate kernel", (long long)sizeof(DefLds)},
+                                                               {"deflate kernel (levels 5 to 9)", (long long)sizeof(DefChainLds)},
                                                                {"inflate kernel", (long long)(INF_ENTRIES * INF_LANES * 2 + INF_SBUF * INF_LANES * 4)}};
         if (ctx->split) need.push_back({ctx->st_form == 5 ? "Stats kernel (form 5)" : "Stats kernel", (long long)ctx->st_lds_dwords * 4});
         if (ctx->lane) need.push_back({"lane kernel", (long long)ctx->ln_lds.total * 4});
@@ -915,6 +921,7 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
     CREATE_TRY(hipFuncSetAttribute((const void*)fq_ovr_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, aux_lds_cap(ctx)));
     CREATE_TRY(hipFuncSetAttribute((const void*)fq_text_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, aux_lds_cap(ctx)));
     CREATE_TRY(hipFuncSetAttribute((const void*)fq_deflate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(DefLds)));
+    CREATE_TRY(hipFuncSetAttribute((const void*)fq_deflate_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(DefChainLds)));
     if ((int)sizeof(IwLds) <= ctx->lds_bytes)   // (a card with less LDS inflates with the lane kernel only)
         CREATE_TRY(hipFuncSetAttribute((const void*)fq_inflate_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(IwLds)));
     CREATE_TRY(hipFuncSetAttribute((const void*)fq_inflate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2548,10 +2555,15 @@ extern "C" int fastp_gpu_eval_overrep(fastp_gpu_ctx* ctx, const uint8_t* seq, co
 }
 
 // ---- output text -> BGZF-framed gzip members (fq_deflate.h) ------------------------------------------------
-extern "C" int fastp_gpu_deflate_bgzf(fastp_gpu_ctx* ctx, const uint8_t* text, int64_t nbytes, int write_eof, uint8_t* out,
-                                      int64_t out_capacity, int64_t* out_len) {
+// the reference's -z (1..9; 0 = the default) -> the match stage: levels up to 4 are the one-candidate greedy stage, 5..7 and 8..9
+// the chain stage at two depths (DESIGN.md 7 has the table and what each tier costs)
+extern "C" int fastp_gpu_deflate_bgzf_level(fastp_gpu_ctx* ctx, const uint8_t* text, int64_t nbytes, int write_eof, int level, uint8_t* out,
+                                            int64_t out_capacity, int64_t* out_len) {
     if (!ctx || !out_len || nbytes < 0 || out_capacity < 0 || (nbytes > 0 && !text) || (out_capacity > 0 && !out))
         return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
+    if (level < 0 || level > 9) return fail(ctx, FASTP_GPU_E_INVALID, "compression level outside 0..9");
+    const bool chain = level >= 5;
+    const u32 chain_depth = level >= 8 ? 16u : 4u, chain_lazy = 32u;
     *out_len = 0;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
@@ -2560,10 +2572,11 @@ extern "C" int fastp_gpu_deflate_bgzf(fastp_gpu_ctx* ctx, const uint8_t* text, i
     // a round = what is in flight at once (a wavefront per block, eight per CU): the scratch is sized by it - 4 bytes of
     // tokens per input byte + a member slot per block - so a larger round only costs HBM
     const int round = (int)std::min<int64_t>(total_blocks, (int64_t)ctx->cus * 8);
+    const int chain_grid = chain ? std::min(round, ctx->cus * std::max(1, ctx->lds_bytes / (int)sizeof(DefChainLds))) : 0;
     if (round > 0) {
         const size_t b_slots = (size_t)round * DEF_SLOT, b_tok = (size_t)round * DEF_BLOCK * 4, b_sizes = (size_t)round * 4 + 8,
-                     b_offs = ((size_t)round + 1) * 8;
-        int rc = ensure(ctx, (void**)&ctx->d_def, &ctx->def_cap, b_slots + b_tok + b_sizes + b_offs);
+                     b_offs = ((size_t)round + 1) * 8, b_prev = (size_t)chain_grid * DEF_PREV * 2;   // (a chain array per RESIDENT workgroup: 128 KB x 5 per CU)
+        int rc = ensure(ctx, (void**)&ctx->d_def, &ctx->def_cap, b_slots + b_tok + b_sizes + b_offs + b_prev);
         if (rc) return rc;
     }
     u64 written = 0;   // bytes needed so far
@@ -2580,8 +2593,16 @@ extern "C" int fastp_gpu_deflate_bgzf(fastp_gpu_ctx* ctx, const uint8_t* text, i
         a.out = out;
         a.out_base = written;
         a.out_cap = (u64)out_capacity;
-        const int grid = std::min(a.nblocks, ctx->cus * std::max(1, ctx->lds_bytes / (int)sizeof(DefLds)));
-        hipLaunchKernelGGL(fq_deflate_kernel, dim3(grid), dim3(64), sizeof(DefLds), st, a);
+        if (chain) {
+            a.prev = (u16*)((u8*)a.offs + ((size_t)round + 1) * 8);
+            a.depth = chain_depth;
+            a.lazy_max = chain_lazy;
+            const int grid = std::min(a.nblocks, chain_grid);
+            hipLaunchKernelGGL(fq_deflate_chain_kernel, dim3(grid), dim3(64), sizeof(DefChainLds), st, a);
+        } else {
+            const int grid = std::min(a.nblocks, ctx->cus * std::max(1, ctx->lds_bytes / (int)sizeof(DefLds)));
+            hipLaunchKernelGGL(fq_deflate_kernel, dim3(grid), dim3(64), sizeof(DefLds), st, a);
+        }
         HIP_TRY(ctx, hipGetLastError());
         hipLaunchKernelGGL(fq_deflate_scan_kernel, dim3(1), dim3(1024), 1024 * 8, st, a);
         HIP_TRY(ctx, hipGetLastError());
@@ -2602,6 +2623,11 @@ extern "C" int fastp_gpu_deflate_bgzf(fastp_gpu_ctx* ctx, const uint8_t* text, i
     *out_len = (int64_t)written;
     if (written > (u64)out_capacity) return fail(ctx, FASTP_GPU_E_OVERFLOW, "output buffer too small (see out_len for the needed size)");
     return FASTP_GPU_OK;
+}
+
+extern "C" int fastp_gpu_deflate_bgzf(fastp_gpu_ctx* ctx, const uint8_t* text, int64_t nbytes, int write_eof, uint8_t* out,
+                                      int64_t out_capacity, int64_t* out_len) {
+    return fastp_gpu_deflate_bgzf_level(ctx, text, nbytes, write_eof, 0, out, out_capacity, out_len);
 }
 
 extern "C" int fastp_gpu_device_alloc(fastp_gpu_ctx* ctx, int64_t bytes, void** dev_ptr) {

@@ -13,6 +13,8 @@
 //   emit     64 tokens per step: bit lengths scanned across the wave, bits OR-ed into an LDS window, whole
 //            dwords flushed to the member
 //   crc      CRC-32 by 64 lanes x 1 KiB slices combined with precomputed zero-shift operators
+// match and select above are the stage of compression levels 1..4 (def_parse_greedy); levels 5..9 put def_parse_chain in their
+// place - hash chains walked to a depth, a lazy parse, a cost rule for short matches - and share everything from `count` on.
 // Whichever is smaller, the dynamic block or a stored block, is written.  The bytes differ from libdeflate's
 // (DEFLATE has no canonical encoding); what is checked is that every inflater returns the text.
 #pragma once
@@ -25,6 +27,8 @@ enum {
     DEF_BLOCK = 65280,            // text bytes per member (bgzip's own block size: 0xff00)
     DEF_SLOT = 65536 + 64,        // scratch bytes per member; the member starts at +2 so its DEFLATE stream is dword aligned
     DEF_HASH_BITS = 12,           // 8 KB of LDS: ~19 KB per block in all, eight blocks per CU in flight
+    DEF_CHAIN_HASH_BITS = 13,     // the chain stage (levels 5..9): 16 KB, ~27 KB per block, five blocks per CU
+    DEF_PREV = 65536,             // chain entries per workgroup (u16 each, HBM scratch; reused for every block the workgroup takes)
     DEF_WIN = 256,                // LDS bit window, dwords
     DEF_PROBE = 36,               // bytes a lane compares for its own candidate
     DEF_NLL = 288, DEF_ND = 32, DEF_NCL = 20
@@ -40,6 +44,10 @@ struct DeflateArgs {
     u64* offs;           // [nblocks] where each member goes in out (relative to out_base), [nblocks] = total
     u8* out;
     u64 out_base, out_cap;
+    // the chain stage only (fq_deflate_chain_kernel)
+    u16* prev;           // [workgroups of the launch][DEF_PREV] the earlier position of the same bucket, per position of the block in hand
+    u32 depth;           // candidates a lane looks at per position
+    u32 lazy_max;        // a match shorter than this waits for the next position's (0: greedy; at most DEF_PROBE)
 };
 
 // CRC-32 of up to 64 KiB by one wavefront: the byte table and the operators "append 1024 * 2^k zero bytes"
@@ -48,8 +56,9 @@ struct CrcLds {
     u32 mat[6][32];
 };
 
-struct DefLds {
-    u16 head[1 << DEF_HASH_BITS];
+template <int HASH_BITS> struct DefLdsT {
+    enum { HB = HASH_BITS };
+    u16 head[1 << HASH_BITS];
     u32 hist_ll[DEF_NLL], hist_d[DEF_ND], hist_cl[DEF_NCL];
     u32 code_ll[DEF_NLL], code_d[DEF_ND], code_cl[DEF_NCL];   // bit-reversed code | length << 16
     u8 len_ll[DEF_NLL], len_d[DEF_ND], len_cl[DEF_NCL];
@@ -62,6 +71,8 @@ struct DefLds {
     CrcLds crc;
     u32 win[DEF_WIN];
 };
+typedef DefLdsT<DEF_HASH_BITS> DefLds;             // levels 1..4
+typedef DefLdsT<DEF_CHAIN_HASH_BITS> DefChainLds;  // levels 5..9
 
 FQ_DEV u32 def_ld4(const u8* p) {
     u32 w;
@@ -156,7 +167,7 @@ FQ_DEV u32 def_crc32(const CrcLds& S, const u8* in, u32 n, int lane) {
 // ---- length-limited Huffman code of n symbols ---------------------------------------------------------------
 FQ_DEV u32 def_bitrev(u32 c, u32 len) { return brev32(c) >> (32u - len); }
 
-FQ_DEV void def_build(DefLds& S, const u32* freq, int n, int maxbits, u8* len, u32* code, int lane) {
+template <class LDS> FQ_DEV void def_build(LDS& S, const u32* freq, int n, int maxbits, u8* len, u32* code, int lane) {
     int used = 0;
     for (int s = lane; s < n; s += 64) {
         len[s] = 0;
@@ -242,14 +253,14 @@ FQ_DEV void def_build(DefLds& S, const u32* freq, int n, int maxbits, u8* len, u
 
 // ---- the bit window -----------------------------------------------------------------------------------------
 // win[0] holds the partly filled dword at bit cursor `cur` (bits of the DEFLATE stream written so far)
-FQ_DEV void def_put_serial(DefLds& S, u32& cur_local, u32 base_bits, u32 v, u32 nb) {   // one lane, nb <= 16
+template <class LDS> FQ_DEV void def_put_serial(LDS& S, u32& cur_local, u32 base_bits, u32 v, u32 nb) {   // one lane, nb <= 16
     const u32 off = cur_local - base_bits;
     S.win[off >> 5] |= v << (off & 31u);
     if ((off & 31u) + nb > 32u) S.win[(off >> 5) + 1u] |= v >> (32u - (off & 31u));
     cur_local += nb;
 }
 // flush the whole dwords of the window [base dword of old_cur, new_cur) to the stream, keep the partial one
-FQ_DEV void def_flush(DefLds& S, u32* stream, u32 old_cur, u32 new_cur, int lane) {
+template <class LDS> FQ_DEV void def_flush(LDS& S, u32* stream, u32 old_cur, u32 new_cur, int lane) {
     wave_sync();
     const u32 w0 = old_cur >> 5, w1 = new_cur >> 5;   // dwords [w0, w1) are complete
     const u32 nfull = w1 - w0;
@@ -267,25 +278,9 @@ FQ_DEV void def_flush(DefLds& S, u32* stream, u32 old_cur, u32 new_cur, int lane
     wave_sync();
 }
 
-FQ_DEV void deflate_block(const DeflateArgs& a, DefLds& S, int blk, int lane) {
-    const u64 start = (u64)blk * DEF_BLOCK;
-    const u32 n = (u32)(a.nbytes - start < (u64)DEF_BLOCK ? a.nbytes - start : (u64)DEF_BLOCK);
-    // (Staging the block's text in LDS was measured and dropped: 93 KB per block leaves one wavefront per CU, and a
-    // single wavefront's time is set by instruction latency either way - 3.5 ms per block against 4.1 from global memory
-    // with five blocks per CU in flight.)
-    const u8* in = a.text + start;
-    u8* member = a.slots + (size_t)blk * DEF_SLOT + 2;
-    u32* stream = (u32*)(member + 18);
-    u32* tok = a.tokens + (size_t)blk * DEF_BLOCK;
-
-    for (int i = lane; i < (1 << DEF_HASH_BITS); i += 64) S.head[i] = 0xFFFFu;
-    for (int i = lane; i < DEF_NLL; i += 64) S.hist_ll[i] = 0;
-    if (lane < DEF_ND) S.hist_d[lane] = 0;
-    if (lane < DEF_NCL) S.hist_cl[lane] = 0;
-    for (int i = lane; i < DEF_WIN; i += 64) S.win[i] = 0;
-    wave_sync();
-
-    // ---- match, select, count ----
+// ---- match, select, count: one candidate per position, greedy (levels 1..4) -----------------------------------
+// returns the number of tokens written
+FQ_DEV u32 def_parse_greedy(DefLds& S, const u8* in, u32 n, u32* tok, int lane) {
     u32 ntok = 0, carry = 0;
     for (u32 base = 0; base < n; base += 64u) {
         const u32 p = base + (u32)lane;
@@ -371,6 +366,238 @@ FQ_DEV void deflate_block(const DeflateArgs& a, DefLds& S, int blk, int lane) {
         }
         ntok += (u32)popc64(starts);
     }
+    return ntok;
+}
+
+// ---- match, select, count: hash chains, lazy parse, cost rule (levels 5..9) -----------------------------------
+// 4 * log2(v) rounded down to a quarter (the two bits below the leading one as the fraction): integers only, so the
+// emulator and the device take the same decisions
+FQ_DEV u32 def_lg4(u32 v) {
+    const u32 e = (u32)def_log2(v);
+    return 4u * e + (((v << 2) >> e) & 3u);
+}
+// the match at pj of L bytes (so far) at distance dj, extended to at most mx by the whole wave: 4 bytes per lane
+FQ_DEV u32 def_extend(const u8* t, u32 pj, u32 dj, u32 L, u32 mx, int lane) {
+    while (L < mx) {
+        const u32 k = L + 4u * (u32)lane;
+        u32 same = 0;   // bytes of this lane's dword that match (from its low end), capped by mx
+        if (k < mx) {
+            const u32 lim = mx - k < 4u ? mx - k : 4u;
+            if (lim == 4u) {
+                const u32 x = def_ld4(t + pj + k) ^ def_ld4(t + pj - dj + k);
+                same = x ? (u32)(def_ctz32(x) >> 3) : 4u;
+            } else {
+                while (same < lim && t[pj + k + same] == t[pj - dj + k + same]) same++;
+            }
+        }
+        const u64 stop = ballot(same < 4u);
+        const u32 f = stop ? (u32)ffs64(stop) - 1u : 64u;
+        L += 4u * f + (f < 64u ? shfl(same, (int)f) : 0u);
+        if (f < 64u) break;
+    }
+    return L > mx ? mx : L;
+}
+enum {
+    DEF_COST_MATCH = 4 * 12,      // quarter bits: what a match's length and distance symbols cost before their extra bits
+    DEF_COST_LEN = 16,            // matches of at least this many bytes are taken without the estimate
+    DEF_LEN_WEIGHT = 4            // quarter bits a byte of length is worth against a distance's extra bits when candidates are compared
+};
+// What differs from def_parse_greedy:
+//   candidates  head[] (most recent position of the bucket) + prev[] (the one before, per position, HBM scratch): a lane walks
+//               its bucket's chain to `depth` and keeps a longer match when its length is worth its distance (one bit per
+//               byte against the distance's extra bits: the longest match at any distance made the output LARGER at a
+//               deeper search), the nearest on ties.  Only positions whose four bytes equal the lane's are compared, so
+//               length 3 is left to distance 1.
+//   inserts     all lanes take prev[p] from the head as it was before the step, then the HIGHEST position of a bucket becomes
+//               its head (stores repeated until no lane holds a higher one): the same table on every machine.  The lower
+//               positions of the step that share the bucket are not linked - they lie within 63 bytes of one that is.
+//   cost rule   a match under DEF_COST_LEN bytes is dropped when its symbols and extra bits cost at least what its bytes
+//               cost as literals, estimated from the block's byte counts (lit[]): four bases are ~9 bits, a far length-4
+//               match ~20.
+//   lazy        a match shorter than lazy_max is left for a literal when the next position holds a longer one.  Inside a
+//               step that is a hop along the ballot; the last lane's match waits (dlen, ddist) for lane 0 of the next step,
+//               whose lanes then all look for candidates.  The last position of a block has no successor and is taken.
+template <class LDS> FQ_DEV u32 def_parse_chain(LDS& S, const u8* in, u32 n, u32* tok, u16* prev, u32 depth, u32 lazy_max, int lane) {
+    // literal costs in quarter bits, in cl_sym[] (free until the code lengths are run-length coded); counts in hist_ll[]
+    u8* lit = S.cl_sym;
+    for (u32 i = 4u * (u32)lane; i < n; i += 256u) {
+        if (i + 4u <= n) {
+            const u32 w = def_ld4(in + i);
+            for (int k = 0; k < 4; k++) lds_add_u32(&S.hist_ll[(w >> (8 * k)) & 0xFFu], 1u);
+        } else {
+            for (u32 k = i; k < n; k++) lds_add_u32(&S.hist_ll[in[k]], 1u);
+        }
+    }
+    wave_sync();
+    const u32 lgn = n ? def_lg4(n) : 0u;
+    u32 cst[4];
+    for (int k = 0; k < 4; k++) {
+        const u32 c = S.hist_ll[k * 64 + lane];
+        const u32 v = c ? lgn - def_lg4(c) : 60u;
+        cst[k] = v < 4u ? 4u : v;
+    }
+    wave_sync();
+    for (int k = 0; k < 4; k++) {
+        lit[k * 64 + lane] = (u8)cst[k];
+        S.hist_ll[k * 64 + lane] = 0;
+    }
+    wave_sync();
+    if (lazy_max > (u32)DEF_PROBE) lazy_max = (u32)DEF_PROBE;   // a waiting match is never one whose probe was cut short
+
+    u32 ntok = 0, carry = 0, dlen = 0, ddist = 0;   // dlen != 0: the match of position base - 1 waits for this step's lane 0
+    for (u32 base = 0; base < n; base += 64u) {
+        const u32 p = base + (u32)lane;
+        const u32 cnt = n - base < 64u ? n - base : 64u;
+        u32 mlen = 0, mdist = 0, h = 0xFFFFFFFFu, old = 0xFFFFu;
+        u32 maxl = 0;
+        if ((u32)lane < cnt && p + 4u <= n) {
+            const u32 w = def_ld4(in + p);
+            h = (w * 2654435761u) >> (32 - LDS::HB);
+            old = S.head[h];
+            if ((u32)lane >= carry) {
+                maxl = n - p < 258u ? n - p : 258u;
+                const u32 probe = maxl < (u32)DEF_PROBE ? maxl : (u32)DEF_PROBE;
+                u32 c = old;
+                int score = 0;   // DEF_LEN_WEIGHT per byte less the distance's extra bits: a byte more is not worth any distance
+                for (u32 d = 0; d < depth && c != 0xFFFFu && p - c <= 32768u; d++) {
+                    const u32 nx = prev[c];   // (< c: the chain ends by itself)
+                    if (def_ld4(in + c) == w) {
+                        const u32 l = def_match(in + p, in + c, probe);
+                        u32 eb, ev;
+                        def_dist_sym(p - c, eb, ev);
+                        const int sc = (int)(l * (u32)DEF_LEN_WEIGHT) - (int)(4u * eb);
+                        if (l > mlen && sc > score) {   // (the nearest on ties: the chain runs from near to far)
+                            mlen = l;
+                            mdist = p - c;
+                            score = sc;
+                            if (l >= probe) break;
+                        }
+                    }
+                    c = nx;
+                }
+                if (p >= 1u) {
+                    const u32 l = def_match(in + p, in + p - 1, probe);
+                    if (l >= 3u && (int)(l * (u32)DEF_LEN_WEIGHT) >= score) { mlen = l; mdist = 1u; }
+                }
+                if (mlen >= 3u && mlen < (u32)DEF_COST_LEN) {
+                    u32 eb, ev, cost = (u32)DEF_COST_MATCH, as_literals = 0;
+                    def_len_sym(mlen, eb, ev);
+                    cost += 4u * eb;
+                    def_dist_sym(mdist, eb, ev);
+                    cost += 4u * eb;
+                    for (u32 k = 0; k < mlen; k++) as_literals += lit[in[p + k]];
+                    if (cost >= as_literals) mlen = 0;
+                }
+            }
+        }
+        wave_sync();   // every lookup before any insert of this step
+        bool pend = h != 0xFFFFFFFFu;
+        if (pend) prev[p] = (u16)old;
+        while (ballot(pend)) {
+            if (pend) S.head[h] = (u16)p;
+            wave_sync();
+            if (pend && S.head[h] >= p) pend = false;   // this lane's, or a higher position of this step
+            wave_sync();
+        }
+        const u64 mmask = ballot(mlen >= 3u);
+        const u64 live = cnt == 64u ? ~0ull : (1ull << cnt) - 1ull;
+        u64 starts = 0, mstart = 0;
+        u32 pos = carry;
+        if (dlen) {   // (carry is 0) position base - 1: a literal if this step's first position matches longer
+            const u32 L0 = shfl(mlen, 0);
+            if (lane == 0) {
+                u32 eb, ev;
+                if (L0 > dlen) {
+                    const u32 b = in[base - 1u];
+                    tok[ntok] = b;
+                    lds_add_u32(&S.hist_ll[b], 1u);
+                } else {
+                    tok[ntok] = 0x80000000u | ((dlen - 3u) << 15) | (ddist - 1u);
+                    lds_add_u32(&S.hist_ll[def_len_sym(dlen, eb, ev)], 1u);
+                    lds_add_u32(&S.hist_d[def_dist_sym(ddist, eb, ev)], 1u);
+                }
+            }
+            ntok++;
+            if (L0 <= dlen) pos = dlen - 1u;
+            dlen = 0;
+        }
+        while (pos < cnt) {
+            const u64 m = mmask & (~0ull << pos);
+            if (!m) {
+                starts |= (~0ull << pos) & live;
+                pos = cnt;
+                break;
+            }
+            u32 j = (u32)ffs64(m) - 1u;
+            u32 L = shfl(mlen, (int)j);
+            bool wait = false;
+            while (L < lazy_max) {
+                if (j + 1u < cnt) {
+                    const u32 Ln = shfl(mlen, (int)j + 1);
+                    if (Ln <= L) break;
+                    j++;        // j becomes a literal
+                    L = Ln;
+                } else {
+                    wait = base + cnt < n;   // the next step decides (j == 63)
+                    break;
+                }
+            }
+            if (wait) {
+                starts |= (~0ull << pos) & ((1ull << j) - 1ull);   // literals [pos, j)
+                dlen = L;
+                ddist = shfl(mdist, (int)j);
+                pos = 64u;
+                break;
+            }
+            starts |= (~0ull << pos) & ((2ull << j) - 1ull);   // literals [pos, j) and the match at j
+            mstart |= 1ull << j;
+            const u32 mx = shfl(maxl, (int)j);
+            if (L >= (u32)DEF_PROBE && L < mx) {
+                L = def_extend(in, base + j, shfl(mdist, (int)j), L, mx, lane);
+                if ((u32)lane == j) mlen = L;
+            }
+            pos = j + L;
+        }
+        carry = pos >= 64u ? pos - 64u : 0u;
+        if ((starts >> lane) & 1ull) {
+            const u32 idx = ntok + (u32)popc64(starts & ((1ull << lane) - 1ull));
+            if ((mstart >> lane) & 1ull) {
+                u32 eb, ev;
+                tok[idx] = 0x80000000u | ((mlen - 3u) << 15) | (mdist - 1u);
+                lds_add_u32(&S.hist_ll[def_len_sym(mlen, eb, ev)], 1u);
+                lds_add_u32(&S.hist_d[def_dist_sym(mdist, eb, ev)], 1u);
+            } else {
+                const u32 b = in[p];
+                tok[idx] = b;
+                lds_add_u32(&S.hist_ll[b], 1u);
+            }
+        }
+        ntok += (u32)popc64(starts);
+    }
+    return ntok;
+}
+
+template <class LDS> FQ_DEV void deflate_block(const DeflateArgs& a, LDS& S, int blk, int lane) {
+    const u64 start = (u64)blk * DEF_BLOCK;
+    const u32 n = (u32)(a.nbytes - start < (u64)DEF_BLOCK ? a.nbytes - start : (u64)DEF_BLOCK);
+    // (Staging the block's text in LDS was measured and dropped: 93 KB per block leaves one wavefront per CU, and a
+    // single wavefront's time is set by instruction latency either way - 3.5 ms per block against 4.1 from global memory
+    // with five blocks per CU in flight.)
+    const u8* in = a.text + start;
+    u8* member = a.slots + (size_t)blk * DEF_SLOT + 2;
+    u32* stream = (u32*)(member + 18);
+    u32* tok = a.tokens + (size_t)blk * DEF_BLOCK;
+
+    for (int i = lane; i < (1 << LDS::HB); i += 64) S.head[i] = 0xFFFFu;
+    for (int i = lane; i < DEF_NLL; i += 64) S.hist_ll[i] = 0;
+    if (lane < DEF_ND) S.hist_d[lane] = 0;
+    if (lane < DEF_NCL) S.hist_cl[lane] = 0;
+    for (int i = lane; i < DEF_WIN; i += 64) S.win[i] = 0;
+    wave_sync();
+
+    u32 ntok;
+    if constexpr (LDS::HB == DEF_HASH_BITS) ntok = def_parse_greedy(S, in, n, tok, lane);
+    else ntok = def_parse_chain(S, in, n, tok, a.prev + (size_t)block_id() * DEF_PREV, a.depth, a.lazy_max, lane);
     wave_sync();
     if (lane == 0) S.hist_ll[256] = 1;   // end of block
     wave_sync();
@@ -530,8 +757,8 @@ FQ_DEV void deflate_block(const DeflateArgs& a, DefLds& S, int blk, int lane) {
     wave_sync();
 }
 
-FQ_DEV void deflate_body(const DeflateArgs& a, u32* ldsw) {
-    DefLds& S = *(DefLds*)ldsw;
+template <class LDS> FQ_DEV void deflate_body(const DeflateArgs& a, u32* ldsw) {
+    LDS& S = *(LDS*)ldsw;
     const int lane = lane_id();
     def_crc_setup(S.crc, lane);
     for (int blk = block_id(); blk < a.nblocks; blk += grid_blocks()) deflate_block(a, S, blk, lane);

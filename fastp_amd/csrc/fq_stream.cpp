@@ -237,6 +237,8 @@ struct fastp_gpu_stream {
     int32_t* h_counts = nullptr;   // pinned: n_corrections, n_adapter_events
     hipStream_t sx = nullptr, cp_in = nullptr;
     bool any_out = false;
+    int deflate_level = 0;         // of every compressed stream (fastp_gpu_stream_set_deflate_level, FASTP_GPU_STREAM_DEFLATE_LEVEL)
+    bool started = false;          // fastp_gpu_stream_run was called: the level is fixed
 
     int fail(int code, const std::string& m) {
         err = m;
@@ -725,6 +727,8 @@ int fastp_gpu_stream_create(const fastp_gpu_params* params, const fastp_gpu_stre
     if (cfg->chunk_bytes <= 0 && getenv("FASTP_GPU_STREAM_CHUNK_BYTES")) s->chunk = atoll(getenv("FASTP_GPU_STREAM_CHUNK_BYTES"));   // tests: many small trips
     s->chunk = std::max<int64_t>(4096, std::min<int64_t>(s->chunk, (int64_t)1 << 30)) / 256 * 256;
     if (s->cfg.io_threads <= 0) s->cfg.io_threads = env_int("FASTP_GPU_STREAM_IO_THREADS", 8);
+    s->deflate_level = env_int("FASTP_GPU_STREAM_DEFLATE_LEVEL", 0);   // how a binding that does not call the setter passes -z
+    if (s->deflate_level < 0 || s->deflate_level > 9) { g_stream_error = "FASTP_GPU_STREAM_DEFLATE_LEVEL outside 0..9"; return FASTP_GPU_E_INVALID; }
     for (int m = 0; m < s->nf; m++) {
         s->src_kind[m] = input_kind(m ? s->in2 : s->in1);
         s->st.input_kind[m] = s->src_kind[m];
@@ -1433,8 +1437,8 @@ int run_loop(Run* R) {
                     if (!s->cfg.want[q]) { lens[q] = 0; continue; }
                     if (s->cfg.compress[q] && lens[q] > 0) {
                         int64_t glen = 0;
-                        if (fastp_gpu_deflate_bgzf(s->ctx, d_out[q], lens[q], 0, s->d_gz[wj.oslot][q], s->gz_cap[q], &glen) != FASTP_GPU_OK)
-                            return s->fail_ctx(FASTP_GPU_E_HIP, "fastp_gpu_deflate_bgzf");
+                        if (fastp_gpu_deflate_bgzf_level(s->ctx, d_out[q], lens[q], 0, s->deflate_level, s->d_gz[wj.oslot][q], s->gz_cap[q], &glen) != FASTP_GPU_OK)
+                            return s->fail_ctx(FASTP_GPU_E_HIP, "fastp_gpu_deflate_bgzf_level");
                         lens[q] = glen;
                         src[q] = s->d_gz[wj.oslot][q];
                     }
@@ -1524,8 +1528,17 @@ static int gunzip_file_with(G* g, int fd, uint8_t* out, int64_t capacity, int64_
     return rc;
 }
 
+extern "C" int fastp_gpu_stream_set_deflate_level(fastp_gpu_stream* s, int level) {
+    if (!s) return FASTP_GPU_E_INVALID;
+    if (s->started) return s->fail(FASTP_GPU_E_INVALID, "the compression level is set before fastp_gpu_stream_run");
+    if (level < 0 || level > 9) return s->fail(FASTP_GPU_E_INVALID, "compression level outside 0..9");
+    s->deflate_level = level;
+    return FASTP_GPU_OK;
+}
+
 extern "C" int fastp_gpu_stream_run(fastp_gpu_stream* s) {
     if (!s || !s->ctx) return FASTP_GPU_E_INVALID;
+    s->started = true;
     const double t_start = now_s();
     fq::timeline("stream: run begin");
     S_HIP(s, hipSetDevice(s->cfg.device));

@@ -79,6 +79,7 @@ class FastqPipeline:
         self.stage_out = None      # [slot][stream]: pinned, sized in run() for the streams that are asked for
         self.outs = [None] * abi.N_OUTPUTS       # device text per stream
         self.gzbuf = [None] * abi.N_OUTPUTS      # device gzip members per compressed stream
+        self.gz_level = None                     # run(compression_level=...)
         self.max_blocks = (2 * self.chunk) // 8192 + 64     # BGZF members per chunk (bgzip: ~64 KiB of text each)
         self.check_crc = True
         self.stats = dict(units=0, chunks=0, bytes_in=0, bytes_out=0, t_parse=0.0, t_engine=0.0, t_format=0.0, t_h2d=0.0,
@@ -255,10 +256,14 @@ class FastqPipeline:
 
     def run(self, in1: str, in2: str | None, out1: str, out2: str | None, failed_out: str | None = None,
             merged_out: str | None = None, unpaired1: str | None = None, unpaired2: str | None = None,
-            umi: tuple | None = None) -> dict:
+            umi: tuple | None = None, compression_level: int | None = None) -> dict:
         """umi = (location "read1" | "read2" | "per_read", length[, prefix bytes[, delimiter bytes]]): the name edit that goes
-        with params.umi_len1/2 (UmiProcessor::addUmiToName)"""
+        with params.umi_len1/2 (UmiProcessor::addUmiToName).  compression_level: the reference's -z (1..9, 0 = the default)
+        for every ".gz" output; None is the default encoder through fastp_gpu_deflate_bgzf"""
         torch = self.torch
+        if compression_level is not None and not 0 <= int(compression_level) <= 9:
+            raise PipelineError("compression_level is 0 (the default) to 9")
+        self.gz_level = None if compression_level is None else int(compression_level)
         if self.paired != (in2 is not None) or self.paired != (out2 is not None):
             raise PipelineError("paired engine needs in2/out2, single-end engine must not get them")
         if self.params.merge and not merged_out:
@@ -459,7 +464,8 @@ class FastqPipeline:
         t0 = time.perf_counter()
         for q in range(abi.N_OUTPUTS):
             if self.out_cap[q] and self.gz_out[q]:
-                rc, lens[q] = self.eng.deflate_bgzf(self.outs[q].data_ptr(), lens[q], self.gzbuf[q].data_ptr(), self.gzbuf[q].numel())
+                rc, lens[q] = self.eng.deflate_bgzf(self.outs[q].data_ptr(), lens[q], self.gzbuf[q].data_ptr(), self.gzbuf[q].numel(),
+                                                          level=self.gz_level)
         st["t_deflate"] = st.get("t_deflate", 0.0) + time.perf_counter() - t0
         return lens
 

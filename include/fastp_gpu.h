@@ -527,6 +527,18 @@ int fastp_gpu_device_download(fastp_gpu_ctx* ctx, void* dst_host, const void* sr
  * FASTP_GPU_E_OVERFLOW is returned.  An upper bound for out_capacity: nbytes + 31 * (nbytes / 65280 + 1) + 28. */
 int fastp_gpu_deflate_bgzf(fastp_gpu_ctx* ctx, const uint8_t* text, int64_t nbytes, int write_eof, uint8_t* out,
                            int64_t out_capacity, int64_t* out_len);
+/* The same with the reference's --compression / -z (src/options.cpp:288, 1..9).  level 0 is the default and what
+ * fastp_gpu_deflate_bgzf calls.  Levels 1..4 are that one encoder (one candidate per position, greedy parse): the
+ * same bytes.  Levels 5..9 search harder for the same member format: a chain of earlier positions per hash bucket
+ * walked to a depth the level sets (5..7: 4, 8..9: 16); a longer candidate replaces a nearer one only when it gains
+ * more bytes than its distance code has extra bits (so a match of l bytes is looked for within about 2^(l+1) bytes, and
+ * distance 1 wins over a farther match that is not worth its distance), the nearest on ties; a match is dropped for a
+ * literal when the next position holds a longer one; and matches under 16 bytes are taken only where their length and
+ * distance codes cost less than the literals they replace (estimated from the block's byte counts).  Smaller
+ * output, more time (DESIGN.md 7 has both per level).  Any other level: FASTP_GPU_E_INVALID.  The capacity bound
+ * above holds at every level (the stored-block fallback). */
+int fastp_gpu_deflate_bgzf_level(fastp_gpu_ctx* ctx, const uint8_t* text, int64_t nbytes, int write_eof, int level, uint8_t* out,
+                                 int64_t out_capacity, int64_t* out_len);
 
 /* ---- the Evaluator pre-pass ON THE DEVICE ------------------------------
  * The loops of src/evaluator.cpp that scan a prefix of the input before the workers start, run on packed

@@ -100,6 +100,11 @@ typedef struct fastp_gpu_stream fastp_gpu_stream;
 int fastp_gpu_stream_create(const fastp_gpu_params* params, const fastp_gpu_stream_config* cfg, fastp_gpu_stream** out);
 /* the whole run: returns when every byte has been handed to its file descriptor / emit callback */
 int fastp_gpu_stream_run(fastp_gpu_stream* s);
+/* --compression / -z of the reference (src/options.cpp:288) for every compressed stream: the level of
+ * fastp_gpu_deflate_bgzf_level (0 = the default, 1..9).  To be called between create and run;
+ * FASTP_GPU_E_INVALID for a level outside 0..9 and once fastp_gpu_stream_run has been called.  A stream this was never
+ * called for takes the environment variable FASTP_GPU_STREAM_DEFLATE_LEVEL (read at create, 0..9), else the default. */
+int fastp_gpu_stream_set_deflate_level(fastp_gpu_stream* s, int level);
 /* the run's counter block in the layout of the LAST context (cycles = its max_len; the blocks of the contexts a
  * re-plan replaced are folded in).  fastp_gpu_stream_layout first, then counters with n = layout.total. */
 int fastp_gpu_stream_layout(const fastp_gpu_stream* s, fastp_gpu_counter_layout* out);

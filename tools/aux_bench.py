@@ -55,6 +55,14 @@ def defl():
     box["n"] = nb
 timed("deflate_bgzf(out1)", defl, lens[0])
 print(f"ratio {box['n'] / lens[0]:.4f}")
+# the same text per level of fastp_gpu_deflate_bgzf_level (1..4: the default stage; 5..7 and 8..9: the chain stage's two tiers)
+for level in (1, 5, 9):
+    def defl_level():
+        rc, nb = g.deflate_bgzf(mem.ptr(outs[0]), lens[0], mem.ptr(comp), comp.numel(), True, level=level)
+        box["level"] = nb
+    timed(f"deflate_bgzf_level(out1, {level})", defl_level, lens[0], reps=5)
+    print(f"ratio {box['level'] / lens[0]:.4f}")
+defl()   # (what is inflated below)
 import zlib
 txt = mem.download(outs[0], min(lens[0], 20 << 20))
 t0 = time.perf_counter(); z = zlib.compress(txt, 4); dt = time.perf_counter() - t0
