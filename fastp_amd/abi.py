@@ -193,7 +193,8 @@ class FormatOptions(C.Structure):
 
 
 N_OUTPUTS = 6  # FASTP_GPU_OUT1, OUT2, FAILED, MERGED, UNPAIRED1, UNPAIRED2
-OUT_OVERLAPPED = 6   # host glue only (FASTP_GPU_OVERLAPPED)
+N_ALL_OUTPUTS = 7  # ... and FASTP_GPU_OVERLAPPED (OUT_OVERLAPPED, --overlapped_out's stream): fastp_gpu_format_all_streams
+OUT_OVERLAPPED = 6   # FASTP_GPU_OVERLAPPED: the host glue's and fastp_gpu_format_all_streams' seventh stream
 OVOUT_HIT = 0x8000   # fastp_gpu_read_result.reserved of read 1 with overlapped_out
 
 

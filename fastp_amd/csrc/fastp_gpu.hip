@@ -214,7 +214,7 @@ extern "C" __global__ void __launch_bounds__(256) fq_eval_text_kernel(EvalCensus
 extern "C" __global__ void __launch_bounds__(256) fq_fmts_corr_kernel(FmtsArgs f) { fmts_corr_body(f); }
 extern "C" __global__ void __launch_bounds__(256) fq_fmts_len_kernel(FmtsArgs f) {
     extern __shared__ u32 fq_lds[];
-    fmts_len_body(f, fq_lds);
+    fmts_len_body<FMTS_STREAMS, 2>(f, fq_lds);
 }
 extern "C" __global__ void __launch_bounds__(1024) fq_fmts_scan_kernel(FmtsArgs f) {
     extern __shared__ u32 fq_lds[];
@@ -222,7 +222,17 @@ extern "C" __global__ void __launch_bounds__(1024) fq_fmts_scan_kernel(FmtsArgs 
 }
 extern "C" __global__ void __launch_bounds__(256) fq_fmts_write_kernel(FmtsArgs f) {
     extern __shared__ u32 fq_lds[];
-    fmts_write_body(f, fq_lds);
+    fmts_write_body<FMTS_STREAMS, 2>(f, fq_lds);
+}
+// the same with --overlapped_out's stream: seven streams, up to three emissions per unit (fastp_gpu_format_all_streams;
+// fq_fmts_corr_kernel and fq_fmts_scan_kernel serve both, the latter with one workgroup per stream)
+extern "C" __global__ void __launch_bounds__(256) fq_fmts7_len_kernel(FmtsArgs f) {
+    extern __shared__ u32 fq_lds[];
+    fmts_len_body<FMTS_ALL_STREAMS, 3>(f, fq_lds);
+}
+extern "C" __global__ void __launch_bounds__(256) fq_fmts7_write_kernel(FmtsArgs f) {
+    extern __shared__ u32 fq_lds[];
+    fmts_write_body<FMTS_ALL_STREAMS, 3>(f, fq_lds);
 }
 extern "C" __global__ void __launch_bounds__(64 * TEXT_WAVES) fq_text_kernel(TextArgs e) {
     extern __shared__ __attribute__((aligned(16))) u32 fq_lds[];
@@ -2289,21 +2299,23 @@ extern "C" int fastp_gpu_format_fastq(fastp_gpu_ctx* ctx, int32_t n, const fastp
     return FASTP_GPU_OK;
 }
 
-extern "C" int fastp_gpu_format_streams(fastp_gpu_ctx* ctx, int32_t n, const fastp_gpu_format_io* m1, const fastp_gpu_format_io* m2,
-                                        const fastp_gpu_pair_result* pair, const fastp_gpu_correction* corrections,
-                                        const int32_t* n_corrections, const fastp_gpu_format_options* opts,
-                                        uint8_t* const out[FASTP_GPU_N_OUTPUTS], const int64_t out_capacity[FASTP_GPU_N_OUTPUTS],
-                                        int64_t out_len[FASTP_GPU_N_OUTPUTS]) {
+// fastp_gpu_format_streams (ns = 6: the (6, 2) kernels) and fastp_gpu_format_all_streams (ns = 7: the (7, 3) kernels); out,
+// out_capacity and out_len hold ns entries
+static int format_streams_impl(fastp_gpu_ctx* ctx, const int ns, int32_t n, const fastp_gpu_format_io* m1, const fastp_gpu_format_io* m2,
+                               const fastp_gpu_pair_result* pair, const fastp_gpu_correction* corrections, const int32_t* n_corrections,
+                               const fastp_gpu_format_options* opts, uint8_t* const* out, const int64_t* out_capacity, int64_t* out_len) {
     if (!ctx || !m1 || !out || !out_capacity || !out_len || n < 0) return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
-    for (int q = 0; q < FASTP_GPU_N_OUTPUTS; q++) out_len[q] = 0;
+    for (int q = 0; q < ns; q++) out_len[q] = 0;
     const bool paired = ctx->dp.paired != 0;
     if (paired != (m2 != nullptr)) return fail(ctx, FASTP_GPU_E_INVALID, "mate 2 must be given exactly for a paired engine");
     if (paired && !pair) return fail(ctx, FASTP_GPU_E_INVALID, "a paired engine needs the pair records");
-    if (ctx->dp.overlapped_out && !ctx->host_overlapped)
+    const bool all = ns == FMTS_ALL_STREAMS;
+    if (!all && ctx->dp.overlapped_out && !ctx->host_overlapped)
         return fail(ctx, FASTP_GPU_E_UNSUPPORTED, "--overlapped_out's stream is written by the host (fastp_gpu_host.h, or fastp_gpu_host_writes_overlapped)");
     FmtsArgs f;
     memset(&f, 0, sizeof(f));
     f.n = n;
+    f.overlapped_out = (all && paired && ctx->dp.overlapped_out) ? 1 : 0;
     f.paired = paired ? 1 : 0;
     f.dedup = ctx->dp.dedup;
     f.merge = paired ? ctx->dp.merge : 0;
@@ -2333,8 +2345,8 @@ extern "C" int fastp_gpu_format_streams(fastp_gpu_ctx* ctx, int32_t n, const fas
     }
     if (n == 0) return FASTP_GPU_OK;
     // the streams this configuration can write to need a buffer
-    bool need[FMTS_STREAMS] = {true, paired, f.want_failed != 0, f.merge != 0, paired && f.want_u1, paired && f.want_u2};
-    for (int q = 0; q < FMTS_STREAMS; q++) {
+    const bool need[FMTS_ALL_STREAMS] = {true, paired, f.want_failed != 0, f.merge != 0, paired && f.want_u1, paired && f.want_u2, f.overlapped_out != 0};
+    for (int q = 0; q < ns; q++) {
         if (out_capacity[q] < 0 || (need[q] && !out[q])) return fail(ctx, FASTP_GPU_E_INVALID, "null output buffer for a stream the options ask for");
         f.out[q] = out[q];
         f.out_cap[q] = out[q] ? (u64)out_capacity[q] : 0;
@@ -2342,12 +2354,12 @@ extern "C" int fastp_gpu_format_streams(fastp_gpu_ctx* ctx, int32_t n, const fas
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     f.nblocks = (n + FMT_BLOCK - 1) / FMT_BLOCK;
-    const size_t words = (size_t)2 * FMTS_STREAMS * f.nblocks + FMTS_STREAMS;
+    const size_t words = (size_t)2 * ns * f.nblocks + ns;
     int rc = ensure(ctx, (void**)&ctx->d_fmt, &ctx->fmt_cap, words * 8);
     if (rc) return rc;
     f.blocksum = ctx->d_fmt;
-    f.blockbase = f.blocksum + (size_t)FMTS_STREAMS * f.nblocks;
-    f.totals = f.blockbase + (size_t)FMTS_STREAMS * f.nblocks;
+    f.blockbase = f.blocksum + (size_t)ns * f.nblocks;
+    f.totals = f.blockbase + (size_t)ns * f.nblocks;
     const fastp_gpu_format_io* ins[2] = {m1, m2};
     for (int m = 0; m < (paired ? 2 : 1); m++) {
         if (!ins[m]->text || !ins[m]->line_off || !ins[m]->line_len || !ins[m]->res) return fail(ctx, FASTP_GPU_E_INVALID, "null input");
@@ -2373,22 +2385,41 @@ extern "C" int fastp_gpu_format_streams(fastp_gpu_ctx* ctx, int32_t n, const fas
             HIP_TRY(ctx, hipGetLastError());
         }
     }
-    hipLaunchKernelGGL(fq_fmts_len_kernel, dim3(f.nblocks), dim3(FMT_BLOCK), FMTS_STREAMS * 4, st, f);
+    // LDS: a block sum per stream; then wave sums per stream + a u64 offset per (unit, emission slot)
+    if (all) hipLaunchKernelGGL(fq_fmts7_len_kernel, dim3(f.nblocks), dim3(FMT_BLOCK), FMTS_ALL_STREAMS * 4, st, f);
+    else hipLaunchKernelGGL(fq_fmts_len_kernel, dim3(f.nblocks), dim3(FMT_BLOCK), FMTS_STREAMS * 4, st, f);
     HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(fq_fmts_scan_kernel, dim3(FMTS_STREAMS), dim3(1024), 1024 * 8, st, f);
+    hipLaunchKernelGGL(fq_fmts_scan_kernel, dim3(ns), dim3(1024), 1024 * 8, st, f);
     HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(fq_fmts_write_kernel, dim3(f.nblocks), dim3(FMT_BLOCK), FMTS_STREAMS * 16 * 4 + FMT_BLOCK * 16, st, f);
+    if (all) hipLaunchKernelGGL(fq_fmts7_write_kernel, dim3(f.nblocks), dim3(FMT_BLOCK), FMTS_ALL_STREAMS * 16 * 4 + FMT_BLOCK * 3 * 8, st, f);
+    else hipLaunchKernelGGL(fq_fmts_write_kernel, dim3(f.nblocks), dim3(FMT_BLOCK), FMTS_STREAMS * 16 * 4 + FMT_BLOCK * 16, st, f);
     HIP_TRY(ctx, hipGetLastError());
-    u64 totals[FMTS_STREAMS];
-    HIP_TRY(ctx, hipMemcpyAsync(totals, f.totals, sizeof(totals), hipMemcpyDeviceToHost, st));
+    u64 totals[FMTS_ALL_STREAMS];
+    HIP_TRY(ctx, hipMemcpyAsync(totals, f.totals, (size_t)ns * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     bool overflow = false;
-    for (int q = 0; q < FMTS_STREAMS; q++) {
+    for (int q = 0; q < ns; q++) {
         out_len[q] = (int64_t)totals[q];
         if (totals[q] > f.out_cap[q]) overflow = true;
     }
     if (overflow) return fail(ctx, FASTP_GPU_E_OVERFLOW, "output buffer too small (see out_len for the needed sizes)");
     return FASTP_GPU_OK;
+}
+
+extern "C" int fastp_gpu_format_streams(fastp_gpu_ctx* ctx, int32_t n, const fastp_gpu_format_io* m1, const fastp_gpu_format_io* m2,
+                                        const fastp_gpu_pair_result* pair, const fastp_gpu_correction* corrections,
+                                        const int32_t* n_corrections, const fastp_gpu_format_options* opts,
+                                        uint8_t* const out[FASTP_GPU_N_OUTPUTS], const int64_t out_capacity[FASTP_GPU_N_OUTPUTS],
+                                        int64_t out_len[FASTP_GPU_N_OUTPUTS]) {
+    return format_streams_impl(ctx, FMTS_STREAMS, n, m1, m2, pair, corrections, n_corrections, opts, out, out_capacity, out_len);
+}
+
+extern "C" int fastp_gpu_format_all_streams(fastp_gpu_ctx* ctx, int32_t n, const fastp_gpu_format_io* m1, const fastp_gpu_format_io* m2,
+                                            const fastp_gpu_pair_result* pair, const fastp_gpu_correction* corrections,
+                                            const int32_t* n_corrections, const fastp_gpu_format_options* opts,
+                                            uint8_t* const out[FASTP_GPU_N_HOST_OUTPUTS], const int64_t out_capacity[FASTP_GPU_N_HOST_OUTPUTS],
+                                            int64_t out_len[FASTP_GPU_N_HOST_OUTPUTS]) {
+    return format_streams_impl(ctx, FMTS_ALL_STREAMS, n, m1, m2, pair, corrections, n_corrections, opts, out, out_capacity, out_len);
 }
 
 // ---- Evaluator pre-pass (fq_eval.h) ---------------------------------------------------------------------

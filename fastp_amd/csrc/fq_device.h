@@ -3954,9 +3954,12 @@ FQ_DEV void fmt_fix_body(const FmtArgs& f) {
 // peprocessor.cpp:518-621 / seprocessor.cpp:280-290 from the result records, Read::appendToString /
 // appendToStringWithTag (read.cpp:119-154), OverlapAnalysis::merge's string assembly
 // (overlapanalysis.cpp:148-179) and UmiProcessor::addUmiToName (umiprocessor.cpp:62-81).
-// A unit (pair / single read) makes at most two records ("emissions"); an emission is
-//   stream | source << 3 | tag kind << 5 | filter code << 8      source: 0 read 1, 1 read 2, 2 the merged read
+// A unit (pair / single read) makes at most two records ("emissions") for the six streams of the worker loop, and a
+// third for --overlapped_out's stream (peprocessor.cpp:488-495, written before anything is routed); an emission is
+//   stream | source << 3 | tag kind << 5 | filter code << 8      source: 0 read 1, 1 read 2, 2 the merged read,
+//                                                                          3 read 1 behind the overlapped region
 //                                                                  tag kind: 0 none, 1 FAILED_TYPES[code], 2 "paired_read_is_failing"
+// The bodies take (NS streams, SLOTS emissions per unit): (6, 2) is fastp_gpu_format_streams, (7, 3) fastp_gpu_format_all_streams.
 //   fmts_corr  : BaseCorrector's edits patched into the parsed text (the reference edits reads in place)
 //   fmts_len   : bytes each block's units add to each stream
 //   fmts_scan  : running offsets per stream
@@ -4020,6 +4023,21 @@ FQ_DEV void fmts_route(const FmtsArgs& f, int g, u32 e[2]) {
     }
 }
 
+// the emissions of unit g into e[SLOTS]: the worker loop's two, then --overlapped_out's (the engine leaves
+// FASTP_GPU_OVOUT_HIT | first position in read 1's `reserved`, the count in read 2's, on every plan)
+template <int SLOTS>
+FQ_DEV void fmts_route_all(const FmtsArgs& f, int g, u32* e) {
+    fmts_route(f, g, e);
+    if (SLOTS > 2) {
+        const bool hit = f.overlapped_out && f.paired && ((f.m[0].res[(size_t)g * 3 + 2] >> 16) & FMTS_OVOUT_HIT);
+        e[2] = hit ? fmts_em(6, 3, 0, 0) : FMTS_NONE;
+    }
+}
+template <int SLOTS>
+FQ_DEV bool fmts_any(const u32* e) {
+    return SLOTS > 2 ? (e[0] != FMTS_NONE || e[2] != FMTS_NONE) : e[0] != FMTS_NONE;
+}
+
 // FAILED_TYPES (common.h:57-66) / "paired_read_is_failing": character i of the tag, its length
 FQ_DEV const char* fmts_tag_text(int kind, u32 code) {
     if (kind == 2) return "paired_read_is_failing";
@@ -4041,6 +4059,7 @@ FQ_DEV u32 fmts_strlen(const char* t) {
     while (t[n]) n++;
     return n;
 }
+FQ_DEV u32 fmts_umin(u32 a, u32 b) { return a < b ? a : b; }
 FQ_DEV u32 fmts_digits(u32 v) { return v >= 1000u ? 4u : v >= 100u ? 3u : v >= 10u ? 2u : 1u; }
 
 // UmiProcessor::process + addUmiToName: length of the text inserted into the names of this unit (0 = no edit),
@@ -4065,9 +4084,11 @@ struct FmtsRec {
     int mt;            // the mate whose name / strand lines are used
     u32 name_len, strand_len, seq_len, tag_len, umi_len, mtag_len;   // mtag: " merged_L1_L2"
     u32 m1, m2, ol;    // merged parts
+    u32 start;         // source 3: first printed position of the sequence / quality line
     bool strand_tagged;
     u32 bytes;
 };
+template <int SLOTS>
 FQ_DEV void fmts_rec(const FmtsArgs& f, int g, u32 em, u32 umi_len, FmtsRec& r) {
     const int src = (int)((em >> 3) & 3u);
     r.mt = src == 1 ? 1 : 0;
@@ -4079,8 +4100,15 @@ FQ_DEV void fmts_rec(const FmtsArgs& f, int g, u32 em, u32 umi_len, FmtsRec& r) 
     r.tag_len = tagkind ? fmts_strlen(fmts_tag_text(tagkind, (em >> 8) & 0xFFu)) : 0u;
     r.mtag_len = 0;
     r.m1 = r.m2 = r.ol = 0;
+    r.start = 0;
     r.strand_tagged = false;
-    if (src == 2) {
+    if (SLOTS > 2 && src == 3) {
+        // read 1's [pos, pos + cnt) of the parsed text; never outside the sequence (or quality) line whatever the records say
+        const u32 ll = fmts_umin(M.line_len[4 * (size_t)g + 1], M.line_len[4 * (size_t)g + 3]);
+        const u32 pos = (M.res[(size_t)g * 3] & 0xFFFFu) + ((M.res[(size_t)g * 3 + 2] >> 16) & 0x7FFFu);
+        r.start = fmts_umin(pos, ll);
+        r.seq_len = fmts_umin(f.m[1].res[(size_t)g * 3 + 2] >> 16, ll - r.start);
+    } else if (src == 2) {
         // bases of each mate in the merged read, from the pair record (see ovr_count_body)
         const u32 pw = f.pair[2 * (size_t)g];
         const int poff = (int)(int16_t)(pw & 0xFFFFu);
@@ -4114,34 +4142,35 @@ FQ_DEV void fmts_corr_body(const FmtsArgs& f) {
 }
 
 // per-unit byte counts per stream -> LDS block sums -> blocksum
+template <int NS, int SLOTS>
 FQ_DEV void fmts_len_body(const FmtsArgs& f, u32* lds) {
-    if (thread_id() < FMTS_STREAMS) lds[thread_id()] = 0;
+    if (thread_id() < NS) lds[thread_id()] = 0;
     block_sync();
     const int g = block_id() * block_threads() + thread_id();
-    u32 bytes[FMTS_STREAMS] = {0, 0, 0, 0, 0, 0};
+    u32 bytes[NS] = {};
     if (g < f.n) {
-        u32 e[2];
-        fmts_route(f, g, e);
+        u32 e[SLOTS];
+        fmts_route_all<SLOTS>(f, g, e);
         u32 u1, u2;
-        const u32 ul = (e[0] != FMTS_NONE) ? fmts_umi(f, g, u1, u2) : 0u;
-        for (int k = 0; k < 2; k++) {
+        const u32 ul = fmts_any<SLOTS>(e) ? fmts_umi(f, g, u1, u2) : 0u;
+        for (int k = 0; k < SLOTS; k++) {
             if (e[k] == FMTS_NONE) continue;
             FmtsRec r;
-            fmts_rec(f, g, e[k], ul, r);
+            fmts_rec<SLOTS>(f, g, e[k], ul, r);
             const int st = (int)(e[k] & 7u);
 #pragma unroll
-            for (int q = 0; q < FMTS_STREAMS; q++) bytes[q] += q == st ? r.bytes : 0u;
+            for (int q = 0; q < NS; q++) bytes[q] += q == st ? r.bytes : 0u;
         }
     }
 #pragma unroll
-    for (int q = 0; q < FMTS_STREAMS; q++) {
+    for (int q = 0; q < NS; q++) {
         u32 b = bytes[q];
 #pragma unroll
         for (int sh = 1; sh < 64; sh <<= 1) b += shfl_xor(b, sh);
         if (lane_id() == 0 && b) lds_add_u32(&lds[q], b);
     }
     block_sync();
-    if (thread_id() < FMTS_STREAMS) f.blocksum[(size_t)thread_id() * f.nblocks + block_id()] = lds[thread_id()];
+    if (thread_id() < NS) f.blocksum[(size_t)thread_id() * f.nblocks + block_id()] = lds[thread_id()];
 }
 
 FQ_DEV void fmts_scan_body(const FmtsArgs& f, u64* lds) {
@@ -4207,32 +4236,37 @@ FQ_DEV u32 fmts_put_mtag(u8* dst, u32 m1, u32 m2, int gl) {
     return 8u + d1 + 1u + d2;
 }
 
+template <int NS, int SLOTS>
 FQ_DEV void fmts_write_body(const FmtsArgs& f, u32* lds) {
-    // lds: [FMTS_STREAMS][16 waves] wave sums, then per unit [2] u64 offsets of its emissions (block_threads * 2 * 2 dwords)
+    // lds: [NS][16 waves] wave sums, then per unit [SLOTS] u64 offsets of its emissions (block_threads * SLOTS * 2 dwords)
     const int tid = thread_id(), nw = block_threads() >> 6, wave = wave_id();
     const int g0 = block_id() * block_threads();
     const int g = g0 + tid;
-    u32 e[2] = {FMTS_NONE, FMTS_NONE};
-    u32 sz[2] = {0, 0};
+    u32 e[SLOTS], sz[SLOTS];
+#pragma unroll
+    for (int k = 0; k < SLOTS; k++) { e[k] = FMTS_NONE; sz[k] = 0; }
     u32 ul = 0, u1 = 0, u2 = 0;
     if (g < f.n) {
-        fmts_route(f, g, e);
-        if (e[0] != FMTS_NONE) ul = fmts_umi(f, g, u1, u2);
-        for (int k = 0; k < 2; k++)
+        fmts_route_all<SLOTS>(f, g, e);
+        if (fmts_any<SLOTS>(e)) ul = fmts_umi(f, g, u1, u2);
+#pragma unroll
+        for (int k = 0; k < SLOTS; k++)
             if (e[k] != FMTS_NONE) {
                 FmtsRec r;
-                fmts_rec(f, g, e[k], ul, r);
+                fmts_rec<SLOTS>(f, g, e[k], ul, r);
                 sz[k] = r.bytes;
             }
     }
-    u64* eoff = (u64*)(lds + FMTS_STREAMS * 16);
-    u64 off[2] = {~0ull, ~0ull};
-    u32 excl[FMTS_STREAMS], mine0[FMTS_STREAMS];
+    u64* eoff = (u64*)(lds + NS * 16);
+    u64 off[SLOTS];
 #pragma unroll
-    for (int q = 0; q < FMTS_STREAMS; q++) {
-        const u32 b0 = (e[0] != FMTS_NONE && (int)(e[0] & 7u) == q) ? sz[0] : 0u;
-        const u32 b1 = (e[1] != FMTS_NONE && (int)(e[1] & 7u) == q) ? sz[1] : 0u;
-        const u32 b = b0 + b1;
+    for (int k = 0; k < SLOTS; k++) off[k] = ~0ull;
+    u32 excl[NS];
+#pragma unroll
+    for (int q = 0; q < NS; q++) {
+        u32 b = 0;
+#pragma unroll
+        for (int k = 0; k < SLOTS; k++) b += (e[k] != FMTS_NONE && (int)(e[k] & 7u) == q) ? sz[k] : 0u;
         u32 incl = b;
 #pragma unroll
         for (int sh = 1; sh < 64; sh <<= 1) {
@@ -4241,35 +4275,41 @@ FQ_DEV void fmts_write_body(const FmtsArgs& f, u32* lds) {
         }
         if (lane_id() == 63) lds[q * 16 + wave] = incl;
         excl[q] = incl - b;
-        mine0[q] = b0;
     }
     block_sync();
 #pragma unroll
-    for (int q = 0; q < FMTS_STREAMS; q++) {
+    for (int q = 0; q < NS; q++) {
         u64 base = f.blockbase[(size_t)q * f.nblocks + block_id()] + excl[q];
         for (int w = 0; w < nw; w++)
             if (w < wave) base += lds[q * 16 + w];
-        if (e[0] != FMTS_NONE && (int)(e[0] & 7u) == q) off[0] = base;
-        if (e[1] != FMTS_NONE && (int)(e[1] & 7u) == q) off[1] = base + mine0[q];
+        // a unit's emissions into one stream follow each other in slot order
+#pragma unroll
+        for (int k = 0; k < SLOTS; k++)
+            if (e[k] != FMTS_NONE && (int)(e[k] & 7u) == q) {
+                off[k] = base;
+                base += sz[k];
+            }
     }
-    eoff[2 * tid] = off[0];
-    eoff[2 * tid + 1] = off[1];
+#pragma unroll
+    for (int k = 0; k < SLOTS; k++) eoff[SLOTS * tid + k] = off[k];
     block_sync();
     // a 16-lane group per (unit, emission slot)
     const int gl = lane_id() & 15, ngroups = block_threads() >> 4;
-    for (int t = tid >> 4; t < block_threads() * 2; t += ngroups) {
-        const int u = t >> 1, k = t & 1;
+    for (int t = tid >> 4; t < block_threads() * SLOTS; t += ngroups) {
+        const int u = t / SLOTS, k = t % SLOTS;
         const int gu = g0 + u;
         if (gu >= f.n) break;
-        const u64 o64 = eoff[2 * u + k];
+        const u64 o64 = eoff[SLOTS * u + k];
         if (o64 == ~0ull) continue;
-        u32 ee[2];
-        fmts_route(f, gu, ee);
-        const u32 em = ee[k];
+        u32 ee[SLOTS];
+        fmts_route_all<SLOTS>(f, gu, ee);
+        u32 em = ee[0];
+#pragma unroll
+        for (int j = 1; j < SLOTS; j++) em = k == j ? ee[j] : em;   // (no indexed private array)
         u32 v1, v2;
         const u32 uml = fmts_umi(f, gu, v1, v2);
         FmtsRec r;
-        fmts_rec(f, gu, em, uml, r);
+        fmts_rec<SLOTS>(f, gu, em, uml, r);
         const int st = (int)(em & 7u), src = (int)((em >> 3) & 3u), tagkind = (int)((em >> 5) & 7u);
         if (!f.out[st] || o64 + r.bytes > f.out_cap[st]) continue;  // the host sees the needed size in totals
         const FmtsMate& M = f.m[r.mt];
@@ -4311,7 +4351,7 @@ FQ_DEV void fmts_write_body(const FmtsArgs& f, u32* lds) {
         if (gl == 0) o[0] = 10;
         o += 1;
         // ---- sequence, strand, quality ----
-        const u32 front = M.res[(size_t)gu * 3] & 0xFFFFu;
+        const u32 front = (SLOTS > 2 && src == 3) ? r.start : (M.res[(size_t)gu * 3] & 0xFFFFu);
         const u8* seq = M.text + M.line_off[4 * (size_t)gu + 1] + front;
         const u8* qual = M.text + M.line_off[4 * (size_t)gu + 3] + front;
         const u8 *seq2 = nullptr, *qual2 = nullptr;

@@ -162,9 +162,9 @@ struct ReadDone {
 enum { SRC_PLAIN = 0, SRC_GZIP = 1, SRC_BGZF = 2 };
 struct WriteJob {
     int oslot = -1;                // -1: stop; 3: only the host-built stream below (a trip whose device streams are all unwanted)
-    int64_t len[FASTP_GPU_N_OUTPUTS] = {0, 0, 0, 0, 0, 0};
+    int64_t len[FASTP_GPU_N_HOST_OUTPUTS] = {0, 0, 0, 0, 0, 0, 0};   // ([FASTP_GPU_OVERLAPPED]: only when the device formats that stream)
     bool copy_pending = false;     // the device-to-host copy into pin_out[oslot] is in flight: wait for ev_out[oslot] first
-    bool has_ov = false;           // --overlapped_out's records of this chunk (may be empty: the writer takes one string per chunk)
+    bool has_ov = false;           // --overlapped_out's records of this chunk, assembled on the host (may be empty: the writer takes one string per chunk)
     std::string ov;
 };
 // the adapter strings of one chunk, in input order: entries [kind u8][len1 u16][len2 u16][bytes1][bytes2]
@@ -223,12 +223,17 @@ struct fastp_gpu_stream {
     // the output streams' text (and its gzip members) on the device, one set per page-locked output slot: the copy of chunk k
     // to the host runs on its own stream under the parser / worker loop / formatter of chunk k + 1 (round 5; the caller's
     // thread used to wait for it - 2 of the 6.5 s of a 100 M-pair run, profiles/r04_dropin_100M_reader_ab.txt)
-    uint8_t* d_out[2][FASTP_GPU_N_OUTPUTS] = {};
-    uint8_t* d_gz[2][FASTP_GPU_N_OUTPUTS] = {};
+    // (seven of each: --overlapped_out's stream, once the device formats it - ov_device - is a stream like the other six)
+    uint8_t* d_out[2][FASTP_GPU_N_HOST_OUTPUTS] = {};
+    uint8_t* d_gz[2][FASTP_GPU_N_HOST_OUTPUTS] = {};
     hipStream_t cp_out = nullptr;
     hipEvent_t ev_out[2] = {nullptr, nullptr};   // the copy into pin_out[slot] has landed (the writer thread waits for it)
-    int64_t out_cap[FASTP_GPU_N_OUTPUTS] = {}, gz_cap[FASTP_GPU_N_OUTPUTS] = {};
-    uint8_t* pin_out[2][FASTP_GPU_N_OUTPUTS] = {};
+    int64_t out_cap[FASTP_GPU_N_HOST_OUTPUTS] = {}, gz_cap[FASTP_GPU_N_HOST_OUTPUTS] = {};
+    uint8_t* pin_out[2][FASTP_GPU_N_HOST_OUTPUTS] = {};
+    // cfg.want / compress / out_fd / out_offset with the seventh stream's entries behind them (fastp_gpu_stream_set_overlapped_output)
+    int32_t want[FASTP_GPU_N_HOST_OUTPUTS] = {}, compress[FASTP_GPU_N_HOST_OUTPUTS] = {}, out_fd[FASTP_GPU_N_HOST_OUTPUTS] = {};
+    int64_t out_offset[FASTP_GPU_N_HOST_OUTPUTS] = {};
+    bool ov_device = false;        // --overlapped_out's stream is formatted on the device (fastp_gpu_format_all_streams)
     // host copies for the adapter replay
     fastp_gpu_read_result* h_res[2] = {nullptr, nullptr};
     uint32_t* h_loff[2] = {nullptr, nullptr};
@@ -258,6 +263,16 @@ namespace {
         if (e_ != hipSuccess) return (s)->fail(FASTP_GPU_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+void free_output(fastp_gpu_stream* s, int q) {
+    if (s->d_out[1][q] == s->d_out[0][q]) s->d_out[1][q] = nullptr;   // (an unwanted stream's two sets are one buffer)
+    for (int sl = 0; sl < 2; sl++) {
+        if (s->d_out[sl][q]) (void)hipFree(s->d_out[sl][q]);
+        if (s->d_gz[sl][q]) (void)hipFree(s->d_gz[sl][q]);
+        if (s->pin_out[sl][q]) (void)hipHostFree(s->pin_out[sl][q]);
+        s->d_out[sl][q] = s->d_gz[sl][q] = s->pin_out[sl][q] = nullptr;
+    }
+}
+
 void free_buffers(fastp_gpu_stream* s) {
     auto dfree = [](void* p) { if (p) (void)hipFree(p); };
     auto hfree = [](void* p) { if (p) (void)hipHostFree(p); };
@@ -284,14 +299,7 @@ void free_buffers(fastp_gpu_stream* s) {
     s->d_pair = nullptr; s->d_corr = nullptr; s->d_ev = nullptr; s->d_nc = s->d_nev = nullptr; s->d_zero = nullptr;
     hfree(s->h_corr); hfree(s->h_ev); hfree(s->h_counts);
     s->h_corr = nullptr; s->h_ev = nullptr; s->h_counts = nullptr;
-    for (int q = 0; q < FASTP_GPU_N_OUTPUTS; q++) {
-        if (s->d_out[1][q] == s->d_out[0][q]) s->d_out[1][q] = nullptr;   // (an unwanted stream's two sets are one buffer)
-        for (int sl = 0; sl < 2; sl++) {
-            dfree(s->d_out[sl][q]); dfree(s->d_gz[sl][q]);
-            s->d_out[sl][q] = s->d_gz[sl][q] = nullptr;
-        }
-        for (int sl = 0; sl < 2; sl++) { hfree(s->pin_out[sl][q]); s->pin_out[sl][q] = nullptr; }
-    }
+    for (int q = 0; q < FASTP_GPU_N_HOST_OUTPUTS; q++) free_output(s, q);
     for (int sl = 0; sl < 2; sl++)
         if (s->ev_out[sl]) { (void)hipEventDestroy(s->ev_out[sl]); s->ev_out[sl] = nullptr; }
     if (s->cp_out) { (void)hipStreamDestroy(s->cp_out); s->cp_out = nullptr; }
@@ -315,6 +323,44 @@ int alloc_rows(fastp_gpu_stream* s) {
         s->il_seq = s->il_qual = nullptr;
         S_HIP(s, hipMalloc((void**)&s->il_seq, 2 * (size_t)s->max_records * ss));
         S_HIP(s, hipMalloc((void**)&s->il_qual, 2 * (size_t)s->max_records * qs));
+    }
+    return FASTP_GPU_OK;
+}
+
+// the output streams' device and page-locked buffers; called again when the seventh stream moves to the device after
+// create (what is there stays)
+int alloc_outputs(fastp_gpu_stream* s) {
+    const int nf = s->nf;
+    // what a record can grow by over its input text: the UMI tag on the name (delimiter + prefix + '_' + the UMI of one or
+    // both mates joined by '_', UmiProcessor::addUmiToName), the failed / merged tags on the name and the strand line
+    int64_t grow = 0;
+    if (s->cfg.format.umi_loc != FASTP_GPU_UMI_NONE)
+        grow = (int64_t)s->umi_delim.size() + (s->umi_prefix.empty() ? 0 : (int64_t)s->umi_prefix.size() + 1) + 2 * (int64_t)s->cfg.format.umi_len + 1;
+    const int64_t both = nf * s->text_cap + (int64_t)s->max_records * (96 + 2 * grow);   // every record of both mates + tags
+    const int64_t one = s->text_cap + (int64_t)s->max_records * grow + 64;              // out1 / out2: records only shrink, but for the UMI tag
+    // (--overlapped_out's: parts of read 1's records with the UMI tag, fastp_gpu_format_all_streams' bound)
+    const int64_t caps[FASTP_GPU_N_HOST_OUTPUTS] = {one, one, both, both, both, both, one};
+    s->any_out = false;
+    for (int q = 0; q < FASTP_GPU_N_HOST_OUTPUTS; q++) s->any_out = s->any_out || s->want[q];
+    // the formatter wants a buffer for every stream the options can route to
+    const bool need[FASTP_GPU_N_HOST_OUTPUTS] = {true, s->paired, s->cfg.format.want_failed != 0, s->paired && s->p.merge,
+                                                 s->paired && s->cfg.format.want_unpaired1, s->paired && s->cfg.format.want_unpaired2, s->ov_device};
+    for (int q = 0; q < FASTP_GPU_N_HOST_OUTPUTS; q++) {
+        if (!s->any_out || !(need[q] || s->want[q]) || s->d_out[0][q]) continue;
+        s->out_cap[q] = caps[q];
+        // (a stream nobody asked for is written by the formatter and never copied: its two sets are one buffer)
+        for (int sl = 0; sl < 2; sl++) {
+            if (sl == 1 && !s->want[q]) { s->d_out[1][q] = s->d_out[0][q]; continue; }
+            S_HIP(s, hipMalloc((void**)&s->d_out[sl][q], (size_t)caps[q]));
+        }
+        int64_t host_bytes = caps[q];
+        if (s->want[q] && s->compress[q]) {
+            s->gz_cap[q] = caps[q] + 31 * (caps[q] / 65280 + 1) + 64;
+            for (int sl = 0; sl < 2; sl++) S_HIP(s, hipMalloc((void**)&s->d_gz[sl][q], (size_t)s->gz_cap[q]));
+            host_bytes = s->gz_cap[q];
+        }
+        if (s->want[q])
+            for (int sl = 0; sl < 2; sl++) S_HIP(s, hipHostMalloc((void**)&s->pin_out[sl][q], (size_t)host_bytes));
     }
     return FASTP_GPU_OK;
 }
@@ -381,36 +427,8 @@ int alloc_buffers(fastp_gpu_stream* s) {
         s->ev_cap = (int32_t)std::min<int64_t>((int64_t)s->max_records * 2 * std::min(s->p.n_adapter_fasta, 8) + 16, (int64_t)1 << 28);
         S_HIP(s, hipMalloc((void**)&s->d_ev, (size_t)s->ev_cap * sizeof(fastp_gpu_adapter_event)));
     }
-    // what a record can grow by over its input text: the UMI tag on the name (delimiter + prefix + '_' + the UMI of one or
-    // both mates joined by '_', UmiProcessor::addUmiToName), the failed / merged tags on the name and the strand line
-    int64_t grow = 0;
-    if (s->cfg.format.umi_loc != FASTP_GPU_UMI_NONE)
-        grow = (int64_t)s->umi_delim.size() + (s->umi_prefix.empty() ? 0 : (int64_t)s->umi_prefix.size() + 1) + 2 * (int64_t)s->cfg.format.umi_len + 1;
-    const int64_t both = nf * s->text_cap + (int64_t)s->max_records * (96 + 2 * grow);   // every record of both mates + tags
-    const int64_t one = s->text_cap + (int64_t)s->max_records * grow + 64;              // out1 / out2: records only shrink, but for the UMI tag
-    const int64_t caps[FASTP_GPU_N_OUTPUTS] = {one, one, both, both, both, both};
-    s->any_out = false;
-    for (int q = 0; q < FASTP_GPU_N_OUTPUTS; q++) s->any_out = s->any_out || s->cfg.want[q];
-    // fastp_gpu_format_streams wants a buffer for every stream the options can route to
-    const bool need[FASTP_GPU_N_OUTPUTS] = {true, s->paired, s->cfg.format.want_failed != 0, s->paired && s->p.merge,
-                                            s->paired && s->cfg.format.want_unpaired1, s->paired && s->cfg.format.want_unpaired2};
-    for (int q = 0; q < FASTP_GPU_N_OUTPUTS; q++) {
-        if (!s->any_out || !(need[q] || s->cfg.want[q])) continue;
-        s->out_cap[q] = caps[q];
-        // (a stream nobody asked for is written by the formatter and never copied: its two sets are one buffer)
-        for (int sl = 0; sl < 2; sl++) {
-            if (sl == 1 && !s->cfg.want[q]) { s->d_out[1][q] = s->d_out[0][q]; continue; }
-            S_HIP(s, hipMalloc((void**)&s->d_out[sl][q], (size_t)caps[q]));
-        }
-        int64_t host_bytes = caps[q];
-        if (s->cfg.want[q] && s->cfg.compress[q]) {
-            s->gz_cap[q] = caps[q] + 31 * (caps[q] / 65280 + 1) + 64;
-            for (int sl = 0; sl < 2; sl++) S_HIP(s, hipMalloc((void**)&s->d_gz[sl][q], (size_t)s->gz_cap[q]));
-            host_bytes = s->gz_cap[q];
-        }
-        if (s->cfg.want[q])
-            for (int sl = 0; sl < 2; sl++) S_HIP(s, hipHostMalloc((void**)&s->pin_out[sl][q], (size_t)host_bytes));
-    }
+    rc = alloc_outputs(s);
+    if (rc) return rc;
     if (s->cfg.host || s->cfg.want_overlapped) {
         for (int m = 0; m < nm; m++) {
             S_HIP(s, hipHostMalloc((void**)&s->h_res[m], (size_t)s->max_records * sizeof(fastp_gpu_read_result)));
@@ -483,7 +501,7 @@ int replan(fastp_gpu_stream* s, int needed) {
     s->p.max_len = target;
     rc = fastp_gpu_create(&s->p, s->cfg.device, &s->ctx);
     if (rc != FASTP_GPU_OK) { if (image) (void)hipFree(image); return s->fail(rc, std::string("fastp_gpu_create (re-plan): ") + fastp_gpu_last_error(nullptr)); }
-    if (s->cfg.want_overlapped) (void)fastp_gpu_host_writes_overlapped(s->ctx, 1);
+    if (s->cfg.want_overlapped && !s->ov_device) (void)fastp_gpu_host_writes_overlapped(s->ctx, 1);
     if (image) {
         rc = fastp_gpu_dup_bitmap_import(s->ctx, image);
         (void)hipFree(image);
@@ -729,6 +747,17 @@ int fastp_gpu_stream_create(const fastp_gpu_params* params, const fastp_gpu_stre
     if (s->cfg.io_threads <= 0) s->cfg.io_threads = env_int("FASTP_GPU_STREAM_IO_THREADS", 8);
     s->deflate_level = env_int("FASTP_GPU_STREAM_DEFLATE_LEVEL", 0);   // how a binding that does not call the setter passes -z
     if (s->deflate_level < 0 || s->deflate_level > 9) { g_stream_error = "FASTP_GPU_STREAM_DEFLATE_LEVEL outside 0..9"; return FASTP_GPU_E_INVALID; }
+    for (int q = 0; q < FASTP_GPU_N_OUTPUTS; q++) {
+        s->want[q] = s->cfg.want[q]; s->compress[q] = s->cfg.compress[q]; s->out_fd[q] = s->cfg.out_fd[q]; s->out_offset[q] = s->cfg.out_offset[q];
+    }
+    s->out_fd[FASTP_GPU_OVERLAPPED] = -1;
+    // how a binding that does not call fastp_gpu_stream_set_overlapped_output gets --overlapped_out's stream from the device
+    // ("1" as well: a binding that reads the variable as a number, 0 = no stream mode, can then pass it on)
+    if (const char* v = getenv("FASTP_GPU_STREAM_OVERLAPPED")) {
+        if (!strcmp(v, "device") || !strcmp(v, "1")) s->ov_device = cfg->want_overlapped != 0;
+        else if (*v && strcmp(v, "host")) { g_stream_error = "FASTP_GPU_STREAM_OVERLAPPED is neither \"device\" nor \"host\""; return FASTP_GPU_E_INVALID; }
+    }
+    s->want[FASTP_GPU_OVERLAPPED] = s->ov_device ? 1 : 0;
     for (int m = 0; m < s->nf; m++) {
         s->src_kind[m] = input_kind(m ? s->in2 : s->in1);
         s->st.input_kind[m] = s->src_kind[m];
@@ -738,8 +767,8 @@ int fastp_gpu_stream_create(const fastp_gpu_params* params, const fastp_gpu_stre
         const bool possible = q == FASTP_GPU_OUT1 || (s->paired && q == FASTP_GPU_OUT2) || (q == FASTP_GPU_FAILED && cfg->format.want_failed) ||
                               (q == FASTP_GPU_MERGED && s->paired && params->merge) || (q == FASTP_GPU_UNPAIRED1 && s->paired && cfg->format.want_unpaired1) ||
                               (q == FASTP_GPU_UNPAIRED2 && s->paired && cfg->format.want_unpaired2);
-        if (s->cfg.want[q] && !possible) { g_stream_error = "a stream is wanted that the options never write to"; return FASTP_GPU_E_INVALID; }
-        if (s->cfg.want[q] && s->cfg.out_fd[q] < 0 && !s->cfg.emit) { g_stream_error = "a wanted stream has neither a file descriptor nor an emit callback"; return FASTP_GPU_E_INVALID; }
+        if (s->want[q] && !possible) { g_stream_error = "a stream is wanted that the options never write to"; return FASTP_GPU_E_INVALID; }
+        if (s->want[q] && s->out_fd[q] < 0 && !s->cfg.emit) { g_stream_error = "a wanted stream has neither a file descriptor nor an emit callback"; return FASTP_GPU_E_INVALID; }
     }
     if (params->merge && s->paired && !s->cfg.want[FASTP_GPU_MERGED] && (s->cfg.want[FASTP_GPU_OUT1] || s->cfg.want[FASTP_GPU_OUT2])) {
         // merge mode without --merged_out: legal for the reference (the merged reads are dropped); nothing to check
@@ -759,7 +788,7 @@ int fastp_gpu_stream_create(const fastp_gpu_params* params, const fastp_gpu_stre
     buf_thread.join();
     if (rc != FASTP_GPU_OK) { free_buffers(s.get()); g_stream_error = create_err; return rc; }
     s->st.max_len = s->p.max_len;
-    if (s->cfg.want_overlapped) (void)fastp_gpu_host_writes_overlapped(s->ctx, 1);
+    if (s->cfg.want_overlapped && !s->ov_device) (void)fastp_gpu_host_writes_overlapped(s->ctx, 1);
     if (rc_buf != FASTP_GPU_OK) {
         g_stream_error = s->err;
         free_buffers(s.get());
@@ -822,7 +851,7 @@ struct Run {
     Channel<WriteJob> q_write;
     Channel<int> q_ofree;
     Channel<ReplayJob> q_replay;
-    int64_t out_pos[FASTP_GPU_N_OUTPUTS];
+    int64_t out_pos[FASTP_GPU_N_HOST_OUTPUTS];
     explicit Run(fastp_gpu_stream* st) : s(st) {}
 };
 
@@ -1097,18 +1126,18 @@ void writer_main(Run* R) {
             if (s->cfg.emit(s->cfg.user, FASTP_GPU_OVERLAPPED, j.ov.data(), (int64_t)j.ov.size()) != 0) R->emit_err.store(1);
             s->st.bytes_overlapped += (int64_t)j.ov.size();
         }
-        for (int q = 0; q < FASTP_GPU_N_OUTPUTS && j.oslot != 3; q++) {
-            if (!s->cfg.want[q]) continue;
+        for (int q = 0; q < FASTP_GPU_N_HOST_OUTPUTS && j.oslot != 3; q++) {
+            if (!s->want[q]) continue;
             const uint8_t* src = j.oslot >= 2 ? BGZF_EOF : s->pin_out[j.oslot][q];   // oslot 2: the end-of-file members of the compressed streams
             if (j.oslot >= 2 && !j.len[q]) continue;
-            if (s->cfg.out_fd[q] >= 0) {
+            if (s->out_fd[q] >= 0) {
                 // one positional write per stream and chunk, the streams side by side: on tmpfs eight writers into one file
                 // were slower than one (7.8 vs 10 GB/s, profiles/r04_dropin.txt); FASTP_GPU_STREAM_WRITE_PIECE_MB cuts them up
                 static const int64_t piece = (int64_t)env_int("FASTP_GPU_STREAM_WRITE_PIECE_MB", 0) << 20;
                 const int64_t step = piece > 0 ? piece : std::max<int64_t>(j.len[q], 1);
                 for (int64_t a = 0; a < j.len[q]; a += step) {
                     const int64_t e = std::min(j.len[q], a + step);
-                    const int fd = s->cfg.out_fd[q];
+                    const int fd = s->out_fd[q];
                     const int64_t off = R->out_pos[q] + a;
                     std::atomic<int>* err = &R->io_err;
                     pool.submit([fd, src, a, e, off, err] {
@@ -1125,7 +1154,8 @@ void writer_main(Run* R) {
                 if (s->cfg.emit(s->cfg.user, q, (const char*)src, j.len[q]) != 0) R->emit_err.store(1);
             }
             R->out_pos[q] += j.len[q];
-            s->st.bytes_out[q] += j.len[q];
+            if (q < FASTP_GPU_N_OUTPUTS) s->st.bytes_out[q] += j.len[q];
+            else s->st.bytes_overlapped += j.len[q];
         }
         pool.wait();
         s->st.write_s += now_s() - t0;
@@ -1379,7 +1409,8 @@ int run_loop(Run* R) {
             t0 = now_s();
             S_HIP(s, hipMemcpyAsync(&s->h_counts[0], s->d_nc, 4, hipMemcpyDeviceToHost, s->sx));
             S_HIP(s, hipMemcpyAsync(&s->h_counts[1], s->d_nev, 4, hipMemcpyDeviceToHost, s->sx));
-            const bool host_records = s->cfg.host || s->cfg.want_overlapped;
+            const bool host_ov = s->cfg.want_overlapped && !s->ov_device;
+            const bool host_records = s->cfg.host || host_ov;
             if (host_records)
                 for (int m = 0; m < nm; m++) {
                     S_HIP(s, hipMemcpyAsync(s->h_res[m], s->d_res[m], (size_t)n * sizeof(fastp_gpu_read_result), hipMemcpyDeviceToHost, s->sx));
@@ -1401,7 +1432,7 @@ int run_loop(Run* R) {
                     ex.run(n, text, job.blob);
                     if (!job.blob.empty()) R->q_replay.put(std::move(job));
                 }
-                if (s->cfg.want_overlapped) {
+                if (host_ov) {
                     wj.has_ov = true;
                     ex.overlapped(n, text, wj.ov);
                 }
@@ -1425,17 +1456,18 @@ int run_loop(Run* R) {
                 s->st.wait_write_s += now_s() - tw;
                 t0 = now_s();
                 uint8_t* const* d_out = s->d_out[wj.oslot];
-                int64_t lens[FASTP_GPU_N_OUTPUTS];
-                if (fastp_gpu_format_streams(s->ctx, n, &io[0], s->paired ? &io[1] : nullptr, s->d_pair, s->d_corr, s->corr_cap ? s->d_nc : nullptr, &fo,
-                                             const_cast<uint8_t**>(d_out), s->out_cap, lens) != FASTP_GPU_OK)
-                    return s->fail_ctx(FASTP_GPU_E_HIP, "fastp_gpu_format_streams");
+                int64_t lens[FASTP_GPU_N_HOST_OUTPUTS] = {};
+                const auto format = s->ov_device ? fastp_gpu_format_all_streams : fastp_gpu_format_streams;   // (seven entries or six of the same arrays)
+                if (format(s->ctx, n, &io[0], s->paired ? &io[1] : nullptr, s->d_pair, s->d_corr, s->corr_cap ? s->d_nc : nullptr, &fo,
+                           const_cast<uint8_t**>(d_out), s->out_cap, lens) != FASTP_GPU_OK)
+                    return s->fail_ctx(FASTP_GPU_E_HIP, s->ov_device ? "fastp_gpu_format_all_streams" : "fastp_gpu_format_streams");
                 s->st.format_s += now_s() - t0;
                 t0 = now_s();
-                const uint8_t* src[FASTP_GPU_N_OUTPUTS];
-                for (int q = 0; q < FASTP_GPU_N_OUTPUTS; q++) {
+                const uint8_t* src[FASTP_GPU_N_HOST_OUTPUTS];
+                for (int q = 0; q < FASTP_GPU_N_HOST_OUTPUTS; q++) {
                     src[q] = d_out[q];
-                    if (!s->cfg.want[q]) { lens[q] = 0; continue; }
-                    if (s->cfg.compress[q] && lens[q] > 0) {
+                    if (!s->want[q]) { lens[q] = 0; continue; }
+                    if (s->compress[q] && lens[q] > 0) {
                         int64_t glen = 0;
                         if (fastp_gpu_deflate_bgzf_level(s->ctx, d_out[q], lens[q], 0, s->deflate_level, s->d_gz[wj.oslot][q], s->gz_cap[q], &glen) != FASTP_GPU_OK)
                             return s->fail_ctx(FASTP_GPU_E_HIP, "fastp_gpu_deflate_bgzf_level");
@@ -1447,7 +1479,7 @@ int run_loop(Run* R) {
                 t0 = now_s();
                 // (the formatter / deflater have returned their lengths: the text is complete on the device)  The copy runs on its
                 // own stream; the writer thread waits for its event, this thread goes on to the next chunk
-                for (int q = 0; q < FASTP_GPU_N_OUTPUTS; q++) {
+                for (int q = 0; q < FASTP_GPU_N_HOST_OUTPUTS; q++) {
                     wj.len[q] = lens[q];
                     if (lens[q] > 0) S_HIP(s, hipMemcpyAsync(s->pin_out[wj.oslot][q], src[q], (size_t)lens[q], hipMemcpyDeviceToHost, s->cp_out));
                 }
@@ -1536,9 +1568,33 @@ extern "C" int fastp_gpu_stream_set_deflate_level(fastp_gpu_stream* s, int level
     return FASTP_GPU_OK;
 }
 
+extern "C" int fastp_gpu_stream_set_overlapped_output(fastp_gpu_stream* s, int out_fd, int64_t out_offset, int compress) {
+    if (!s || !s->ctx) return FASTP_GPU_E_INVALID;
+    if (s->started) return s->fail(FASTP_GPU_E_INVALID, "the overlapped stream's output is set before fastp_gpu_stream_run");
+    if (!s->cfg.want_overlapped) return s->fail(FASTP_GPU_E_INVALID, "the stream was not created with want_overlapped");
+    if (out_fd < -1 || out_offset < 0) return s->fail(FASTP_GPU_E_INVALID, "bad file descriptor or offset");
+    if (out_fd < 0 && !s->cfg.emit) return s->fail(FASTP_GPU_E_INVALID, "neither a file descriptor nor an emit callback");
+    s->ov_device = true;
+    s->want[FASTP_GPU_OVERLAPPED] = 1;
+    s->out_fd[FASTP_GPU_OVERLAPPED] = out_fd;
+    s->out_offset[FASTP_GPU_OVERLAPPED] = out_offset;
+    s->compress[FASTP_GPU_OVERLAPPED] = compress != 0;
+    (void)hipSetDevice(s->cfg.device);
+    free_output(s, FASTP_GPU_OVERLAPPED);   // (sized at create when the environment chose the device path; run() allocates for what is set now)
+    (void)fastp_gpu_host_writes_overlapped(s->ctx, 0);
+    return FASTP_GPU_OK;
+}
+
+extern "C" int fastp_gpu_stream_overlapped_on_device(const fastp_gpu_stream* s) { return s && s->ov_device ? 1 : 0; }
+
 extern "C" int fastp_gpu_stream_run(fastp_gpu_stream* s) {
     if (!s || !s->ctx) return FASTP_GPU_E_INVALID;
     s->started = true;
+    if (s->ov_device) {   // the seventh stream's buffers (and, when it is the only stream wanted, the ones the formatter needs)
+        S_HIP(s, hipSetDevice(s->cfg.device));
+        const int rc = alloc_outputs(s);
+        if (rc) return rc;
+    }
     const double t_start = now_s();
     fq::timeline("stream: run begin");
     S_HIP(s, hipSetDevice(s->cfg.device));
@@ -1554,7 +1610,7 @@ extern "C" int fastp_gpu_stream_run(fastp_gpu_stream* s) {
         R.pipe[m] = !S_ISREG(sb.st_mode);   // --stdin, a FIFO: read in sequence (a bgzip-written stream then goes through the host inflater)
         R.sizes[m] = R.pipe[m] ? ((int64_t)1 << 62) : (int64_t)sb.st_size;
     }
-    for (int q = 0; q < FASTP_GPU_N_OUTPUTS; q++) R.out_pos[q] = s->cfg.out_offset[q];
+    for (int q = 0; q < FASTP_GPU_N_HOST_OUTPUTS; q++) R.out_pos[q] = s->out_offset[q];
     R.q_ofree.put(0);
     R.q_ofree.put(1);
     std::thread reader(reader_main, &R), writer(writer_main, &R), replayer(replay_main, &R);
@@ -1563,8 +1619,8 @@ extern "C" int fastp_gpu_stream_run(fastp_gpu_stream* s) {
         WriteJob eofs;
         eofs.oslot = 2;
         bool any = false;
-        for (int q = 0; q < FASTP_GPU_N_OUTPUTS; q++)
-            if (s->cfg.want[q] && s->cfg.compress[q]) { eofs.len[q] = (int64_t)sizeof(BGZF_EOF); any = true; }
+        for (int q = 0; q < FASTP_GPU_N_HOST_OUTPUTS; q++)
+            if (s->want[q] && s->compress[q]) { eofs.len[q] = (int64_t)sizeof(BGZF_EOF); any = true; }
         if (any) R.q_write.put(eofs);
     }
     ReadReq stop_r;

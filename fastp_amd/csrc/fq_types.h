@@ -295,8 +295,10 @@ struct FmtArgs {
 };
 
 // ---- every output stream on the device (fq_fmts_* kernels, fastp_gpu_format_streams) ----
-enum { FMTS_STREAMS = 6 };
+// the six streams of the worker loop; --overlapped_out's is the seventh (fq_fmts7_* kernels, fastp_gpu_format_all_streams)
+enum { FMTS_STREAMS = 6, FMTS_ALL_STREAMS = 7 };
 constexpr u32 FMTS_NONE = 0xFFFFFFFFu;
+constexpr u32 FMTS_OVOUT_HIT = 0x8000u;   // FASTP_GPU_OVOUT_HIT in read 1's `reserved`
 struct FmtsMate {
     u8* text;                // corrections are patched in
     const u32* line_off;
@@ -307,15 +309,16 @@ struct FmtsArgs {
     int n, paired, dedup, merge, merge_include_unmerged;
     int want_failed, want_u1, want_u2;
     int umi_loc, umi_len;
+    int overlapped_out;      // the seven-stream kernels only: the records' `reserved` fields describe --overlapped_out's record
     u32 delim_len, prefix_len;
     u8 delim[8], prefix[32];
     FmtsMate m[2];
     const u32* pair;         // 2 dwords per pair record
-    u8* out[FMTS_STREAMS];
-    u64 out_cap[FMTS_STREAMS];
-    u64* blocksum;           // [FMTS_STREAMS][nblocks] bytes the block's units add to each stream
-    u64* blockbase;          // [FMTS_STREAMS][nblocks]
-    u64* totals;             // [FMTS_STREAMS]
+    u8* out[FMTS_ALL_STREAMS];
+    u64 out_cap[FMTS_ALL_STREAMS];
+    u64* blocksum;           // [streams][nblocks] bytes the block's units add to each stream
+    u64* blockbase;          // [streams][nblocks]
+    u64* totals;             // [streams]
     int nblocks;
     const u32* corrections;  // fastp_gpu_correction, 2 dwords each
     const int* n_corrections;

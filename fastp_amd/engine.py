@@ -17,7 +17,7 @@ _LIBS: dict[str, C.CDLL] = {}
 EXPORTS = [
     "fastp_gpu_default_params", "fastp_gpu_seq_stride", "fastp_gpu_qual_stride", "fastp_gpu_cycles_for",
     "fastp_gpu_counter_layout_for", "fastp_gpu_counter_layout_for_params", "fastp_gpu_create", "fastp_gpu_destroy", "fastp_gpu_last_error",
-    "fastp_gpu_pack_reads", "fastp_gpu_pack_reads_x", "fastp_gpu_bgzf_index", "fastp_gpu_inflate_bgzf", "fastp_gpu_parse_fastq", "fastp_gpu_parse_exotic", "fastp_gpu_phred64_to_33", "fastp_gpu_host_writes_overlapped", "fastp_gpu_format_fastq", "fastp_gpu_format_streams", "fastp_gpu_deflate_bgzf", "fastp_gpu_deflate_bgzf_level", "fastp_gpu_device_alloc", "fastp_gpu_device_free", "fastp_gpu_device_upload", "fastp_gpu_device_download", "fastp_gpu_eval_seq_len", "fastp_gpu_eval_adapter_kmers", "fastp_gpu_eval_overrep", "fastp_gpu_submit_host", "fastp_gpu_submit_device", "fastp_gpu_synchronize",
+    "fastp_gpu_pack_reads", "fastp_gpu_pack_reads_x", "fastp_gpu_bgzf_index", "fastp_gpu_inflate_bgzf", "fastp_gpu_parse_fastq", "fastp_gpu_parse_exotic", "fastp_gpu_phred64_to_33", "fastp_gpu_host_writes_overlapped", "fastp_gpu_format_fastq", "fastp_gpu_format_streams", "fastp_gpu_format_all_streams", "fastp_gpu_deflate_bgzf", "fastp_gpu_deflate_bgzf_level", "fastp_gpu_device_alloc", "fastp_gpu_device_free", "fastp_gpu_device_upload", "fastp_gpu_device_download", "fastp_gpu_eval_seq_len", "fastp_gpu_eval_adapter_kmers", "fastp_gpu_eval_overrep", "fastp_gpu_submit_host", "fastp_gpu_submit_device", "fastp_gpu_synchronize",
     "fastp_gpu_counters_device", "fastp_gpu_counters", "fastp_gpu_kernel_time",
     "fastp_gpu_counters_export", "fastp_gpu_counters_import",
     "fastp_gpu_dup_scan_bytes", "fastp_gpu_submit_pass1_device", "fastp_gpu_dup_bitmap_bytes", "fastp_gpu_dup_bitmap_export",
@@ -31,7 +31,7 @@ EXPORTS = [
     "fastp_gpu_host_adapter_entries", "fastp_gpu_host_adapter_entry", "fastp_gpu_host_add_adapter", "fastp_gpu_host_add_adapter_pair",
     # include/fastp_gpu_stream.h
     "fastp_gpu_stream_create", "fastp_gpu_stream_run", "fastp_gpu_stream_layout", "fastp_gpu_stream_counters", "fastp_gpu_stream_get_stats",
-    "fastp_gpu_stream_last_error", "fastp_gpu_stream_destroy", "fastp_gpu_stream_set_deflate_level", "fastp_gpu_stream_gunzip_file", "fastp_gpu_stream_gunzip_file_mt",
+    "fastp_gpu_stream_last_error", "fastp_gpu_stream_destroy", "fastp_gpu_stream_set_deflate_level", "fastp_gpu_stream_set_overlapped_output", "fastp_gpu_stream_overlapped_on_device", "fastp_gpu_stream_gunzip_file", "fastp_gpu_stream_gunzip_file_mt",
 ]
 
 
@@ -338,14 +338,24 @@ class GpuEngine:
                        opts: abi.FormatOptions | None, out_ptrs, out_caps, check=True):
         """every output stream of the worker loop on the device (out1, out2, failed, merged, unpaired1, unpaired2);
         corrections are patched into the mates' text.  Returns (rc, [needed bytes per stream])"""
-        fn = self.lib.fastp_gpu_format_streams
+        return self._format_n(self.lib.fastp_gpu_format_streams, abi.N_OUTPUTS, n, m1, m2, pair_ptr, corrections_ptr,
+                              n_corrections_ptr, opts, out_ptrs, out_caps, check)
+
+    def format_all_streams(self, n, m1: abi.FormatIn, m2, pair_ptr, corrections_ptr, n_corrections_ptr,
+                           opts: abi.FormatOptions | None, out_ptrs, out_caps, check=True):
+        """format_streams' six streams plus --overlapped_out's as the seventh (fastp_gpu_format_all_streams): lists of
+        abi.N_ALL_OUTPUTS entries.  Returns (rc, [needed bytes per stream])"""
+        return self._format_n(self.lib.fastp_gpu_format_all_streams, abi.N_ALL_OUTPUTS, n, m1, m2, pair_ptr, corrections_ptr,
+                              n_corrections_ptr, opts, out_ptrs, out_caps, check)
+
+    def _format_n(self, fn, ns, n, m1, m2, pair_ptr, corrections_ptr, n_corrections_ptr, opts, out_ptrs, out_caps, check):
         fn.restype = C.c_int
         fn.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.FormatIn), C.POINTER(abi.FormatIn), C.c_void_p, C.c_void_p,
                        C.c_void_p, C.POINTER(abi.FormatOptions), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                        C.POINTER(C.c_int64)]
-        outs = (C.c_void_p * abi.N_OUTPUTS)(*[p or None for p in out_ptrs])
-        caps = (C.c_int64 * abi.N_OUTPUTS)(*out_caps)
-        lens = (C.c_int64 * abi.N_OUTPUTS)()
+        outs = (C.c_void_p * ns)(*[p or None for p in out_ptrs])
+        caps = (C.c_int64 * ns)(*out_caps)
+        lens = (C.c_int64 * ns)()
         rc = fn(self.h, n, C.byref(m1), C.byref(m2) if m2 is not None else None, pair_ptr, corrections_ptr,
                 n_corrections_ptr, C.byref(opts) if opts is not None else None, outs, caps, lens)
         if check:

@@ -7,7 +7,8 @@ writerthread.cpp:118-168).  Line splitting + packing (`fastp_gpu_parse_fastq`), 
 reference's processSingleEnd / processPairEnd would have written to out1 / out2 comes out byte for
 byte.  Input files may be plain FASTQ or BGZF (.gz written by bgzip: the reference's BgzfMtReader path,
 src/bgzf.h) - those are shipped compressed and inflated on the device (`fastp_gpu_inflate_bgzf`).
-Every output stream of the worker loop is assembled on the device (`fastp_gpu_format_streams`): out1 / out2,
+Every output stream of the worker loop is assembled on the device (`fastp_gpu_format_streams`; with `--overlapped_out`
+`fastp_gpu_format_all_streams`, which writes that option's stream as well): out1 / out2,
 --failed_out, --unpaired1/2, the merged stream, UMI-renamed records; an output path ending in ".gz" is compressed
 on the device too (`fastp_gpu_deflate_bgzf`: BGZF-framed gzip members, what the reference's WriterThread does per
 pack with libdeflate).  Reader and writer run on their own threads so file I/O overlaps the device work of the
@@ -77,8 +78,9 @@ class FastqPipeline:
         # two pinned staging sets per direction: the reader fills one while the device works on the other
         self.stage_in = [[torch.empty(self.chunk + 64, dtype=torch.uint8).pin_memory() for _ in range(nm)] for _ in range(2)]
         self.stage_out = None      # [slot][stream]: pinned, sized in run() for the streams that are asked for
-        self.outs = [None] * abi.N_OUTPUTS       # device text per stream
-        self.gzbuf = [None] * abi.N_OUTPUTS      # device gzip members per compressed stream
+        # (seven streams: --overlapped_out's is the last, written when params.overlapped_out is set)
+        self.outs = [None] * abi.N_ALL_OUTPUTS   # device text per stream
+        self.gzbuf = [None] * abi.N_ALL_OUTPUTS  # device gzip members per compressed stream
         self.gz_level = None                     # run(compression_level=...)
         self.max_blocks = (2 * self.chunk) // 8192 + 64     # BGZF members per chunk (bgzip: ~64 KiB of text each)
         self.check_crc = True
@@ -232,10 +234,11 @@ class FastqPipeline:
                 2 * int(umi[1]) + 1
         both = nm * self.text_cap + self.max_records * (96 + 2 * grow)          # every record of both mates + tags
         one = self.text_cap + self.max_records * (64 + grow)
-        caps = [one, one, both, both, both, both]
-        self.out_cap = [0] * abi.N_OUTPUTS
+        # --overlapped_out's stream: parts of read 1's records + the UMI tag (fastp_gpu_format_all_streams' bound)
+        caps = [one, one, both, both, both, both, self.text_cap + self.max_records * grow]
+        self.out_cap = [0] * abi.N_ALL_OUTPUTS
         self.gz_out = [bool(p) and p.endswith(".gz") for p in paths]
-        for q in range(abi.N_OUTPUTS):
+        for q in range(abi.N_ALL_OUTPUTS):
             if not paths[q]:
                 continue
             self.out_cap[q] = caps[q]
@@ -245,21 +248,22 @@ class FastqPipeline:
                 gcap = caps[q] + 31 * (caps[q] // 65280 + 1) + 64
                 if self.gzbuf[q] is None or self.gzbuf[q].numel() < gcap:
                     self.gzbuf[q] = torch.empty(gcap, dtype=torch.uint8, device=self.dev)
-        need = [(self.gzbuf[q].numel() if self.gz_out[q] else caps[q]) if paths[q] else 0 for q in range(abi.N_OUTPUTS)]
+        need = [(self.gzbuf[q].numel() if self.gz_out[q] else caps[q]) if paths[q] else 0 for q in range(abi.N_ALL_OUTPUTS)]
         if self.stage_out is None:
-            self.stage_out = [[None] * abi.N_OUTPUTS for _ in range(2)]
+            self.stage_out = [[None] * abi.N_ALL_OUTPUTS for _ in range(2)]
         for sl in range(2):
-            for q in range(abi.N_OUTPUTS):
+            for q in range(abi.N_ALL_OUTPUTS):
                 have = self.stage_out[sl][q]
                 if need[q] and (have is None or have.numel() < need[q]):
                     self.stage_out[sl][q] = torch.empty(need[q], dtype=torch.uint8).pin_memory()
 
     def run(self, in1: str, in2: str | None, out1: str, out2: str | None, failed_out: str | None = None,
             merged_out: str | None = None, unpaired1: str | None = None, unpaired2: str | None = None,
-            umi: tuple | None = None, compression_level: int | None = None) -> dict:
+            umi: tuple | None = None, compression_level: int | None = None, overlapped_out: str | None = None) -> dict:
         """umi = (location "read1" | "read2" | "per_read", length[, prefix bytes[, delimiter bytes]]): the name edit that goes
         with params.umi_len1/2 (UmiProcessor::addUmiToName).  compression_level: the reference's -z (1..9, 0 = the default)
-        for every ".gz" output; None is the default encoder through fastp_gpu_deflate_bgzf"""
+        for every ".gz" output; None is the default encoder through fastp_gpu_deflate_bgzf.  overlapped_out: the file of
+        --overlapped_out's stream, needed when params.overlapped_out is set (a ".gz" path is compressed like the others)"""
         torch = self.torch
         if compression_level is not None and not 0 <= int(compression_level) <= 9:
             raise PipelineError("compression_level is 0 (the default) to 9")
@@ -268,10 +272,12 @@ class FastqPipeline:
             raise PipelineError("paired engine needs in2/out2, single-end engine must not get them")
         if self.params.merge and not merged_out:
             raise PipelineError("merge mode needs merged_out")
+        if bool(self.params.overlapped_out) != bool(overlapped_out):
+            raise PipelineError("params.overlapped_out and the overlapped_out file go together")
         if (self.params.umi_len1 or self.params.umi_len2) and umi is None:
             raise PipelineError("params trim a UMI off the reads: pass umi=(location, length) for the name edit")
         out_paths = [out1, out2, failed_out, merged_out if self.params.merge else None, unpaired1 if self.paired else None,
-                     unpaired2 if self.paired else None]
+                     unpaired2 if self.paired else None, overlapped_out]
         self._setup_outputs(out_paths, umi)
         self.fmt_opts = abi.FormatOptions()
         self.fmt_opts.want_failed = int(bool(failed_out))
@@ -381,7 +387,7 @@ class FastqPipeline:
                     st["t_wait_write"] += time.perf_counter() - t0
                     oslot = out_free.pop(0)
                     t0 = time.perf_counter()
-                    for q in range(abi.N_OUTPUTS):
+                    for q in range(abi.N_ALL_OUTPUTS):
                         if fout[q] is not None and lens[q]:
                             src = self.gzbuf[q] if self.gz_out[q] else self.outs[q]
                             self.stage_out[oslot][q][:lens[q]].copy_(src[:lens[q]], non_blocking=True)
@@ -452,17 +458,20 @@ class FastqPipeline:
             f = abi.FormatIn()
             f.text, f.line_off, f.line_len, f.res = M[m].text.data_ptr(), M[m].loff.data_ptr(), M[m].llen.data_ptr(), M[m].res.data_ptr()
             fi.append(f)
-        rc, lens = self.eng.format_streams(n, fi[0], fi[1] if self.paired else None, self.pair.data_ptr() if self.paired else None,
-                                           self.corr.data_ptr() if self.corr_cap else None,
-                                           self.nc.data_ptr() if self.corr_cap else None, self.fmt_opts,
-                                           [t.data_ptr() if t is not None and self.out_cap[q] else None for q, t in enumerate(self.outs)],
-                                           self.out_cap)
+        # the six streams of the worker loop, or all seven for an --overlapped_out run
+        ns = abi.N_ALL_OUTPUTS if self.params.overlapped_out else abi.N_OUTPUTS
+        fmt = self.eng.format_all_streams if self.params.overlapped_out else self.eng.format_streams
+        rc, lens = fmt(n, fi[0], fi[1] if self.paired else None, self.pair.data_ptr() if self.paired else None,
+                       self.corr.data_ptr() if self.corr_cap else None, self.nc.data_ptr() if self.corr_cap else None, self.fmt_opts,
+                       [t.data_ptr() if t is not None and self.out_cap[q] else None for q, t in enumerate(self.outs[:ns])],
+                       self.out_cap[:ns])
+        lens += [0] * (abi.N_ALL_OUTPUTS - ns)
         if self.corr_cap and int(self.nc[0].item()) > self.corr_cap:
             raise PipelineError("correction list overflow: raise corr_capacity")
         st["t_format"] += time.perf_counter() - t0
         st["bytes_text"] = st.get("bytes_text", 0) + sum(lens)
         t0 = time.perf_counter()
-        for q in range(abi.N_OUTPUTS):
+        for q in range(abi.N_ALL_OUTPUTS):
             if self.out_cap[q] and self.gz_out[q]:
                 rc, lens[q] = self.eng.deflate_bgzf(self.outs[q].data_ptr(), lens[q], self.gzbuf[q].data_ptr(), self.gzbuf[q].numel(),
                                                           level=self.gz_level)

@@ -380,11 +380,12 @@ int fastp_gpu_parse_fastq(fastp_gpu_ctx* ctx, const uint8_t* text, int64_t nbyte
                           uint32_t* line_off,  /* [4*max_records] offset of each record line in `text`      */
                           uint32_t* line_len,  /* [4*max_records] its length without the terminator        */
                           fastp_gpu_parse_info* info);
-/* --overlapped_out (src/peprocessor.cpp:488-495) makes a seventh stream that the device formatter does not write: by
- * default fastp_gpu_format_streams refuses a context with that option (FASTP_GPU_E_UNSUPPORTED) so that nobody loses the
- * stream unnoticed.  A caller that assembles it itself from the records (read 1's `reserved` = FASTP_GPU_OVOUT_HIT | first
- * printed position, read 2's = the number of printed bases; what fastp_gpu_host.h and fastp_gpu_stream.h do) says so
- * here; the other six streams are then formatted as usual (merged part lengths come from the pair records). */
+/* --overlapped_out (src/peprocessor.cpp:488-495) makes a seventh stream.  fastp_gpu_format_all_streams writes it on the
+ * device with the other six.  The six-stream call, fastp_gpu_format_streams, does not: by default it refuses a context
+ * with that option (FASTP_GPU_E_UNSUPPORTED) so that nobody loses the stream unnoticed.  A caller of the six-stream call
+ * that assembles the seventh itself from the records (read 1's `reserved` = FASTP_GPU_OVOUT_HIT | first printed position,
+ * read 2's = the number of printed bases; what fastp_gpu_host.h and fastp_gpu_stream.h's host path do) says so here; the
+ * six streams are then formatted as usual (merged part lengths come from the pair records). */
 int fastp_gpu_host_writes_overlapped(fastp_gpu_ctx* ctx, int on);
 
 /* --phred64 (Read::convertPhred64To33 src/read.cpp, applied by FastqReader::read src/fastqreader.cpp:309-368 to every read of
@@ -468,7 +469,8 @@ int fastp_gpu_format_fastq(fastp_gpu_ctx* ctx, int32_t n, const fastp_gpu_format
  * too small.  All pointers except opts / out / out_capacity / out_len themselves are DEVICE pointers. */
 enum { FASTP_GPU_OUT1 = 0, FASTP_GPU_OUT2 = 1, FASTP_GPU_FAILED = 2, FASTP_GPU_MERGED = 3,
        FASTP_GPU_UNPAIRED1 = 4, FASTP_GPU_UNPAIRED2 = 5, FASTP_GPU_N_OUTPUTS = 6,
-       /* host glue only (fastp_gpu_host.h): --overlapped_out's stream; fastp_gpu_format_streams refuses that option */
+       /* --overlapped_out's stream: written by fastp_gpu_format_all_streams and by the host glue (fastp_gpu_host.h);
+        * fastp_gpu_format_streams has the six above and refuses that option */
        FASTP_GPU_OVERLAPPED = 6, FASTP_GPU_N_HOST_OUTPUTS = 7 };
 #define FASTP_GPU_UMI_NONE 0
 #define FASTP_GPU_UMI_READ1 1     /* UMI_LOC_READ1    */
@@ -502,6 +504,25 @@ int fastp_gpu_format_streams(fastp_gpu_ctx* ctx, int32_t n, const fastp_gpu_form
                              const fastp_gpu_format_options* opts /* NULL = main streams only */,
                              uint8_t* const out[FASTP_GPU_N_OUTPUTS], const int64_t out_capacity[FASTP_GPU_N_OUTPUTS],
                              int64_t out_len[FASTP_GPU_N_OUTPUTS] /* host: bytes written (needed) per stream */);
+
+/* Every stream of fastp_gpu_format_streams plus --overlapped_out's (src/peprocessor.cpp:488-495): arrays of
+ * FASTP_GPU_N_HOST_OUTPUTS (7), index FASTP_GPU_OVERLAPPED.  Streams 0..5 get the bytes fastp_gpu_format_streams writes
+ * for the same inputs (FASTP_GPU_E_OVERFLOW, needed sizes and skipped records included).  The seventh gets, for every pair
+ * whose read 1 record has FASTP_GPU_OVOUT_HIT in `reserved` - whatever its filter codes, RS_NULL or --dedup say: the
+ * reference writes it before it routes anything - read 1's name (after the UMI name edit, as out1 prints it), the bases and
+ * qualities [pos, pos + cnt) of read 1's lines in the parsed text (pos = front + (reserved & 0x7FFF), cnt = read 2's
+ * `reserved`, clamped to the line; BaseCorrector's edits applied) and read 1's strand line, without failed or merged
+ * tags; cnt == 0 gives a record with two empty lines.  A context created with overlapped_out needs a buffer for it
+ * (FASTP_GPU_E_INVALID otherwise); on any other context out_len[6] is 0 and the buffer may be NULL.
+ * fastp_gpu_host_writes_overlapped is not consulted.  The seventh stream never needs more than the bytes of mate 1's
+ * text plus n times the length of the UMI tag (delimiter + prefix + '_' + both UMIs + '_'). */
+int fastp_gpu_format_all_streams(fastp_gpu_ctx* ctx, int32_t n, const fastp_gpu_format_io* mate1,
+                                 const fastp_gpu_format_io* mate2 /* NULL for single-end */,
+                                 const fastp_gpu_pair_result* pair /* [n] paired; NULL for single-end */,
+                                 const fastp_gpu_correction* corrections, const int32_t* n_corrections /* may be NULL */,
+                                 const fastp_gpu_format_options* opts /* NULL = main streams only */,
+                                 uint8_t* const out[FASTP_GPU_N_HOST_OUTPUTS], const int64_t out_capacity[FASTP_GPU_N_HOST_OUTPUTS],
+                                 int64_t out_len[FASTP_GPU_N_HOST_OUTPUTS] /* host: bytes written (needed) per stream */);
 
 /* ---- device memory for callers that do not link the HIP runtime themselves ----------------
  * The entry points that take DEVICE pointers (submit_device, parse / format / deflate / inflate, eval_*)

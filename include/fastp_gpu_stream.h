@@ -73,9 +73,11 @@ typedef struct fastp_gpu_stream_config {
     int32_t phred64;            /* --phred64: quality characters are converted as FastqReader::read does
                                  * (fastp_gpu_phred64_to_33 after the parser)                                        */
     int32_t want_overlapped;    /* --overlapped_out (params->overlapped_out): its stream - the bases of read 1 the reference
-                                 * prints for an overlapped pair, src/peprocessor.cpp:488-495 - is assembled on the host from
-                                 * the records and the chunk's text and handed to emit() as stream FASTP_GPU_OVERLAPPED (one
-                                 * call per chunk, in order, also with len == 0); emit must be given                     */
+                                 * prints for an overlapped pair, src/peprocessor.cpp:488-495 - is produced.  By default it is
+                                 * assembled on the host from the records and the chunk's text and handed to emit() as stream
+                                 * FASTP_GPU_OVERLAPPED (one call per chunk, in order, also with len == 0); emit must be given.
+                                 * fastp_gpu_stream_set_overlapped_output (or FASTP_GPU_STREAM_OVERLAPPED=device) moves it to
+                                 * the device formatter                                                                  */
 } fastp_gpu_stream_config;
 
 typedef struct fastp_gpu_stream_stats {
@@ -90,7 +92,7 @@ typedef struct fastp_gpu_stream_stats {
     double inflate_s;           /* BGZF inputs: the device inflate + the text's copy to the host                */
     int64_t bytes_file[2];      /* bytes read from each input file (bytes_in counts TEXT)                        */
     int32_t input_kind[2];      /* 0 plain text, 1 gzip inflated on the host, 2 BGZF inflated on the device      */
-    int64_t bytes_overlapped;   /* bytes handed to emit() for --overlapped_out's stream                          */
+    int64_t bytes_overlapped;   /* bytes of --overlapped_out's stream handed to emit() or written (device path: as bytes_out) */
 } fastp_gpu_stream_stats;
 
 typedef struct fastp_gpu_stream fastp_gpu_stream;
@@ -105,6 +107,17 @@ int fastp_gpu_stream_run(fastp_gpu_stream* s);
  * FASTP_GPU_E_INVALID for a level outside 0..9 and once fastp_gpu_stream_run has been called.  A stream this was never
  * called for takes the environment variable FASTP_GPU_STREAM_DEFLATE_LEVEL (read at create, 0..9), else the default. */
 int fastp_gpu_stream_set_deflate_level(fastp_gpu_stream* s, int level);
+/* Between create and run, for a stream created with want_overlapped: --overlapped_out's stream is formatted (and, with
+ * compress != 0, deflated at the stream's level) on the device, by fastp_gpu_format_all_streams, beside the other six:
+ * the records and line tables then stay on the device unless the adapter replay (config.host) wants them.
+ * out_fd >= 0: pwrite from out_offset on; out_fd == -1: emit(user, FASTP_GPU_OVERLAPPED, ...) - one call per chunk, in
+ * order, also with len == 0, as on the host path.  A compressed stream ends in bgzip's end-of-file member.
+ * FASTP_GPU_E_INVALID once fastp_gpu_stream_run has been called, and for a stream created without want_overlapped.
+ * A stream this was never called for takes the environment variable FASTP_GPU_STREAM_OVERLAPPED (read at create):
+ * "device" (or "1") = this call with out_fd -1 and compress 0, "host" or unset = the host path, anything else
+ * FASTP_GPU_E_INVALID. */
+int fastp_gpu_stream_set_overlapped_output(fastp_gpu_stream* s, int out_fd, int64_t out_offset, int compress);
+int fastp_gpu_stream_overlapped_on_device(const fastp_gpu_stream* s);   /* 1 once the device writes it */
 /* the run's counter block in the layout of the LAST context (cycles = its max_len; the blocks of the contexts a
  * re-plan replaced are folded in).  fastp_gpu_stream_layout first, then counters with n = layout.total. */
 int fastp_gpu_stream_layout(const fastp_gpu_stream* s, fastp_gpu_counter_layout* out);
