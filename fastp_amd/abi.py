@@ -192,6 +192,12 @@ class FormatOptions(C.Structure):
                 ("corrections_capacity", C.c_int32)]
 
 
+# FASTP_GPU_UMI_*: FormatOptions.umi_loc (and the host glue's); NAME_FIX_MGI (--fix_mgi_id) is OR-ed into it
+UMI_NONE, UMI_READ1, UMI_READ2, UMI_PER_READ, UMI_INDEX1, UMI_INDEX2, UMI_PER_INDEX = range(7)
+UMI_LOC = {"read1": UMI_READ1, "read2": UMI_READ2, "per_read": UMI_PER_READ,
+           "index1": UMI_INDEX1, "index2": UMI_INDEX2, "per_index": UMI_PER_INDEX}
+NAME_FIX_MGI = 0x100   # FASTP_GPU_NAME_FIX_MGI
+
 N_OUTPUTS = 6  # FASTP_GPU_OUT1, OUT2, FAILED, MERGED, UNPAIRED1, UNPAIRED2
 N_ALL_OUTPUTS = 7  # ... and FASTP_GPU_OVERLAPPED (OUT_OVERLAPPED, --overlapped_out's stream): fastp_gpu_format_all_streams
 OUT_OVERLAPPED = 6   # FASTP_GPU_OVERLAPPED: the host glue's and fastp_gpu_format_all_streams' seventh stream

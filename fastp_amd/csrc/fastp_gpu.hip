@@ -220,7 +220,10 @@ extern "C" __global__ void __launch_bounds__(1024) fq_fmts_scan_kernel(FmtsArgs 
     extern __shared__ u32 fq_lds[];
     fmts_scan_body(f, (u64*)fq_lds);
 }
-extern "C" __global__ void __launch_bounds__(256) fq_fmts_write_kernel(FmtsArgs f) {
+// (six wavefronts per SIMD, i.e. 80 VGPRs, as before the name plan: without the bound the allocator takes 82 - 87 and drops to
+// five.  The bound changes the allocation of the options-off path as well - 73 -> 80 VGPRs, 33 -> 50 SGPRs spilled to VGPR lanes;
+// what was measured is one shape in one visit, 1 M pairs of 2 x 150 bases: 1.58 - 1.59 ms against the parent's 1.60)
+extern "C" __global__ void __launch_bounds__(256, 6) fq_fmts_write_kernel(FmtsArgs f) {
     extern __shared__ u32 fq_lds[];
     fmts_write_body<FMTS_STREAMS, 2>(f, fq_lds);
 }
@@ -230,7 +233,7 @@ extern "C" __global__ void __launch_bounds__(256) fq_fmts7_len_kernel(FmtsArgs f
     extern __shared__ u32 fq_lds[];
     fmts_len_body<FMTS_ALL_STREAMS, 3>(f, fq_lds);
 }
-extern "C" __global__ void __launch_bounds__(256) fq_fmts7_write_kernel(FmtsArgs f) {
+extern "C" __global__ void __launch_bounds__(256, 6) fq_fmts7_write_kernel(FmtsArgs f) {
     extern __shared__ u32 fq_lds[];
     fmts_write_body<FMTS_ALL_STREAMS, 3>(f, fq_lds);
 }
@@ -2326,9 +2329,12 @@ static int format_streams_impl(fastp_gpu_ctx* ctx, const int ns, int32_t n, cons
         f.want_failed = opts->want_failed != 0;
         f.want_u1 = opts->want_unpaired1 != 0;
         f.want_u2 = opts->want_unpaired2 != 0;
-        if (opts->umi_loc < FASTP_GPU_UMI_NONE || opts->umi_loc > FASTP_GPU_UMI_PER_READ)
-            return fail(ctx, FASTP_GPU_E_UNSUPPORTED, "UMIs taken from the index part of the name are host logic");
-        f.umi_loc = opts->umi_loc;
+        const int loc = opts->umi_loc & 0xFF;
+        if (opts->umi_loc < 0 || (opts->umi_loc & ~(0xFF | FASTP_GPU_NAME_FIX_MGI)) || loc > FASTP_GPU_UMI_PER_INDEX)
+            return fail(ctx, FASTP_GPU_E_UNSUPPORTED, "unknown UMI location or name option in umi_loc");
+        f.umi_loc = loc;
+        f.fix_mgi = (opts->umi_loc & FASTP_GPU_NAME_FIX_MGI) ? 1 : 0;
+        f.name_scan = (f.fix_mgi || loc >= FASTP_GPU_UMI_INDEX1) ? 1 : 0;
         f.umi_len = opts->umi_len;
         if (opts->umi_delimiter) {
             const size_t dl = strlen(opts->umi_delimiter);

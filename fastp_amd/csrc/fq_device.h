@@ -27,6 +27,7 @@
 // whose behaviour it reproduces (paths relative to the reference root).
 #pragma once
 #include "fq_intrin.h"
+#include "fq_names.h"
 
 namespace fq {
 
@@ -4062,40 +4063,84 @@ FQ_DEV u32 fmts_strlen(const char* t) {
 FQ_DEV u32 fmts_umin(u32 a, u32 b) { return a < b ? a : b; }
 FQ_DEV u32 fmts_digits(u32 v) { return v >= 1000u ? 4u : v >= 100u ? 3u : v >= 10u ? 2u : 1u; }
 
-// UmiProcessor::process + addUmiToName: length of the text inserted into the names of this unit (0 = no edit),
-// and the lengths of its two UMI parts
-FQ_DEV u32 fmts_umi(const FmtsArgs& f, int g, u32& u1, u32& u2) {
-    u1 = u2 = 0;
-    if (f.umi_loc == 0) return 0;
-    const u32 ul = (u32)imax(0, f.umi_len);
-    const u32 l1 = f.m[0].line_len[4 * (size_t)g + 1];
-    const u32 l2 = f.paired ? f.m[1].line_len[4 * (size_t)g + 1] : 0u;
+// The name plan of unit g: Read::fixMGI on each mate, then UmiProcessor::process + addUmiToName (peprocessor.cpp:413-420).
+// Both mates of a unit get the same tag, in front of their (fixed) name's first space.
+struct FmtsNames {
+    u32 tag_len;       // delimiter + prefix + '_' + UMI text; 0: nothing is inserted
+    u32 mgi;           // bit m: mate m's name gets the space of the MGI fix
+    struct { u32 off, len; } ix[2];   // each mate's part of the UMI text.  index1 / index2 / per_index: read 1's firstIndex, read 2's lastIndex
+                       // (fq_names.h; a piece that reaches the end of an MGI-fixed name holds the fix's space);
+                       // read1 / read2 / per_read: len bases from the start of the mate's sequence line
+};
+// GROUP: called by all 16 lanes of a copy group (lane gl), which walk the names together
+template <bool GROUP>
+FQ_DEV void fmts_names(const FmtsArgs& f, int g, int gl, FmtsNames& p) {
+    p.tag_len = 0;
+    p.mgi = 0;
+    p.ix[0].off = p.ix[0].len = p.ix[1].off = p.ix[1].len = 0;
+    if (f.umi_loc == 0 && !f.name_scan) return;
     bool tag = true;
-    if (f.umi_loc == 1) u1 = l1 < ul ? l1 : ul;
-    else if (f.umi_loc == 2) { if (f.paired) u2 = l2 < ul ? l2 : ul; else tag = false; }
-    else { u1 = l1 < ul ? l1 : ul; if (f.paired) u2 = l2 < ul ? l2 : ul; }
-    if (f.umi_loc != 3 && u1 + u2 == 0u) tag = false;
-    if (!tag) return 0;
-    return f.delim_len + (f.prefix_len ? f.prefix_len + 1u : 0u) + u1 + u2 + ((f.umi_loc == 3 && f.paired) ? 1u : 0u);
+    u32 body = 0;
+    if (!f.name_scan || f.umi_loc <= 3) {
+        if (f.umi_loc == 0) tag = false;
+        const u32 ul = (u32)imax(0, f.umi_len);
+        const u32 l1 = f.m[0].line_len[4 * (size_t)g + 1];
+        const u32 l2 = f.paired ? f.m[1].line_len[4 * (size_t)g + 1] : 0u;
+        if (f.umi_loc == 1) p.ix[0].len = l1 < ul ? l1 : ul;
+        else if (f.umi_loc == 2) { if (f.paired) p.ix[1].len = l2 < ul ? l2 : ul; else tag = false; }
+        else if (f.umi_loc == 3) { p.ix[0].len = l1 < ul ? l1 : ul; if (f.paired) p.ix[1].len = l2 < ul ? l2 : ul; }
+        if (f.umi_loc != 3 && p.ix[0].len + p.ix[1].len == 0u) tag = false;
+        body = p.ix[0].len + p.ix[1].len + ((f.umi_loc == 3 && f.paired) ? 1u : 0u);
+    }
+    if (f.name_scan) {  // (uniform: the options word)  the names themselves are read only here
+        const u8* nm[2] = {nullptr, nullptr};
+        u32 nl[2] = {0u, 0u};
+        for (int m = 0; m < (f.paired ? 2 : 1); m++) {
+            nm[m] = f.m[m].text + f.m[m].line_off[4 * (size_t)g];
+            nl[m] = f.m[m].line_len[4 * (size_t)g];
+            if (f.fix_mgi && name_is_mgi(nm[m], nl[m])) p.mgi |= 1u << m;
+        }
+        if (f.umi_loc >= 4) {
+            if (f.umi_loc != 5) {
+                const bool mgi = (p.mgi & 1u) != 0u;
+                const NameIndex x = GROUP ? name_first_index_group(nm[0], nl[0], mgi, gl) : name_first_index(nm[0], nl[0], mgi);
+                p.ix[0].off = x.off;
+                p.ix[0].len = x.len;
+            }
+            if (f.umi_loc != 4 && f.paired) {
+                const bool mgi = (p.mgi & 2u) != 0u;
+                const NameIndex x = GROUP ? name_last_index_group(nm[1], nl[1], mgi, gl) : name_last_index(nm[1], nl[1], mgi);
+                p.ix[1].off = x.off;
+                p.ix[1].len = x.len;
+            }
+            body = p.ix[0].len + p.ix[1].len;
+            if (f.umi_loc == 6) body += f.paired ? 1u : 0u;   // a tag whatever the indexes hold, "_" between the mates' indexes
+            else if (body == 0u) tag = false;                   // (index2 of a single read: no edit)
+        }
+    }
+    if (!tag) return;   // (a tag of no bytes - an empty delimiter in front of empty indexes - edits nothing either)
+    p.tag_len = f.delim_len + (f.prefix_len ? f.prefix_len + 1u : 0u) + body;
 }
 
 // geometry of one emission of unit g
 struct FmtsRec {
     int mt;            // the mate whose name / strand lines are used
-    u32 name_len, strand_len, seq_len, tag_len, umi_len, mtag_len;   // mtag: " merged_L1_L2"
+    u32 name_len, strand_len, seq_len, tag_len, umi_len, mtag_len;   // name_len: as parsed; mtag: " merged_L1_L2"
+    u32 mgi;           // 1: the name is printed with the space of the MGI fix
     u32 m1, m2, ol;    // merged parts
     u32 start;         // source 3: first printed position of the sequence / quality line
     bool strand_tagged;
     u32 bytes;
 };
 template <int SLOTS>
-FQ_DEV void fmts_rec(const FmtsArgs& f, int g, u32 em, u32 umi_len, FmtsRec& r) {
+FQ_DEV void fmts_rec(const FmtsArgs& f, int g, u32 em, const FmtsNames& names, FmtsRec& r) {
     const int src = (int)((em >> 3) & 3u);
     r.mt = src == 1 ? 1 : 0;
     const FmtsMate& M = f.m[r.mt];
     r.name_len = M.line_len[4 * (size_t)g];
     r.strand_len = M.line_len[4 * (size_t)g + 2];
-    r.umi_len = umi_len;
+    r.umi_len = names.tag_len;
+    r.mgi = (names.mgi >> r.mt) & 1u;
     const int tagkind = (int)((em >> 5) & 7u);
     r.tag_len = tagkind ? fmts_strlen(fmts_tag_text(tagkind, (em >> 8) & 0xFFu)) : 0u;
     r.mtag_len = 0;
@@ -4123,7 +4168,7 @@ FQ_DEV void fmts_rec(const FmtsArgs& f, int g, u32 em, u32 umi_len, FmtsRec& r) 
     } else {
         r.seq_len = M.res[(size_t)g * 3] >> 16;
     }
-    r.bytes = r.name_len + r.umi_len + r.mtag_len + (r.tag_len ? 1u + r.tag_len : 0u) + 1u + r.seq_len + 1u + r.strand_len +
+    r.bytes = r.name_len + r.mgi + r.umi_len + r.mtag_len + (r.tag_len ? 1u + r.tag_len : 0u) + 1u + r.seq_len + 1u + r.strand_len +
               (r.strand_tagged ? r.mtag_len : 0u) + 1u + r.seq_len + 1u;
 }
 
@@ -4151,12 +4196,12 @@ FQ_DEV void fmts_len_body(const FmtsArgs& f, u32* lds) {
     if (g < f.n) {
         u32 e[SLOTS];
         fmts_route_all<SLOTS>(f, g, e);
-        u32 u1, u2;
-        const u32 ul = fmts_any<SLOTS>(e) ? fmts_umi(f, g, u1, u2) : 0u;
+        FmtsNames names = {};
+        if (fmts_any<SLOTS>(e)) fmts_names<false>(f, g, 0, names);
         for (int k = 0; k < SLOTS; k++) {
             if (e[k] == FMTS_NONE) continue;
             FmtsRec r;
-            fmts_rec<SLOTS>(f, g, e[k], ul, r);
+            fmts_rec<SLOTS>(f, g, e[k], names, r);
             const int st = (int)(e[k] & 7u);
 #pragma unroll
             for (int q = 0; q < NS; q++) bytes[q] += q == st ? r.bytes : 0u;
@@ -4212,6 +4257,20 @@ FQ_DEV void fmts_put(u8* dst, const u8* src, u32 n, int gl) {
     if (gl == 15)
         for (u32 i = n & ~3u; i < n; i++) dst[i] = src[i];
 }
+// the piece [off, off + len) of mate M's fixed name (fq_names.h) by the group; returns len
+FQ_DEV u32 fmts_put_index(u8* dst, const FmtsMate& M, int g, u32 off, u32 len, bool mgi, int gl) {
+    if (len == 0u) return 0u;
+    const u8* nm = M.text + M.line_off[4 * (size_t)g];
+    const u32 nl = M.line_len[4 * (size_t)g];
+    if (!(mgi && off + len == nl + 1u)) {   // not up to the end of an MGI-fixed name: the bytes as parsed
+        fmts_put(dst, nm + off, len, gl);
+        return len;
+    }
+    const u32 front = len - 3u;              // ... + ' ' + the name's last two characters
+    fmts_put(dst, nm + off, front, gl);
+    if (gl == 0) { dst[front] = ' '; dst[front + 1u] = nm[nl - 2u]; dst[front + 2u] = nm[nl - 1u]; }
+    return len;
+}
 FQ_DEV u8 fmts_complement(u8 c) {  // util.h:16-33: anything outside ACGTacgt -> 'N'
     switch (c) {
         case 'A': case 'a': return 'T';
@@ -4245,15 +4304,15 @@ FQ_DEV void fmts_write_body(const FmtsArgs& f, u32* lds) {
     u32 e[SLOTS], sz[SLOTS];
 #pragma unroll
     for (int k = 0; k < SLOTS; k++) { e[k] = FMTS_NONE; sz[k] = 0; }
-    u32 ul = 0, u1 = 0, u2 = 0;
     if (g < f.n) {
         fmts_route_all<SLOTS>(f, g, e);
-        if (fmts_any<SLOTS>(e)) ul = fmts_umi(f, g, u1, u2);
+        FmtsNames names = {};
+        if (fmts_any<SLOTS>(e)) fmts_names<false>(f, g, 0, names);
 #pragma unroll
         for (int k = 0; k < SLOTS; k++)
             if (e[k] != FMTS_NONE) {
                 FmtsRec r;
-                fmts_rec<SLOTS>(f, g, e[k], ul, r);
+                fmts_rec<SLOTS>(f, g, e[k], names, r);
                 sz[k] = r.bytes;
             }
     }
@@ -4306,24 +4365,23 @@ FQ_DEV void fmts_write_body(const FmtsArgs& f, u32* lds) {
         u32 em = ee[0];
 #pragma unroll
         for (int j = 1; j < SLOTS; j++) em = k == j ? ee[j] : em;   // (no indexed private array)
-        u32 v1, v2;
-        const u32 uml = fmts_umi(f, gu, v1, v2);
+        FmtsNames names;
+        fmts_names<true>(f, gu, gl, names);
         FmtsRec r;
-        fmts_rec<SLOTS>(f, gu, em, uml, r);
+        fmts_rec<SLOTS>(f, gu, em, names, r);
         const int st = (int)(em & 7u), src = (int)((em >> 3) & 3u), tagkind = (int)((em >> 5) & 7u);
         if (!f.out[st] || o64 + r.bytes > f.out_cap[st]) continue;  // the host sees the needed size in totals
         const FmtsMate& M = f.m[r.mt];
         u8* o = f.out[st] + o64;
-        // ---- name line: name [up to its first space] + UMI tag + rest + merged tag + failed tag ----
+        // ---- name line: name [up to its first space] + UMI tag + rest [the MGI fix's space in front of the last two
+        //      characters] + merged tag + failed tag ----
         const u8* name = M.text + M.line_off[4 * (size_t)gu];
-        u32 sp = r.name_len;
-        if (uml) {  // position of the first space (one lane scans: names are short)
-            for (u32 i = 0; i < r.name_len; i++)
-                if (name[i] == ' ') { sp = i; break; }
-        }
+        const u32 body_end = r.name_len - 2u * r.mgi;   // what lies in front of the MGI fix's space
+        u32 sp = body_end;
+        if (names.tag_len) sp = name_first_space_group(name, r.name_len, r.mgi != 0u, gl);
         fmts_put(o, name, sp, gl);
         o += sp;
-        if (uml) {
+        if (names.tag_len) {
             fmts_put(o, f.delim, f.delim_len, gl);
             o += f.delim_len;
             if (f.prefix_len) {
@@ -4331,17 +4389,30 @@ FQ_DEV void fmts_write_body(const FmtsArgs& f, u32* lds) {
                 if (gl == 0) o[f.prefix_len] = '_';
                 o += f.prefix_len + 1u;
             }
-            fmts_put(o, f.m[0].text + f.m[0].line_off[4 * (size_t)gu + 1], v1, gl);
-            o += v1;
-            if (f.umi_loc == 3 && f.paired) {
-                if (gl == 0) o[0] = '_';
-                o += 1;
+            if (f.umi_loc <= 3) {
+                fmts_put(o, f.m[0].text + f.m[0].line_off[4 * (size_t)gu + 1], names.ix[0].len, gl);
+                o += names.ix[0].len;
+                if (f.umi_loc == 3 && f.paired) {
+                    if (gl == 0) o[0] = '_';
+                    o += 1;
+                }
+                if (names.ix[1].len) fmts_put(o, f.m[1].text + f.m[1].line_off[4 * (size_t)gu + 1], names.ix[1].len, gl);
+                o += names.ix[1].len;
+            } else {
+                o += fmts_put_index(o, f.m[0], gu, names.ix[0].off, names.ix[0].len, (names.mgi & 1u) != 0u, gl);
+                if (f.umi_loc == 6 && f.paired) {
+                    if (gl == 0) o[0] = '_';
+                    o += 1;
+                }
+                if (f.paired) o += fmts_put_index(o, f.m[1], gu, names.ix[1].off, names.ix[1].len, (names.mgi & 2u) != 0u, gl);
             }
-            if (v2) fmts_put(o, f.m[1].text + f.m[1].line_off[4 * (size_t)gu + 1], v2, gl);
-            o += v2;
         }
-        fmts_put(o, name + sp, r.name_len - sp, gl);
-        o += r.name_len - sp;
+        fmts_put(o, name + sp, body_end - sp, gl);
+        o += body_end - sp;
+        if (r.mgi) {
+            if (gl == 0) { o[0] = ' '; o[1] = name[r.name_len - 2u]; o[2] = name[r.name_len - 1u]; }
+            o += 3;
+        }
         if (src == 2) o += fmts_put_mtag(o, r.m1, r.m2, gl);
         if (tagkind) {
             if (gl == 0) o[0] = ' ';

@@ -11,6 +11,8 @@
 #include <vector>
 
 #include "../../include/fastp_gpu_host.h"
+#define FQ_NAMES_HOST
+#include "fq_names.h"
 
 namespace {
 
@@ -102,17 +104,14 @@ struct fastp_gpu_host {
                 const char* tag = nullptr) {
         record(which, View{name.data(), name.size()}, seq, qual, len, View{strand.data(), strand.size()}, tag);
     }
-    std::string umi_tagged(const std::string& name, const std::string& umi) const {  // addUmiToName umiprocessor.cpp:62-81
-        std::string tag = umi_delim + (umi_prefix.empty() ? std::string() : umi_prefix + "_") + umi;
-        const size_t sp = name.find(' ');
-        return sp == std::string::npos ? name + tag : name.substr(0, sp) + tag + name.substr(sp);
-    }
 };
 
 extern "C" {
 
 int fastp_gpu_host_create(const fastp_gpu_params* params, const fastp_gpu_host_options* opts, fastp_gpu_host** out) {
     if (!params || !out) return FASTP_GPU_E_INVALID;
+    if (opts && (opts->umi_loc < 0 || (opts->umi_loc & ~(0xFF | FASTP_GPU_NAME_FIX_MGI)) || (opts->umi_loc & 0xFF) > FASTP_GPU_UMI_PER_INDEX))
+        return FASTP_GPU_E_UNSUPPORTED;
     fastp_gpu_host* h = new fastp_gpu_host();
     h->p = *params;
     memset(&h->o, 0, sizeof(h->o));
@@ -272,17 +271,12 @@ int fastp_gpu_host_apply(fastp_gpu_host* h, const fastp_gpu_reads* b1, const fas
             s2.assign(b2->seq[i], (size_t)b2->len[i]);
             q2.assign(b2->qual[i], (size_t)b2->len[i]);
         }
-        // UMI name edit on the ORIGINAL reads (umiprocessor.cpp:19-61), before anything is routed
-        if (h->o.umi_loc != FASTP_GPU_UMI_NONE) {
-            std::string umi;
-            bool tag = true;
-            const size_t ul = (size_t)std::max(0, h->o.umi_len);
-            if (h->o.umi_loc == FASTP_GPU_UMI_READ1) umi = s1.substr(0, ul);
-            else if (h->o.umi_loc == FASTP_GPU_UMI_READ2) { if (paired) umi = s2.substr(0, ul); else tag = false; }
-            else { umi = s1.substr(0, ul); if (paired) umi += "_" + s2.substr(0, ul); }
-            if (h->o.umi_loc != FASTP_GPU_UMI_PER_READ && umi.empty()) tag = false;
-            if (tag) { name1 = h->umi_tagged(name1, umi); if (paired) name2 = h->umi_tagged(name2, umi); }
-        }
+        // the MGI fix and the UMI name edit on the ORIGINAL reads (peprocessor.cpp:413-420, umiprocessor.cpp:11-61), before
+        // anything is routed
+        if (h->o.umi_loc != FASTP_GPU_UMI_NONE)
+            fq::names_host_edit(h->o.umi_loc, h->o.umi_len, h->umi_delim, h->umi_prefix, b1->name[i], (size_t)b1->name_len[i], s1.data(),
+                                s1.size(), paired ? b2->name[i] : nullptr, paired ? (size_t)b2->name_len[i] : 0, s2.data(), s2.size(),
+                                &name1, &name2);
         // BaseCorrector edits (basecorrector.cpp:39-57)
         auto apply_corr = [&](uint32_t key, std::string& s, std::string& q) {
             auto it = corr.find(key);

@@ -45,6 +45,8 @@
 #include <vector>
 
 #include "../../include/fastp_gpu_stream.h"
+#define FQ_NAMES_HOST
+#include "fq_names.h"
 #include "fq_pgunzip.h"
 #include "fq_timeline.h"
 
@@ -333,11 +335,16 @@ int alloc_outputs(fastp_gpu_stream* s) {
     const int nf = s->nf;
     // what a record can grow by over its input text: the UMI tag on the name (delimiter + prefix + '_' + the UMI of one or
     // both mates joined by '_', UmiProcessor::addUmiToName), the failed / merged tags on the name and the strand line
-    int64_t grow = 0;
-    if (s->cfg.format.umi_loc != FASTP_GPU_UMI_NONE)
-        grow = (int64_t)s->umi_delim.size() + (s->umi_prefix.empty() ? 0 : (int64_t)s->umi_prefix.size() + 1) + 2 * (int64_t)s->cfg.format.umi_len + 1;
-    const int64_t both = nf * s->text_cap + (int64_t)s->max_records * (96 + 2 * grow);   // every record of both mates + tags
-    const int64_t one = s->text_cap + (int64_t)s->max_records * grow + 64;              // out1 / out2: records only shrink, but for the UMI tag
+    // Tags taken from the names' indexes are as long as those: over a chunk they add up to no more than the names of both
+    // mates, i.e. less than the text (fastp_gpu_format_streams' bound); the MGI fix adds a byte per record.
+    int64_t grow = 0, names = 0;
+    const int loc = s->cfg.format.umi_loc & 0xFF;
+    const int64_t tag_fixed = (int64_t)s->umi_delim.size() + (s->umi_prefix.empty() ? 0 : (int64_t)s->umi_prefix.size() + 1);
+    if (loc >= FASTP_GPU_UMI_INDEX1) { grow = tag_fixed + 3; names = nf * s->text_cap; }
+    else if (loc != FASTP_GPU_UMI_NONE) grow = tag_fixed + 2 * (int64_t)std::max(0, s->cfg.format.umi_len) + 1;
+    if (s->cfg.format.umi_loc & FASTP_GPU_NAME_FIX_MGI) grow += 1;
+    const int64_t both = nf * s->text_cap + 2 * names + (int64_t)s->max_records * (96 + 2 * grow);   // every record of both mates + tags
+    const int64_t one = s->text_cap + names + (int64_t)s->max_records * grow + 64;                   // out1 / out2: records only shrink, but for the name edit
     // (--overlapped_out's: parts of read 1's records with the UMI tag, fastp_gpu_format_all_streams' bound)
     const int64_t caps[FASTP_GPU_N_HOST_OUTPUTS] = {one, one, both, both, both, both, one};
     s->any_out = false;
@@ -584,29 +591,20 @@ struct Extractor {
             const char* name_end = line_end(name, t + lo[1]);
             const char* strand = t + lo[2];
             const char* strand_end = line_end(strand, t + lo[3]);
-            // the name after UmiProcessor::process (src/umiprocessor.cpp:19-81): the tag goes in front of the first space
+            // the name after Read::fixMGI and UmiProcessor::process (src/umiprocessor.cpp:11-81)
             if (fo.umi_loc != FASTP_GPU_UMI_NONE) {
-                const size_t ul = (size_t)std::max(0, fo.umi_len);
                 const char* s1 = t + lo[1];
                 const size_t l1 = (size_t)(line_end(s1, t + lo[2]) - s1);
                 const uint32_t* lo2 = s->h_loff[1] + 4 * (size_t)i;
-                const char* s2 = (const char*)text[1] + lo2[1];
-                const size_t l2 = (size_t)(line_end(s2, (const char*)text[1] + lo2[2]) - s2);
-                std::string umi;
-                if (fo.umi_loc == FASTP_GPU_UMI_READ1) umi.assign(s1, std::min(ul, l1));
-                else if (fo.umi_loc == FASTP_GPU_UMI_READ2) umi.assign(s2, std::min(ul, l2));
-                else { umi.assign(s1, std::min(ul, l1)); umi += "_"; umi.append(s2, std::min(ul, l2)); }
-                if (fo.umi_loc == FASTP_GPU_UMI_PER_READ || !umi.empty()) {
-                    const char* sp = name;
-                    while (sp < name_end && *sp != ' ') sp++;
-                    out.append(name, (size_t)(sp - name));
-                    out += s->umi_delim;
-                    if (!s->umi_prefix.empty()) { out += s->umi_prefix; out += '_'; }
-                    out += umi;
-                    out.append(sp, (size_t)(name_end - sp));
-                } else {
-                    out.append(name, (size_t)(name_end - name));
-                }
+                const char* t2 = (const char*)text[1];
+                const char* name2 = t2 + lo2[0];
+                const size_t nl2 = (size_t)(line_end(name2, t2 + lo2[1]) - name2);
+                const char* s2 = t2 + lo2[1];
+                const size_t l2 = (size_t)(line_end(s2, t2 + lo2[2]) - s2);
+                std::string edited;
+                fq::names_host_edit(fo.umi_loc, fo.umi_len, s->umi_delim, s->umi_prefix, name, (size_t)(name_end - name), s1, l1,
+                                    name2, nl2, s2, l2, &edited, nullptr);
+                out += edited;
             } else {
                 out.append(name, (size_t)(name_end - name));
             }

@@ -308,7 +308,9 @@ struct FmtsMate {
 struct FmtsArgs {
     int n, paired, dedup, merge, merge_include_unmerged;
     int want_failed, want_u1, want_u2;
-    int umi_loc, umi_len;
+    int umi_loc, umi_len;    // umi_loc: FASTP_GPU_UMI_* alone (the low byte of the options word)
+    int fix_mgi;             // FASTP_GPU_NAME_FIX_MGI
+    int name_scan;           // fix_mgi or an index location: the kernels read the name lines before they copy them
     int overlapped_out;      // the seven-stream kernels only: the records' `reserved` fields describe --overlapped_out's record
     u32 delim_len, prefix_len;
     u8 delim[8], prefix[32];

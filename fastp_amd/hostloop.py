@@ -151,14 +151,50 @@ def _final_read(batch: FastqBatch, i: int, rr, corr_for_read):
     return s, q
 
 
-class UmiNameEditor:
-    """The name edit of UmiProcessor::process for UMIs taken from the read itself
-    (umiprocessor.cpp:19-61; locations read1 / read2 / per_read).  Host-side by
-    design: the engine only reproduces the sequence front-trim (params.umi_len*)."""
+def fix_mgi_name(name: bytes) -> bytes:
+    """Read::fixMGI (read.cpp:160-171): a name that ends in /1 or /2 gets a space in front of the '/'."""
+    if len(name) >= 2 and name[-2:] in (b"/1", b"/2"):
+        return name[:-2] + b" " + name[-2:]
+    return name
 
-    def __init__(self, loc: str, umi_len: int, prefix: bytes = b"", delimiter: bytes = b":"):
-        assert loc in ("read1", "read2", "per_read")
-        self.loc, self.umi_len, self.prefix, self.delimiter = loc, umi_len, prefix, delimiter
+
+def first_index(name: bytes) -> bytes:
+    """Read::firstIndex (read.cpp:87-100) of a name (the '@' counts): behind the last ':' in front of the final two
+    characters, up to the leftmost '+' behind that ':'."""
+    n = len(name)
+    if n < 5:
+        return b""
+    end = n
+    for i in range(n - 3, -1, -1):
+        if name[i] == 0x2B:   # '+'
+            end = i - 1
+        if name[i] == 0x3A:   # ':'
+            return name[i + 1:i + 1 + (end - i)]
+    return b""
+
+
+def last_index(name: bytes) -> bytes:
+    """Read::lastIndex (read.cpp:75-85): behind the last ':' or '+' in front of the final two characters."""
+    n = len(name)
+    if n < 5:
+        return b""
+    for i in range(n - 3, -1, -1):
+        if name[i] in (0x3A, 0x2B):
+            return name[i + 1:]
+    return b""
+
+
+class UmiNameEditor:
+    """The name edits of the worker loop in front of everything else (peprocessor.cpp:413-420): Read::fixMGI on each
+    mate (fix_mgi=), then UmiProcessor::process (umiprocessor.cpp:11-61) - UMIs taken from the read itself (read1 /
+    read2 / per_read; the engine reproduces the sequence front-trim, params.umi_len*) or from the index part of the
+    fixed name (index1 / index2 / per_index; umi_len is ignored).  loc None: the MGI fix alone."""
+
+    LOCATIONS = ("read1", "read2", "per_read", "index1", "index2", "per_index")
+
+    def __init__(self, loc: str | None, umi_len: int = 0, prefix: bytes = b"", delimiter: bytes = b":", fix_mgi: bool = False):
+        assert loc is None or loc in self.LOCATIONS
+        self.loc, self.umi_len, self.prefix, self.delimiter, self.fix_mgi = loc, umi_len, prefix or b"", delimiter, fix_mgi
 
     def _tagged(self, name: bytes, umi: bytes) -> bytes:  # addUmiToName :62-81
         tag = self.delimiter + (self.prefix + b"_" if self.prefix else b"") + umi
@@ -166,20 +202,33 @@ class UmiNameEditor:
         return name + tag if sp < 0 else name[:sp] + tag + name[sp:]
 
     def edit(self, name1: bytes, seq1: bytes, name2: bytes | None, seq2: bytes | None):
+        if self.fix_mgi:
+            name1 = fix_mgi_name(name1)
+            name2 = fix_mgi_name(name2) if name2 is not None else None
+        paired = name2 is not None
+        if self.loc is None:
+            return name1, name2
         if self.loc == "read1":
             umi = seq1[:self.umi_len]
         elif self.loc == "read2":
-            if seq2 is None:
+            if not paired:
                 return name1, name2
             umi = seq2[:self.umi_len]
-        else:
-            umi = seq1[:self.umi_len]
-            if seq2 is not None:
-                umi = umi + b"_" + seq2[:self.umi_len]
-            return self._tagged(name1, umi), (self._tagged(name2, umi) if name2 is not None else None)
+        elif self.loc == "index1":
+            umi = first_index(name1)
+        elif self.loc == "index2":
+            if not paired:
+                return name1, name2
+            umi = last_index(name2)
+        else:   # per_read / per_index: the tag is always added
+            if self.loc == "per_read":
+                umi = seq1[:self.umi_len] + (b"_" + seq2[:self.umi_len] if paired else b"")
+            else:
+                umi = first_index(name1) + (b"_" + last_index(name2) if paired else b"")
+            return self._tagged(name1, umi), (self._tagged(name2, umi) if paired else None)
         if not umi:
             return name1, name2
-        return self._tagged(name1, umi), (self._tagged(name2, umi) if name2 is not None else None)
+        return self._tagged(name1, umi), (self._tagged(name2, umi) if paired else None)
 
 
 def apply_results(params: abi.Params, b1: FastqBatch, b2: FastqBatch | None, r1, r2, pair, corrections,

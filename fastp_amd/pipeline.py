@@ -222,20 +222,28 @@ class FastqPipeline:
 
     EOF_MEMBER = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")   # bgzip's empty last member
 
-    def _setup_outputs(self, paths, umi=None):
+    def _setup_outputs(self, paths, umi=None, fix_mgi_id=False):
         """device + pinned buffers for the streams that are written; paths[q] per abi stream index"""
         torch = self.torch
         nm = len(self.mates)
         # what a record can grow by over its input text: the UMI name tag (addUmiToName: delimiter + prefix + '_' + the
-        # UMI of one or both mates joined by '_'), the failed / merged tags on the name and the strand line
-        grow = 0
+        # UMI of one or both mates joined by '_'), the failed / merged tags on the name and the strand line.  A tag taken
+        # from the names' indexes is as long as those: over a chunk such tags add up to less than the text of both mates
+        # (fastp_gpu_format_streams' bound); the MGI fix adds a byte per record
+        grow = names = 0
         if umi:
-            grow = len(umi[3] if len(umi) > 3 and umi[3] else b":") + (len(umi[2]) + 1 if len(umi) > 2 and umi[2] else 0) + \
-                2 * int(umi[1]) + 1
-        both = nm * self.text_cap + self.max_records * (96 + 2 * grow)          # every record of both mates + tags
-        one = self.text_cap + self.max_records * (64 + grow)
-        # --overlapped_out's stream: parts of read 1's records + the UMI tag (fastp_gpu_format_all_streams' bound)
-        caps = [one, one, both, both, both, both, self.text_cap + self.max_records * grow]
+            grow = len(umi[3] if len(umi) > 3 and umi[3] else b":") + (len(umi[2]) + 1 if len(umi) > 2 and umi[2] else 0)
+            if umi[0] in ("index1", "index2", "per_index"):
+                grow += 3
+                names = nm * self.text_cap
+            else:
+                grow += 2 * int(umi[1]) + 1
+        if fix_mgi_id:
+            grow += 1
+        both = nm * self.text_cap + 2 * names + self.max_records * (96 + 2 * grow)   # every record of both mates + tags
+        one = self.text_cap + names + self.max_records * (64 + grow)
+        # --overlapped_out's stream: parts of read 1's records + the name edit (fastp_gpu_format_all_streams' bound)
+        caps = [one, one, both, both, both, both, self.text_cap + names + self.max_records * grow]
         self.out_cap = [0] * abi.N_ALL_OUTPUTS
         self.gz_out = [bool(p) and p.endswith(".gz") for p in paths]
         for q in range(abi.N_ALL_OUTPUTS):
@@ -259,9 +267,12 @@ class FastqPipeline:
 
     def run(self, in1: str, in2: str | None, out1: str, out2: str | None, failed_out: str | None = None,
             merged_out: str | None = None, unpaired1: str | None = None, unpaired2: str | None = None,
-            umi: tuple | None = None, compression_level: int | None = None, overlapped_out: str | None = None) -> dict:
+            umi: tuple | None = None, compression_level: int | None = None, overlapped_out: str | None = None,
+            fix_mgi_id: bool = False) -> dict:
         """umi = (location "read1" | "read2" | "per_read", length[, prefix bytes[, delimiter bytes]]): the name edit that goes
-        with params.umi_len1/2 (UmiProcessor::addUmiToName).  compression_level: the reference's -z (1..9, 0 = the default)
+        with params.umi_len1/2 (UmiProcessor::addUmiToName); or (location "index1" | "index2" | "per_index", 0[, prefix[,
+        delimiter]]): the UMI is the index part of the name, nothing is trimmed.  fix_mgi_id: --fix_mgi_id, a space in front
+        of a name's final /1 or /2, before the UMI edit.  compression_level: the reference's -z (1..9, 0 = the default)
         for every ".gz" output; None is the default encoder through fastp_gpu_deflate_bgzf.  overlapped_out: the file of
         --overlapped_out's stream, needed when params.overlapped_out is set (a ".gz" path is compressed like the others)"""
         torch = self.torch
@@ -278,16 +289,20 @@ class FastqPipeline:
             raise PipelineError("params trim a UMI off the reads: pass umi=(location, length) for the name edit")
         out_paths = [out1, out2, failed_out, merged_out if self.params.merge else None, unpaired1 if self.paired else None,
                      unpaired2 if self.paired else None, overlapped_out]
-        self._setup_outputs(out_paths, umi)
+        self._setup_outputs(out_paths, umi, fix_mgi_id)
         self.fmt_opts = abi.FormatOptions()
         self.fmt_opts.want_failed = int(bool(failed_out))
         self.fmt_opts.want_unpaired1 = int(bool(out_paths[4]))
         self.fmt_opts.want_unpaired2 = int(bool(out_paths[5]))
         if umi is not None:
-            self.fmt_opts.umi_loc = {"read1": 1, "read2": 2, "per_read": 3}[umi[0]]
+            if umi[0] not in abi.UMI_LOC:
+                raise PipelineError(f"unknown UMI location {umi[0]!r}")
+            self.fmt_opts.umi_loc = abi.UMI_LOC[umi[0]]
             self.fmt_opts.umi_len = int(umi[1])
             self.fmt_opts.umi_prefix = umi[2] if len(umi) > 2 and umi[2] else None
             self.fmt_opts.umi_delimiter = umi[3] if len(umi) > 3 else None
+        if fix_mgi_id:
+            self.fmt_opts.umi_loc |= abi.NAME_FIX_MGI
         nm = len(self.mates)
         paths = (in1, in2) if self.paired else (in1,)
         gz = [self.is_bgzf(p) for p in paths]

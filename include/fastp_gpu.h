@@ -466,7 +466,17 @@ int fastp_gpu_format_fastq(fastp_gpu_ctx* ctx, int32_t n, const fastp_gpu_format
  * patched INTO `text` first (the reference edits its reads in place, so every stream prints the corrected bases):
  * `text` is therefore written to.  Streams the options do not ask for get no bytes (their buffers may be NULL).
  * Output order inside a stream = input order.  FASTP_GPU_E_OVERFLOW + needed sizes in out_len when a buffer is
- * too small.  All pointers except opts / out / out_capacity / out_len themselves are DEVICE pointers. */
+ * too small.  All pointers except opts / out / out_capacity / out_len themselves are DEVICE pointers.
+ * Capacities that always suffice, with T1 / T2 the bytes of the mates' texts, D = delimiter + (prefix + 1 if there is a
+ * prefix) and G the most a unit's tag adds to one record:
+ *     read1 / read2 / per_read:        G = D + 2 * umi_len + 1
+ *     index1 / index2 / per_index:     the tag is as long as the indexes, which are pieces of the unit's own names:
+ *                                      G <= D + 3 + (name of read 1) + (name of read 2), so over n units
+ *                                      sum G <= n * (D + 3) + T1 + T2, whatever the names hold
+ *     FASTP_GPU_NAME_FIX_MGI:          one more byte per record
+ *   out1, out2:                        T1 (T2) + sum G + n
+ *   failed, merged, unpaired1/2:       T1 + T2 + 2 * (sum G + n) + 96 * n     (both mates' records, the failed tag, and the
+ *                                      merged tag on the name and the strand line) */
 enum { FASTP_GPU_OUT1 = 0, FASTP_GPU_OUT2 = 1, FASTP_GPU_FAILED = 2, FASTP_GPU_MERGED = 3,
        FASTP_GPU_UNPAIRED1 = 4, FASTP_GPU_UNPAIRED2 = 5, FASTP_GPU_N_OUTPUTS = 6,
        /* --overlapped_out's stream: written by fastp_gpu_format_all_streams and by the host glue (fastp_gpu_host.h);
@@ -476,12 +486,23 @@ enum { FASTP_GPU_OUT1 = 0, FASTP_GPU_OUT2 = 1, FASTP_GPU_FAILED = 2, FASTP_GPU_M
 #define FASTP_GPU_UMI_READ1 1     /* UMI_LOC_READ1    */
 #define FASTP_GPU_UMI_READ2 2     /* UMI_LOC_READ2    */
 #define FASTP_GPU_UMI_PER_READ 3  /* UMI_LOC_PER_READ */
+/* UMIs taken from the index part of the name (Read::firstIndex / lastIndex, src/read.cpp:75-100): no bases are trimmed,
+ * umi_len is ignored.  index1: read 1's first index; index2: read 2's last index (no edit on single-end input); for both
+ * an empty index means no tag.  per_index: first index of read 1 [+ '_' + last index of read 2], the tag is always added. */
+#define FASTP_GPU_UMI_INDEX1 4    /* UMI_LOC_INDEX1    */
+#define FASTP_GPU_UMI_INDEX2 5    /* UMI_LOC_INDEX2    */
+#define FASTP_GPU_UMI_PER_INDEX 6 /* UMI_LOC_PER_INDEX */
+/* --fix_mgi_id (Read::fixMGI, src/read.cpp:160-171), OR-ed into umi_loc, whose low byte is the location (which may be
+ * FASTP_GPU_UMI_NONE): a name that ends in "/1" or "/2" gets a space in front of the '/', each mate on its own, BEFORE the
+ * UMI edit - the index functions and the search for the first space see the fixed name.  Any other bit or location:
+ * FASTP_GPU_E_UNSUPPORTED. */
+#define FASTP_GPU_NAME_FIX_MGI 0x100
 
 typedef struct fastp_gpu_format_options {
     int32_t want_failed;      /* --failed_out given   */
     int32_t want_unpaired1;   /* --unpaired1 given    */
     int32_t want_unpaired2;   /* --unpaired2 given (and different from --unpaired1) */
-    int32_t umi_loc;          /* FASTP_GPU_UMI_*      */
+    int32_t umi_loc;          /* FASTP_GPU_UMI_* [| FASTP_GPU_NAME_FIX_MGI] */
     int32_t umi_len;
     const char* umi_prefix;   /* host string, may be NULL, at most 32 characters */
     const char* umi_delimiter;/* host string, NULL = ":", at most 8 characters   */
@@ -514,8 +535,9 @@ int fastp_gpu_format_streams(fastp_gpu_ctx* ctx, int32_t n, const fastp_gpu_form
  * `reserved`, clamped to the line; BaseCorrector's edits applied) and read 1's strand line, without failed or merged
  * tags; cnt == 0 gives a record with two empty lines.  A context created with overlapped_out needs a buffer for it
  * (FASTP_GPU_E_INVALID otherwise); on any other context out_len[6] is 0 and the buffer may be NULL.
- * fastp_gpu_host_writes_overlapped is not consulted.  The seventh stream never needs more than the bytes of mate 1's
- * text plus n times the length of the UMI tag (delimiter + prefix + '_' + both UMIs + '_'). */
+ * fastp_gpu_host_writes_overlapped is not consulted.  The seventh stream never needs more than out1 does: the bytes of
+ * mate 1's text plus sum G + n of fastp_gpu_format_streams' comment - n times (delimiter + prefix + '_' + both UMIs +
+ * '_') for the UMIs taken from the reads, n * (D + 4) + T1 + T2 for those taken from the names' indexes. */
 int fastp_gpu_format_all_streams(fastp_gpu_ctx* ctx, int32_t n, const fastp_gpu_format_io* mate1,
                                  const fastp_gpu_format_io* mate2 /* NULL for single-end */,
                                  const fastp_gpu_pair_result* pair /* [n] paired; NULL for single-end */,

@@ -33,7 +33,7 @@ typedef struct fastp_gpu_host_options {
     int32_t want_failed;      /* --failed_out given   */
     int32_t want_unpaired1;   /* --unpaired1 given    */
     int32_t want_unpaired2;   /* --unpaired2 given    */
-    int32_t umi_loc;          /* FASTP_GPU_UMI_*      */
+    int32_t umi_loc;          /* FASTP_GPU_UMI_* [| FASTP_GPU_NAME_FIX_MGI] */
     int32_t umi_len;
     const char* umi_prefix;   /* may be NULL          */
     const char* umi_delimiter;/* NULL = ":"           */
