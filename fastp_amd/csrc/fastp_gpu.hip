@@ -76,19 +76,9 @@ extern "C" __global__ void __launch_bounds__(1024) fq_stats5_kernel(StatsArgs a)
 #ifdef FQ_PROFILE_ABLATION
     if ((a.debug_skip & 0xC0u) && a.Hs == 10 && a.kc == 2) { stats_body5<2, 10, true>(a, fq_lds); return; }   // profiling build only
 #endif
-#ifndef FQ_ST5_ONEBLK
-#define FQ_ST5_ONEBLK 1   // (A/B: 0 = the block form for every length)
-#endif
-#ifndef FQ_ST5_NOFRONT
-#define FQ_ST5_NOFRONT 1   // (A/B: 0 = the front read from the arguments / the records whatever the options)
-#endif
-    const bool nofront = FQ_ST5_NOFRONT && !a.front_per_read && a.front[0] == 0 && a.front[1] == 0;   // (uniform)
-#ifndef FQ_ST5_TAILCOL
-#define FQ_ST5_TAILCOL 0   // (A/B: 1 = the reads' last column out of the lane mapping: visit o -2.3 %, visit p +1.4 % - no gain, off)
-#endif
-    if (FQ_ST5_TAILCOL && FQ_ST5_ONEBLK && a.Hs == 10 && a.kc == 2 && a.H16 == 10 && nofront) stats_body5<2, 10, false, true, true, true>(a, fq_lds);   // 145 - 160 bases, no front trim
-    else if (FQ_ST5_ONEBLK && a.Hs == 10 && a.kc == 2 && a.H16 <= 10 && nofront) stats_body5<2, 10, false, true, true>(a, fq_lds);   // reads of up to 160 bases, no front trim
-    else if (FQ_ST5_ONEBLK && a.Hs == 10 && a.kc == 2 && a.H16 <= 10) stats_body5<2, 10, false, true>(a, fq_lds);   // reads of up to 160 bases (uniform)
+    const bool nofront = !a.front_per_read && a.front[0] == 0 && a.front[1] == 0;   // (uniform)
+    if (a.Hs == 10 && a.kc == 2 && a.H16 <= 10 && nofront) stats_body5<2, 10, false, true, true>(a, fq_lds);   // reads of up to 160 bases, no front trim
+    else if (a.Hs == 10 && a.kc == 2 && a.H16 <= 10) stats_body5<2, 10, false, true>(a, fq_lds);   // reads of up to 160 bases (uniform)
     else if (a.Hs == 10 && a.kc == 2) stats_body5<2, 10, false>(a, fq_lds);
     else if (a.Hs == 8 && a.kc == 2) stats_body5<2, 8, false>(a, fq_lds);  // two blocks of eight columns: reads of up to 256 bases
     else if (a.kc == 2) stats_body5<2, 0, false>(a, fq_lds);
@@ -243,17 +233,12 @@ extern "C" __global__ void __launch_bounds__(64 * TEXT_WAVES) fq_text_kernel(Tex
 }
 extern "C" __global__ void __launch_bounds__(256) fq_text_mask_kernel(TextMaskArgs m) { text_mask_body(m); }
 extern "C" __global__ void __launch_bounds__(256) fq_reduce_kernel(ReduceArgs r) { reduce_body(r); }
-extern "C" __global__ void __launch_bounds__(256) fq_dup_probe_kernel(DupArgs d) { dup_probe_body(d); }
 extern "C" __global__ void __launch_bounds__(256) fq_dup_claim_kernel(DupArgs d) { dup_claim_body(d); }
 extern "C" __global__ void __launch_bounds__(256) fq_dup_losers_kernel(DupArgs d) { dup_losers_body(d); }
 extern "C" __global__ void __launch_bounds__(256) fq_dup_winners_kernel(DupArgs d) { dup_winners_body(d); }
 extern "C" __global__ void __launch_bounds__(1024) fq_dup_finish_kernel(DupArgs d) {
-    extern __shared__ u32 fq_lds[];
+    extern __shared__ u32 fq_lds[];  // 1 dword: the workgroup's duplicate count
     dup_finish_body(d, fq_lds);
-}
-extern "C" __global__ void __launch_bounds__(1024) fq_dup_resolve_kernel(DupArgs d) {
-    extern __shared__ __attribute__((aligned(16))) u32 fq_lds[];  // 1 dword: the workgroup's duplicate count
-    dup_resolve_body(d, fq_lds);
 }
 
 // ---------------------------------------------------------------------------
@@ -272,10 +257,8 @@ struct Switches {
     int lds_kb;               // the tile kernels' LDS budget (0: not set): tests/test_launch_geometry.py
     int max_tiles_per_block;  // > 0 caps a launch so that a small batch takes several: the parity tests
     int hash_generic;         // the multiply form of the duplicate hash: tests/test_hostsim_parity.py
-    int dup_table;            // Duplicate's first form (probe + resolve): tests/test_hostsim_parity.py, tools/dup_forms_check.py
     int claim_fused;          // 0 = Duplicate's claim as its own kernel: tests/test_hostsim_parity.py, tools/dup_forms_check.py
     int dedup_fold;           // 0 = --dedup through the hash pre-pass on the lane plan too: tests/test_hostsim_parity.py
-    int lane_pool_log2;       // the lane kernel's chunk pool (LaneArgs::pool): tests/test_hostsim_parity.py
     int stats_blocks_per_cu;  // Stats workgroups per CU (0: what fits): tests/test_hostsim_parity.py, tools/two_engine_probe.py
     int exact;                // every unit through the text kernel: tests/test_gpu_parity.py
     int test_merge_slow;      // every merged read's second part counted by the lane kernel: the parity tests
@@ -320,8 +303,6 @@ struct fastp_gpu_ctx {
     int ln_swm = 0, ln_blocks = 0, ln_threads = 256;
     LaneLds ln_lds;
     u32* d_ln_slabs = nullptr;
-    int* d_ln_ctr = nullptr;       // the lane kernel's chunk pool counter (LaneArgs::chunk_ctr)
-    int ln_pool_base = 0;          // LaneArgs::pool_base: what the counter may have reached by the next launch
     // split plans (never null there): Duplicate's losers / winners / finish kernels of a launch run on this stream beside its Stats kernel
     hipStream_t tail = nullptr;
     hipEvent_t ev_k1 = nullptr, ev_tail = nullptr;
@@ -424,10 +405,8 @@ static Switches read_switches() {
     w.lds_kb = env_int("FASTP_GPU_LDS_KB", 0);
     w.max_tiles_per_block = env_int("FASTP_GPU_MAX_TILES_PER_BLOCK", 0);
     w.hash_generic = env_int("FASTP_GPU_HASH_GENERIC", 0);
-    w.dup_table = env_int("FASTP_GPU_DUP_TABLE", 0);
     w.claim_fused = env_int("FASTP_GPU_CLAIM_FUSED", 1);
     w.dedup_fold = env_int("FASTP_GPU_DEDUP_FOLD", 1);
-    w.lane_pool_log2 = env_int("FASTP_GPU_LANE_POOL_LOG2", 0);
     w.stats_blocks_per_cu = env_int("FASTP_GPU_STATS_BLOCKS_PER_CU", 0);
     w.exact = env_int("FASTP_GPU_EXACT", 0);
     w.test_merge_slow = env_int("FASTP_GPU_TEST_MERGE_SLOW", 0);
@@ -480,7 +459,7 @@ extern "C" void fastp_gpu_destroy(fastp_gpu_ctx* ctx) {
                     ctx->d_bitmap, ctx->d_dup_pos, ctx->d_table, ctx->d_need, ctx->d_dupflag, ctx->d_stage, ctx->d_phase,
                     ctx->d_ovr_table[0], ctx->d_ovr_table[1], ctx->d_ovr_sym[0], ctx->d_ovr_sym[1], ctx->d_ovr_len[0],
                     ctx->d_ovr_len[1], ctx->d_post_seen, ctx->d_ovr_work, ctx->d_parse, ctx->d_fmt, ctx->d_prefix, ctx->d_inf, ctx->d_ovr_corr, ctx->d_eval, ctx->d_def, ctx->d_setw, ctx->d_cfilter,
-                    ctx->d_st_slabs, ctx->d_swin[0], ctx->d_swin[1], ctx->d_ln_slabs, ctx->d_ln_ctr,
+                    ctx->d_st_slabs, ctx->d_swin[0], ctx->d_swin[1], ctx->d_ln_slabs,
                     ctx->d_corr_int, ctx->d_corr_chain, ctx->d_x_unit, ctx->d_x_len, ctx->d_x_skip, ctx->d_al[0], ctx->d_al[1], ctx->d_al[2], ctx->d_al[3], ctx->d_x_text[0], ctx->d_x_text[1], ctx->d_x_off[0], ctx->d_x_off[1]};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
@@ -597,7 +576,6 @@ static void fill_arg_templates(fastp_gpu_ctx* ctx) {
     sa.slabs = ctx->d_st_slabs; sa.slab_dwords = ctx->st_slab_dwords;
     LaneArgs& la = ctx->t_lane;
     la.l = ctx->ln_lds;
-    la.chunk_ctr = ctx->d_ln_ctr;
     la.post1 = ctx->d_ctr + cl.stats[1];
     la.st_qual_hist = cl.st_qual_hist; la.st_kmer = cl.st_kmer; la.st_cycle = cl.st_cycle; la.cycles = cl.cycles;
     FrontStatsArgs& fs = ctx->t_front;
@@ -924,8 +902,6 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
         CREATE_TRY(hipEventCreateWithFlags(&ctx->ev_tail, hipEventDisableTiming));
         if (ctx->lane) {
             CREATE_TRY(hipMalloc((void**)&ctx->d_ln_slabs, (size_t)ctx->ln_blocks * ctx->ln_lds.n_misc * 4));
-            CREATE_TRY(hipMalloc((void**)&ctx->d_ln_ctr, sizeof(int)));
-            CREATE_TRY(hipMemset(ctx->d_ln_ctr, 0, sizeof(int)));
             for (int Bh : {0, ctx->dp.dup_enabled ? ctx->dp.dup_bufnum : 0})
                 CREATE_TRY(hipFuncSetAttribute((const void*)lane_kernel_for(ctx->ln_swm, Bh, ctx->dp.paired != 0, lane_ext(ctx->dp)),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, ctx->ln_lds.total * 4));
@@ -1184,9 +1160,8 @@ struct LaunchPlan {
     // without --dedup, Duplicate's tail decides, fq_dedup_apply_kernel takes the duplicates out again before the Stats kernel counts
     // (not in merge mode: a pair that merges is written out whatever Duplicate says, peprocessor.cpp:523-535)
     bool dedup_prepass = false, dedup_folded = false;
-    // the claim step inside the per-read kernel (dup_prepare in front of it, dup_tail behind it; otherwise dup_claim_chain, in the
-    // table form - FASTP_GPU_DUP_TABLE - probe + resolve): plain stream mode, one or two bloom buffers (the lane kernel: four as
-    // well), the context's own stream order
+    // the claim step inside the per-read kernel (dup_prepare in front of it, dup_tail behind it; otherwise dup_claim_chain):
+    // plain stream mode, one or two bloom buffers (the lane kernel: four as well), the context's own stream order
     // ... and a launch with units for the text kernel when that kernel runs beside the lane kernel (TEXT_BESIDE_LANE): the lane kernel
     // claims nothing for such a unit (KernelArgs::xskip), the text kernel claims its units' bits itself (fq_text.h t_claim) and
     // Duplicate's tail - which orders the claims by unit index, whoever fired them first - runs behind both
@@ -1247,7 +1222,7 @@ static LaunchPlan plan_launch(const fastp_gpu_ctx* ctx, const fastp_gpu_batch* b
     p.align_rows = ctx->lane && !aligned && dp.merge_lane;
     const bool use_lane = ctx->lane && (aligned || p.align_rows);
     p.kernel = use_lane ? K_LANE : !ctx->split ? K_FUSED : ctx->cfg.threads > 256 ? K_SCAN_WIDE : K_SCAN;
-    p.dedup_folded = dp.dedup && use_lane && stream && !p.exact && !sw.dup_table && !dp.merge_lane && sw.dedup_fold &&
+    p.dedup_folded = dp.dedup && use_lane && stream && !p.exact && !dp.merge_lane && sw.dedup_fold &&
                      sw.claim_fused;   // (the fold IS the fused claim: without it the hash pre-pass decides)
     p.dedup_prepass = dp.dedup && !p.dedup_folded && stream;
     p.text_prepass = p.exact && (p.dedup_prepass || (mode == CHUNK_PASS1 && dp.dedup));
@@ -1255,7 +1230,7 @@ static LaunchPlan plan_launch(const fastp_gpu_ctx* ctx, const fastp_gpu_batch* b
     p.text = !p.exact ? TEXT_NONE : exact_early ? TEXT_BESIDE_LANE : (ctx->split && stream && !dp.dedup) ? TEXT_BEHIND_ON_TAIL : TEXT_INLINE;
     const bool text_on_tail = p.text == TEXT_BESIDE_LANE || p.text == TEXT_BEHIND_ON_TAIL;
     p.corr_list = ctx->split && dp.corr_lane && mode != CHUNK_OVERREP && !(mode == CHUNK_PASS1 && dp.dedup);
-    p.claim_fused = dp.dup_enabled && (!dp.dedup || p.dedup_folded) && stream && (dp.dup_bufnum <= 2 || p.dedup_folded) && !sw.dup_table &&
+    p.claim_fused = dp.dup_enabled && (!dp.dedup || p.dedup_folded) && stream && (dp.dup_bufnum <= 2 || p.dedup_folded) &&
                     sw.claim_fused && (!p.exact || exact_early);
     p.clears_on_tail = ctx->split && !p.dedup_folded && n > 0;
     if (p.dedup_folded && p.claim_fused && n > 0) p.dup_place = DUP_BEFORE_STATS;
@@ -1499,7 +1474,6 @@ static int dup_args(Launch& l, u8* dupflag, bool scan, DupArgs* out) {
     d.paired = ctx->dp.paired;
     d.ctr_total = ctx->d_ctr + ctx->cl.dup_total;
     d.ctr_dups = ctx->d_ctr + ctx->cl.dup_count;
-    if (ctx->sw.dup_table) return 0;
     rc = ensure(ctx, (void**)&ctx->d_setw, &ctx->setw_cap, (size_t)l.n);
     if (rc) return rc;
     if (!ctx->d_cfilter) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_cfilter, (size_t)1 << (DUP_CF_LOG2 - 3)));
@@ -1547,13 +1521,6 @@ static int dup_claim_chain(Launch& l, u8* dupflag, bool scan, hipStream_t st) {
     const int rc = dup_args(l, dupflag, scan, &d);
     if (rc) return rc;
     HIP_TRY(ctx, hipMemsetAsync(d.table, 0xFF, (size_t)8 << d.table_log2, st));
-    if (ctx->sw.dup_table) {      // the first form: probe (read + table insert for every unit) -> resolve
-        hipLaunchKernelGGL(fq_dup_probe_kernel, dim3(std::max(1, (l.n + 255) / 256)), dim3(256), 0, st, d);
-        HIP_TRY(ctx, hipGetLastError());
-        hipLaunchKernelGGL(fq_dup_resolve_kernel, dim3(std::max(1, (l.n + 1023) / 1024)), dim3(1024), 16, st, d);
-        HIP_TRY(ctx, hipGetLastError());
-        return 0;
-    }
     HIP_TRY(ctx, hipMemsetAsync(d.cfilter, 0, (size_t)1 << (DUP_CF_LOG2 - 3), st));
     return dup_decide(l, d, false, st);
 }
@@ -1627,21 +1594,6 @@ static int launch_per_read(Launch& l) {
         la.k = a;
         la.k.slabs = ctx->d_ln_slabs;
         la.k.slab_dwords = ctx->ln_lds.n_misc;
-        // the chunks no workgroup owns (LaneArgs::pool)
-        // A/B, off: profiles/r06_x_lane_chunk_pool_ab.txt, r06_y_*: an 8th of the chunks -2 %, a 16th 0, a 32nd .. a 128th +0.2 % on the
-        // headline (noise), the single-end lines, -c and configs[4] 0.4 - 2 % SLOWER - the CUs' equal shares already end
-        // together; the asks of the pool cost what little imbalance there is
-        const int lg = ctx->sw.lane_pool_log2;
-        const int chunks = (n + 63) >> 6;
-        la.pool = lg > 0 && lg < 31 ? chunks >> lg : 0;
-        if (ctx->ln_pool_base > 0x60000000) {   // (the counter only counts up: back to zero long before it could wrap)
-            HIP_TRY(ctx, hipMemsetAsync(la.chunk_ctr, 0, sizeof(int), st));
-            ctx->ln_pool_base = 0;
-        }
-        la.pool_base = ctx->ln_pool_base;
-        la.pool_grab = std::max(1, la.pool >> 11);   // at most ~2 k asks per launch
-        // every wavefront asks once more than it gets: the counter ends at most (asks that get chunks) + wavefronts beyond the base
-        ctx->ln_pool_base += (la.pool + la.pool_grab - 1) / la.pool_grab + ctx->ln_blocks * (ctx->ln_threads >> 6) + 64;
         const int Bh = (ctx->dp.dup_enabled && (a.dup_pos || a.claim_won) && !(a.debug_skip & 2u)) ? ctx->dp.dup_bufnum : 0;
         lane_kernel_fn fn = lane_kernel_for(ctx->ln_swm, Bh, ctx->dp.paired != 0, lane_ext(ctx->dp));
         l.ln_grid = std::max(1, std::min(ctx->ln_blocks, (n + 255) / 256));

@@ -2510,10 +2510,8 @@ FQ_DEV void reduce_body(const ReduceArgs& r) {
 //   pair g is a duplicate  <=>  for every buffer i the bit pos_i(g) was set by a
 //   pair with a smaller index (in an earlier batch: "committed", or earlier in
 //   this batch).
-// probe  : read the committed bitmaps; pairs with a missing bit register
-//          (buffer, bit) -> min pair index in an open-addressing table.
-// resolve: a missing bit counts as set iff the table's min index is smaller than
-//          the pair's own; then commit the bits (atomic OR) and count.
+// (claim / winners / finish below; a first form, probe + resolve - four scattered
+// accesses per unit and buffer - is retired)
 // Bitmaps are u32 words: bit `pos` lives in word pos>>5, bit pos&31 (the same bit
 // identity as the reference's byte array: byte pos>>3, bit pos&7).
 // ---------------------------------------------------------------------------
@@ -2527,7 +2525,7 @@ struct DupArgs {
     u64* table;           // open addressing, EMPTY = ~0, entry = key(38 bit) << 25 | pair index
                           // (bit 63 of a real entry is always 0, so it never equals EMPTY)
     int table_log2;
-    u8* need;             // [n] mask of buffers whose bit was not committed
+    u8* need;             // [n] mask of buffers whose bit this unit won (it saw the bit clear: dup_claim_body, or the per-read kernel)
     u32* res[2];          // result records (flags byte gets RS_DUP) - used when dupflag == nullptr
     u8* dupflag;          // [n] --dedup: the decision goes here instead (the records do not exist yet)
     int paired;
@@ -2537,7 +2535,6 @@ struct DupArgs {
     // buffers an earlier unit of this stream had set; no decision, no counters
     u64* scan_pos;        // [n][B]
     u8* scan_mask;        // [n]
-    // claim / winners / finish form (dup_claim_body ...)
     u8* setw;             // [n] buffers a unit claimed but that turn out to have had an earlier unit of this launch
     u32* cfilter;         // 2^DUP_CF_LOG2 bits: keys some unit of this launch lost (a one-hash Bloom filter in front of the table)
 };
@@ -2773,94 +2770,8 @@ FQ_DEV u64 dup_bit(const DupArgs& d, int g, int i) {
 FQ_DEV u64 dup_key(int i, u64 pos) { return ((u64)i << 35) | pos; }
 FQ_DEV u32 dup_slot(u64 key, int log2) { return (u32)((key * 0x9E3779B97F4A7C15ull) >> (64 - log2)); }
 
-FQ_DEV void dup_probe_body(const DupArgs& d) {
-    const int gid = block_id() * block_threads() + thread_id();
-    const int gstride = grid_blocks() * block_threads();
-    const u64 words = d.bits >> 5;
-    const u32 tmask = (1u << d.table_log2) - 1u;
-    for (int g = gid; g < d.n; g += gstride) {
-        u32 need = 0;
-        for (int i = 0; i < d.B; i++) {
-            const u64 pos = dup_bit(d, g, i);
-            const u32 w = d.bitmap[(size_t)i * words + (pos >> 5)];
-            if (!((w >> (pos & 31)) & 1u)) {
-                need |= 1u << i;
-                const u64 key = dup_key(i, pos);
-                const u64 entry = (key << DUP_IDX_BITS) | (u64)g;
-                u32 slot = dup_slot(key, d.table_log2);
-                for (;;) {
-                    u64 cur = g_atomic_cas_u64(&d.table[slot], ~0ull, entry);
-                    if (cur == ~0ull) break;              // claimed an empty slot
-                    if ((cur >> DUP_IDX_BITS) == key) {   // same bit: keep the smallest pair index
-                        g_atomic_min_u64(&d.table[slot], entry);
-                        break;
-                    }
-                    slot = (slot + 1) & tmask;
-                }
-            }
-        }
-        d.need[g] = (u8)need;
-    }
-}
-
-FQ_DEV void dup_resolve_body(const DupArgs& d, u32* block_count) {
-    if (thread_id() == 0) *block_count = 0;
-    block_sync();
-    const int gid = block_id() * block_threads() + thread_id();
-    const int gstride = grid_blocks() * block_threads();
-    const u64 words = d.bits >> 5;
-    const u32 tmask = (1u << d.table_log2) - 1u;
-    const int rounds = (d.n + gstride - 1) / gstride;
-    for (int it = 0; it < rounds; it++) {
-        const int g = gid + it * gstride;
-        bool is_dup = false;
-        if (g < d.n) {
-            const u32 need = d.need[g];
-            is_dup = true;
-            u32 set_before = 0;
-            for (int i = 0; i < d.B; i++) {
-                const bool committed = !((need >> i) & 1u);  // by an earlier batch
-                if (committed) set_before |= 1u << i;
-                if (committed && !d.scan_pos) continue;
-                const u64 pos = dup_bit(d, g, i);
-                if (d.scan_pos) d.scan_pos[(size_t)g * d.B + i] = pos;
-                if (committed) continue;
-                const u64 key = dup_key(i, pos);
-                u32 slot = dup_slot(key, d.table_log2);
-                u64 cur;
-                for (;;) {
-                    cur = d.table[slot];
-                    if ((cur >> DUP_IDX_BITS) == key) break;
-                    slot = (slot + 1) & tmask;
-                }
-                const int first = (int)(cur & ((1ull << DUP_IDX_BITS) - 1));
-                if (first < g) set_before |= 1u << i;
-                else is_dup = false;  // nobody earlier in this batch set it
-                g_atomic_or_u32(&d.bitmap[(size_t)i * words + (pos >> 5)], 1u << (pos & 31));
-            }
-            if (d.scan_mask) {
-                d.scan_mask[g] = (u8)set_before;
-                is_dup = false;  // pass 1 decides nothing
-            } else if (d.dupflag) {
-                d.dupflag[g] = is_dup ? 1 : 0;
-            } else if (is_dup) {
-                d.res[0][(size_t)g * 3 + 1] |= (u32)RS_DUP << 8;
-                if (d.paired) d.res[1][(size_t)g * 3 + 1] |= (u32)RS_DUP << 8;
-            }
-        }
-        // one same-address device atomic per WORKGROUP (they serialize at ~10 ns each): lanes -> ballot,
-        // waves -> LDS counter, workgroup -> global
-        const u64 m = ballot(is_dup);
-        if (lane_id() == 0 && m) lds_add_u32(block_count, (u32)popc64(m));
-    }
-    block_sync();
-    if (d.scan_mask) return;
-    if (thread_id() == 0 && *block_count) g_atomic_add_i64(d.ctr_dups, (int64_t)*block_count);
-    if (gid == 0) g_atomic_add_i64(d.ctr_total, (int64_t)d.n);
-}
-
 // ---------------------------------------------------------------------------
-// The same sequential semantics with one scattered atomic per (unit, buffer) instead of four scattered accesses:
+// The sequential semantics with one scattered atomic per (unit, buffer):
 //   claim   : old = atomic_or(bit).  Exactly one unit of the launch sees a clear bit - it WON the bit (in execution
 //             order, which is not input order).  A unit that lost registers (bit -> its index, min) in the table
 //             and marks the key in a small filter; on fresh data almost nobody loses.

@@ -23,14 +23,6 @@
 #ifndef FQ_LANE_STAGE_BATCH
 #define FQ_LANE_STAGE_BATCH 10
 #endif
-#ifndef FQ_LANE_METRICS      // A/B switch: 2 = read 1 from the load sweep's partial sums + the one cut word, the last-staged read straight from the
-#define FQ_LANE_METRICS 2    // stage (default); 0 = round 3's second staging of the quality rows with every dword masked by the window
-#endif
-#ifdef FQ_LANE_NO_FENCE      // A/B switch
-#define FQ_LANE_FENCE() ((void)0)
-#else
-#define FQ_LANE_FENCE() sched_fence()
-#endif
 
 namespace fq {
 
@@ -65,15 +57,6 @@ struct LaneArgs {
     LaneLds l;
     // A workgroup owns a contiguous share of the launch's chunks and hands them to its wavefronts from a counter in ITS LDS
     // (LaneLds::ctr): the balance of a shared counter inside a CU, none of its traffic.
-    int* chunk_ctr; // the pool's counter in HBM (never null)
-    int pool;       // the launch's LAST `pool` chunks belong to no workgroup - a wavefront whose workgroup's share is
-                    // used up takes them one at a time from chunk_ctr (a word that only ever counts up: a chunk's number in the pool
-                    // is what the atomic returns minus pool_base, the host adds `pool` to pool_base per launch - no reset between
-                    // launches).  The shares are equal, the work per chunk is not (overlap verifications, trims): the kernel ended
-                    // when its slowest CU did.  FASTP_GPU_LANE_POOL_LOG2 (0: no pool, the default - measured: no gain; 5: a 32nd of the chunks)
-    int pool_base;
-    int pool_grab;  // chunks per ask of the pool (>= 1): a launch of many small chunks (single-end runs: 156 k of them) would otherwise
-                    // put ten thousand returning atomics on the one word while its last part runs
     // --merge with -c: the POST Stats object of read 1 in the counter block, for the (rare) merged read whose tail holds an edited
     // base - the lane that has the corrected tail in registers counts it itself (lane_merge_tail_slow)
     int64_t* post1;
@@ -363,14 +346,14 @@ FQ_DEV void lane_sweep_quality(const KernelArgs& a, u32* stage, u32* part, int l
         for (int d = 7; d >= 0; d--) {
             const u32 b1 = (q[d] >> 7) & 0x01010101u;   // bits 0, 8, 16, 24
             nw = dot4_u8(b1, 0x08040201u, nw << 4);     // the four flags as a nibble behind the ones gathered so far
-            if (KEEP && FQ_LANE_METRICS == 2) {
+            if (KEEP) {
                 ts = sum_bytes(q[d] & 0x7F7F7F7Fu, ts);
                 gs += (u32)popc32(((q[d] | 0x80808080u) - thr4) & 0x80808080u);
             }
         }
         r.n[W] = nw;
         anyn |= nw;
-        if (KEEP && FQ_LANE_METRICS == 2) part[W * 64 + lane] = ts | (gs << 16);   // sum of the quality characters | bases at or above the qualified quality << 16
+        if (KEEP) part[W * 64 + lane] = ts | (gs << 16);   // sum of the quality characters | bases at or above the qualified quality << 16
         else { (void)ts; (void)gs; (void)part; (void)thr4; }
         // ---- window predicate (bad_window_word of the tile kernel, windows of up to 8 bases) ----
         u32 m = 0;
@@ -378,7 +361,7 @@ FQ_DEV void lane_sweep_quality(const KernelArgs& a, u32* stage, u32* part, int l
         else if (win > 4) m = lane_window_word<true>(q, keep_lo, keep_hi, nthr);
         else if (win > 0) m = lane_window_word<false>(q, keep_lo, keep_hi, nthr);
         r.bad[W] = m;
-        FQ_LANE_FENCE();   // one mask word at a time: the scheduler would otherwise keep every word's dwords in flight
+        sched_fence();   // one mask word at a time: the scheduler would otherwise keep every word's dwords in flight
     }
     if (anyn) r.flags |= RS_HAS_N;
 }
@@ -559,7 +542,7 @@ FQ_DEV void lane_scan(const u32 (&X)[SWM], u32 y0, int nvalid, u32 premask, u32 
             if (left < 16) cand = left <= 0 ? 0u : (cand & ~lowmask32(16 - left));
             cm[b >> 1] |= cand << (16 * (b & 1));
         }
-        FQ_LANE_FENCE();
+        sched_fence();
     }
 }
 // smallest candidate offset left in cm (removed from it), or -1
@@ -1020,34 +1003,6 @@ FQ_DEV int lane_adjacent_diffs(const LaneRead<SWM>& r, int len) {
     return cnt;
 }
 
-// round 3's form (FQ_LANE_METRICS == 0): the mate's quality rows are staged once more and every dword masked by the window
-template <int SWM>
-FQ_DEV void lane_metrics_staged(const KernelArgs& a, u32* stage, const u32* qual, int chunk0, int rows, int lane, int len, int& tot, int& low, int& nb) {
-    const int qwg = a.p.qw_g;
-    lane_stage_rows<FQ_LANE_STAGE_BATCH>(stage, qual + (size_t)chunk0 * qwg, rows, qwg, lane);
-    const u64* qrow = (const u64*)(stage + lane * qwg);
-    const u32 thr4 = (u32)a.p.qual_thr * 0x01010101u;
-    u32 t = 0, lo = 0, n = 0;
-#pragma unroll
-    for (int c = 0; c < 4 * SWM; c += 2) {
-        const u64 v = qrow[c >> 1];
-#pragma unroll
-        for (int hlf = 0; hlf < 2; hlf++) {
-            const u32 qd = hlf ? (u32)(v >> 32) : (u32)v;
-            const int rem = len - 4 * (c + hlf);
-            const u32 M = rem >= 4 ? 0xFFFFFFFFu : (rem <= 0 ? 0u : lowmask32(8 * rem));
-            const u32 q7 = qd & 0x7F7F7F7Fu & M;
-            const u32 ge = ((q7 | 0x80808080u) - thr4) & 0x80808080u;
-            t = sum_bytes(q7, t);
-            lo += (u32)popc32(~ge & 0x80808080u & M);
-            n += (u32)popc32(qd & 0x80808080u & M);
-        }
-    }
-    tot = (int)t - 33 * len;
-    low = (int)lo;
-    nb = (int)n;
-}
-
 // ---------------------------------------------------------------------------
 // BaseCorrector::correctByOverlapAnalysis (basecorrector.cpp:16-83) with both reads in registers (-c on the lane plan, round 5).
 // The mismatch positions of the accepted overlap come from the same XOR words as the verification; they are taken one per
@@ -1101,9 +1056,6 @@ FQ_DEV void lane_emit_corrections(const KernelArgs& a, int lane, int gp, int whi
     if (which >= 0 && base + rank < a.corr_int_cap) { a.corr_int[2 * (base + rank)] = w0; a.corr_int[2 * (base + rank) + 1] = w1; }
     if (a.corrections && which >= 0 && cb + rank < a.corr_capacity) { a.corrections[2 * (cb + rank)] = w0; a.corrections[2 * (cb + rank) + 1] = w1; }
 }
-#ifndef FQ_CORR_FLUSH
-#define FQ_CORR_FLUSH 1   // (A/B: 0 = a list entry per round)
-#endif
 // The same for a whole chunk: a lane keeps its first two edits (the list's second word each; which read: bits 2 / 3 of `st`, how
 // many: its low two bits) and the wavefront takes the slots of all of them with ONE atomic per list when the rounds are over.
 // Measured on the -c line (profiles/r06_l_corr_rounds_ablation.txt): the per-round form - a ballot, a returning atomic per
@@ -1239,16 +1191,16 @@ FQ_DEV void lane_correct(const KernelArgs& a, u32* misc, LaneRead<SWM>& r1, Lane
         if (ballot(pi[t] >= 0) == 0ull) break;
         em_which = -1;
         if (pi[t] >= 0 && !(abl & 2048u)) edit(pi[t], pq[t]);
-        if (!(abl & 1024u)) { if (FQ_CORR_FLUSH) record(); else lane_emit_corrections(a, lane, gp, em_which, em_pos, em_nb, em_nq); }
+        if (!(abl & 1024u)) record();
     }
     for (;;) {
         const int i = next_mismatch();
         if (ballot(i >= 0) == 0ull) break;
         em_which = -1;
         if (i >= 0 && !(abl & 2048u)) edit(i, (u32)q1row[fr1 + o1 + i] & 0x7Fu);
-        if (!(abl & 1024u)) { if (FQ_CORR_FLUSH) record(); else lane_emit_corrections(a, lane, gp, em_which, em_pos, em_nb, em_nq); }
+        if (!(abl & 1024u)) record();
     }
-    if (FQ_CORR_FLUSH) lane_flush_corrections(a, lane, gp, rec_st, rec0, rec1);
+    lane_flush_corrections(a, lane, gp, rec_st, rec0, rec1);
     if (corrected > 0) {                                           // :75-80
         lds_add_u32(&misc[MISC_CORRECTED_READS], (r1c && r2c) ? 2u : 1u);
         if (r1c) r1.flags |= RS_CORRECTED;
@@ -1461,19 +1413,6 @@ FQ_DEV void lane_merge_tail_slow(const LaneArgs& la, const LaneRead<SWM>& r2, co
 // ---------------------------------------------------------------------------
 // EXT: the option family with adapter sequences, polyX trimming or the complexity filter - a second instantiation, so that
 // the registers those steps need (+30) are not taken from the kernel of the options that do not use them
-// a chunk of the pool (LaneArgs::pool): its number is what the counter returns minus the launch's base.  The base is where the counter
-// CAN be at most when the launch starts (the host adds the pool and one ask per wavefront per launch); where fewer wavefronts asked, the
-// first askers of the next launch get numbers below its base and ask again.
-FQ_DEV int lane_pool_take(const LaneArgs& la, int lane) {
-    int gx;
-    do {
-        gx = 0;
-        if (lane == 0) gx = g_atomic_add_i32(la.chunk_ctr, 1) - la.pool_base;
-        gx = (int)shfl((u32)gx, 0);
-    } while (gx < 0);   // (wave-uniform)
-    return gx;
-}
-
 template <int SWM, int B, int NPL, bool PAIRED, int EXT>
 FQ_DEV void lane_body(const LaneArgs& la, u32* lds) {
     const KernelArgs& a = la.k;
@@ -1523,28 +1462,13 @@ FQ_DEV void lane_body(const LaneArgs& la, u32* lds) {
     const u32 thr4 = (u32)p.qual_thr * 0x01010101u;
     const int chunks = (a.n + 63) >> 6;
     const int wpb = nt >> 6;
-    int nx = 0;
     // the workgroup's share of the chunks: the first (chunks % workgroups) workgroups take one more
-    const int pool = imin(la.pool, chunks);   // (uniform) the chunks behind the workgroups' shares
-    const int shared = chunks - pool;
-    const int pg = imax(1, la.pool_grab), pgroups = (pool + pg - 1) / pg;
-    const int sq = shared / grid_blocks(), sr = shared - sq * grid_blocks();
+    const int sq = chunks / grid_blocks(), sr = chunks - sq * grid_blocks();
     const int share_lo = block_id() * sq + imin(block_id(), sr);
     const int share_hi = share_lo + sq + (block_id() < sr ? 1 : 0);
-    int chunk_end = share_lo + (tid >> 6) + 1;   // (the range in hand: [chunk, chunk_end))
-    int chunk0 = chunk_end - 1;
-    bool in_pool = false;                                       // (uniform)
-    if (pool && chunk0 >= share_hi) {                           // a share smaller than the workgroup: straight to the pool
-        const int gx = lane_pool_take(la, lane);
-        in_pool = true;
-        chunk0 = gx < pgroups ? shared + gx * pg : chunks;
-        chunk_end = imin(chunk0 + pg, chunks);
-    }
-    for (int chunk = chunk0; chunk < (in_pool ? chunks : share_hi);) {       // wave-uniform
-        const bool last_in_hand = chunk + 1 == chunk_end;
-        if (in_pool) {   // (the pool's next range is asked for here as well, when the one in hand ends with this chunk)
-            if (last_in_hand && lane == 0) nx = g_atomic_add_i32(la.chunk_ctr, 1) - la.pool_base;
-        } else if (lane == 0) nx = (int)lds_add_ret_u32(&lds[ll.ctr], 1u);   // the workgroup's next chunk, looked at at the loop's end
+    for (int chunk = share_lo + (tid >> 6); chunk < share_hi;) {       // wave-uniform
+        int nx = 0;
+        if (lane == 0) nx = (int)lds_add_ret_u32(&lds[ll.ctr], 1u);   // the workgroup's next chunk, looked at at the loop's end
         const int gp = chunk * 64 + lane;
         const bool valid = gp < a.n;
         const int rows = imin(64, a.n - chunk * 64);
@@ -1794,12 +1718,6 @@ FQ_DEV void lane_body(const LaneArgs& la, u32* lds) {
         int tot1 = 0, low1 = 0, nb1 = 0, tot2 = 0, low2 = 0, nb2 = 0;
         // (--merge: a pair that merges is filtered as its merged read - the two parts' metrics add up, peprocessor.cpp:524-526)
         const int ml1 = (MG && mov) ? m1 : r1.len, ml2 = (MG && mov) ? m2 : (PAIRED ? r2.len : 0);
-#if FQ_LANE_METRICS == 0
-        if (!(skip & 8u)) {
-            lane_metrics_staged<SWM>(a, stage, a.qual[0], chunk * 64, rows, lane, r1.len, tot1, low1, nb1);
-            if (PAIRED) lane_metrics_staged<SWM>(a, stage, a.qual[1], chunk * 64, rows, lane, r2.len, tot2, low2, nb2);
-        }
-#else
         if (!(skip & 8u)) {
             const u32* row = stage + lane * p.qw_g;   // the quality row of the read that was staged last
             if (FR) {   // (uniform) the windows start at the reads' fronts
@@ -1821,7 +1739,6 @@ FQ_DEV void lane_body(const LaneArgs& la, u32* lds) {
                 lane_metrics_stage<SWM>(a, row, r1, r1.len, tot1, low1, nb1);
             }
         }
-#endif
         if (CR && !(skip & 8u) && ballot((geom & 1) != 0) != 0ull)   // read 1's edited positions inside its final window
             lane_apply_corrected<SWM>(a, clist, lane, geom, (const u8*)(a.qual[0] + (size_t)g * p.qw_g), (const u8*)(stage + lane * p.qw_g), fr1, fr2, ml1,
                                       tot1, low1);
@@ -1922,18 +1839,7 @@ FQ_DEV void lane_body(const LaneArgs& la, u32* lds) {
                 if (claim) a.claim_won[g] = (u8)won;
             }
         }
-        // the next chunk: the range in hand, then the counter's next one
-        if (in_pool && !last_in_hand) chunk++;
-        else {
-            if (!in_pool) { chunk = share_lo + wpb + (int)shfl((u32)nx, 0); chunk_end = chunk + 1; }
-            if (pool && (in_pool || chunk >= share_hi)) {   // the share is used up: the pool's next chunks (a global atomic, few of them)
-                int gx = in_pool ? (int)shfl((u32)nx, 0) : -1;   // (asked for at the loop's head; the first one here)
-                if (gx < 0) gx = lane_pool_take(la, lane);
-                in_pool = true;
-                chunk = gx < pgroups ? shared + gx * pg : chunks;
-                chunk_end = imin(chunk + pg, chunks);
-            }
-        }
+        chunk = share_lo + wpb + (int)shfl((u32)nx, 0);   // the counter's next one
     }
     block_sync();
     u32* slab = a.slabs + (size_t)block_id() * a.slab_dwords;

@@ -45,15 +45,13 @@ def test_sim_records_and_counters_equal_oracle(name):
     assert np.array_equal(co, cg), f"{name}: {int((co != cg).sum())} counters differ"
 
 
-@pytest.mark.parametrize("name,table", [("pe_noadapter_dedup", 0), ("pe_default", 0), ("se_default_noadapter", 0), ("pe_noadapter_dedup", 1)])
-def test_sim_duplicates_when_workgroups_run_out_of_order(name, table, monkeypatch):
+@pytest.mark.parametrize("name", ["pe_noadapter_dedup", "pe_default", "se_default_noadapter"])
+def test_sim_duplicates_when_workgroups_run_out_of_order(name, monkeypatch):
     """Duplicate's decision must not depend on which unit reaches a bloom bit first: the emulator runs the workgroups last
     to first, so the unit that wins a bit is usually NOT the first in input order (the winners / finish kernels have to
-    flip it); many planted duplicates, several launches.  table=1: the first (probe / resolve) form of the kernels."""
+    flip it); many planted duplicates, several launches."""
     monkeypatch.setenv("FASTP_SIM_REVERSE_BLOCKS", "1")
     monkeypatch.setenv("FASTP_GPU_MAX_TILES_PER_BLOCK", "2")
-    if table:
-        monkeypatch.setenv("FASTP_GPU_DUP_TABLE", "1")
     paired, flags, pf, skw = cases.CASES[name]
     d = synth.synth_pairs(2400, L=150, seed=31, paired=paired, **skw)
     rng = np.random.default_rng(32)     # exact copies of earlier units (sequencing noise makes the generator's own rare)
@@ -89,30 +87,6 @@ def test_sim_dedup_without_the_fused_claim(switch, monkeypatch):
     for k in range(3):
         assert np.array_equal(ro[k], rg[k]), f"records {k} differ"
     assert np.array_equal(co, cg)
-
-
-@pytest.mark.parametrize("name,log2", [("pe_default", 1), ("pe_default", 2), ("se_default_noadapter", 1), ("pe_correction", 1), ("pe_noadapter_dedup", 2)])
-def test_sim_lane_chunk_pool(name, log2, monkeypatch):
-    """the lane kernel's chunks behind the workgroups' shares (LaneArgs::pool: taken from a global counter that only counts up, its
-    base moved on by the host per launch): half / a quarter of a launch's chunks in the pool, three launches on one context - every
-    unit exactly once (records, counters), whatever the counter's state between launches"""
-    monkeypatch.setenv("FASTP_GPU_LANE_POOL_LOG2", str(log2))
-    paired, flags, pf, skw = cases.CASES[name]
-    d = synth.synth_pairs(2600, L=150, seed=61, paired=paired, **skw)
-    params = cases.finalize_params(name, pf(150), d["seq1"], d["len1"], d.get("seq2"), d.get("len2"))
-    o = oraclelib.Oracle(params)
-    g = engines.sim_engine(params)
-    assert g.plan() == "lane"
-    for lo, hi in ((0, 1100), (1100, 1200), (1200, 2600)):
-        args = tuple(d[k][lo:hi] for k in (("seq1", "qual1", "len1", "seq2", "qual2", "len2") if paired else ("seq1", "qual1", "len1")))
-        ro, rg = o.process(*args), g.process(*args)
-        for k in range(3):
-            if ro[k] is not None:
-                assert np.array_equal(ro[k], rg[k]), f"{name}: records {k} of units [{lo}, {hi}) differ"
-    co, cg = o.counters(), g.counters()
-    o.close()
-    g.close()
-    assert np.array_equal(co, cg), f"{name}: {int((co != cg).sum())} counters differ"
 
 
 def test_sim_overrep_with_correction_reads_the_engines_own_list():

@@ -32,7 +32,6 @@ CASES = {
     "pe_default_tile": ("pe_default", TILE, {}),
     "pe_default_fused": ("pe_default", FUSED, {}),
     "pe_default_unaligned": ("pe_default", {}, {"unaligned": True}),             # rows off 16 bytes: the tile kernel instead of the lane kernel
-    "pe_dup_table": ("pe_default", {"FASTP_GPU_DUP_TABLE": "1"}, {}),
     "pe_claim_own_kernel": ("pe_default", {"FASTP_GPU_CLAIM_FUSED": "0"}, {}),
     "pe_c_dedup3": ("pe_c_dedup3", {}, {}),                                      # --dedup folded
     "pe_c_dedup3_prepass": ("pe_c_dedup3", {"FASTP_GPU_DEDUP_FOLD": "0"}, {}),   # the hash pre-pass

@@ -1,4 +1,4 @@
-"""the two forms of the Duplicate kernels (probe/resolve table form vs claim/winners/finish, in-kernel claim) on the same
+"""Duplicate's claim inside the per-read kernel vs as its own kernel (FASTP_GPU_CLAIM_FUSED=0) on the same
 stream of batches: every counter and every RF_DUP flag must be identical.  python tools/dup_forms_check.py [batches] [pairs]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -44,11 +44,9 @@ def run(env):
     return ctr, flags
 
 c_new, f_new = run({})
-c_tab, f_tab = run({"FASTP_GPU_DUP_TABLE": "1"})
 c_ker, f_ker = run({"FASTP_GPU_CLAIM_FUSED": "0"})
 print("duplicates flagged per batch (in-kernel claim):", [int((f != 0).sum()) for f in f_new])
-for name, c, f in (("table form", c_tab, f_tab), ("claim kernel", c_ker, f_ker)):
-    same_c = np.array_equal(c_new, c)
-    same_f = all(np.array_equal(a, b) for a, b in zip(f_new, f))
-    print(f"in-kernel claim vs {name}: counters identical {same_c}, RF_DUP flags identical {same_f}")
-    assert same_c and same_f
+same_c = np.array_equal(c_new, c_ker)
+same_f = all(np.array_equal(a, b) for a, b in zip(f_new, f_ker))
+print(f"in-kernel claim vs claim kernel: counters identical {same_c}, RF_DUP flags identical {same_f}")
+assert same_c and same_f
