@@ -70,20 +70,20 @@ extern "C" __global__ void __launch_bounds__(1024, 8) fq_stats_kernel(StatsArgs 
     else if (a.kc == 2) stats_body4<2, false>(a, fq_lds);
     else stats_body4<1, false>(a, fq_lds);
 }
-// form 5 of the Stats kernel (fq_stats5.h): one 1024-lane workgroup per CU that owns the joint table (110 KB at ten item columns)
-extern "C" __global__ void __launch_bounds__(1024) fq_stats5_kernel(StatsArgs a) {
+// form 5 of the Stats kernel (fq_stats5.h): one 1024-lane workgroup per CU that owns the joint table (110 KB at ten item columns).
+// A kernel per instantiation of stats_body5 (the host picks one, stats5_inst_for): a kernel is allocated the registers of its
+// greediest branch, and as ONE kernel with six branches every launch paid the 128 VGPRs of the ONE / front-trim form - four waves
+// per SIMD x 128 = the whole register file, no wave of the tail stream's small kernels got in beside it.  Alone the ONE / no-front
+// form (the 2x150 default) takes 118 -> 120: 32 registers per SIMD stay free, a wave of the MISC fold or of Duplicate's losers /
+// winners (28 / 22 / 25 VGPRs) fits beside the four.
+template <int KC, int HS, bool ABL, bool ONE, bool NF>
+__global__ void __launch_bounds__(1024) fq_st5_kernel(StatsArgs a) {
     extern __shared__ __attribute__((aligned(16))) u32 fq_lds[];
-#ifdef FQ_PROFILE_ABLATION
-    if ((a.debug_skip & 0xC0u) && a.Hs == 10 && a.kc == 2) { stats_body5<2, 10, true>(a, fq_lds); return; }   // profiling build only
-#endif
-    const bool nofront = !a.front_per_read && a.front[0] == 0 && a.front[1] == 0;   // (uniform)
-    if (a.Hs == 10 && a.kc == 2 && a.H16 <= 10 && nofront) stats_body5<2, 10, false, true, true>(a, fq_lds);   // reads of up to 160 bases, no front trim
-    else if (a.Hs == 10 && a.kc == 2 && a.H16 <= 10) stats_body5<2, 10, false, true>(a, fq_lds);   // reads of up to 160 bases (uniform)
-    else if (a.Hs == 10 && a.kc == 2) stats_body5<2, 10, false>(a, fq_lds);
-    else if (a.Hs == 8 && a.kc == 2) stats_body5<2, 8, false>(a, fq_lds);  // two blocks of eight columns: reads of up to 256 bases
-    else if (a.kc == 2) stats_body5<2, 0, false>(a, fq_lds);
-    else stats_body5<1, 0, false>(a, fq_lds);
+    stats_body5<KC, HS, ABL, ONE, NF>(a, fq_lds);
 }
+typedef void (*stats5_kernel_fn)(StatsArgs);
+// the instantiations the host selects among (fastp_gpu_debug_kernel_regs reports the id)
+enum { ST5_ONE_NF = 0, ST5_ONE = 1, ST5_BLOCKS10 = 2, ST5_BLOCKS8 = 3, ST5_ANY_KC2 = 4, ST5_ANY_KC1 = 5, ST5_ABLATION = 6 };
 // Do two streams run BESIDE each other?  HIP hands a stream one of a few hardware queues when it is created; two streams of one
 // engine can land on the same queue (other engines, torch's and the caller's streams hold the others) and then run one behind the
 // other whatever the events between them say - the kernels the engine puts beside the lane / Stats kernels on its second stream (the
@@ -288,6 +288,7 @@ struct fastp_gpu_ctx {
     u32* d_corr_int = nullptr; size_t corr_int_cap = 0;      // -c on the lane plan: the launch's corrections (KernelArgs::corr_int) + 1 counter word
     u32* d_corr_chain = nullptr; size_t corr_chain_cap = 0;  // their per-read chains: head[reads] | next[capacity]
     int st_form = 4, st_max_reads = CYC_MAX_READS, st_max_grid = 0;   // the Stats kernel's form: 5 (fq_stats5.h) where it fits, else 4 (fq_stats.h)
+    stats5_kernel_fn st5_fn = nullptr; int st5_inst = -1;   // form 5: the instantiation this context launches (stats5_inst_for), chosen at create
     // Argument blocks with their constant part filled once (fill_arg_templates, at the end of fastp_gpu_create): a launch copies the
     // block and sets what differs per launch - pointers, n, first, units per block, debug_skip.  The Stats kernel's geometry (H, Hs,
     // kc, H16, its LDS offsets) lives in t_stats only: create's sizing writes it there.
@@ -493,6 +494,32 @@ static int stats5_copies(const DevParams& p, int lds_bytes, int* hb_out = nullpt
     }
     return 0;
 }
+// which instantiation of form 5 a context launches: everything it depends on is fixed at fastp_gpu_create (the table's columns
+// and copies, the reads' columns, whether any front trim exists).  ONE: the table holds every column of the reads; NF: no front
+// trim of any kind, no result record read.
+static int stats5_inst_for(int Hs, int kc, int H16, bool nofront) {
+    if (Hs == 10 && kc == 2 && H16 <= 10) return nofront ? ST5_ONE_NF : ST5_ONE;   // reads of up to 160 bases
+    if (Hs == 10 && kc == 2) return ST5_BLOCKS10;
+    if (Hs == 8 && kc == 2) return ST5_BLOCKS8;    // two blocks of eight columns: reads of up to 256 bases
+    return kc == 2 ? ST5_ANY_KC2 : ST5_ANY_KC1;
+}
+static stats5_kernel_fn stats5_kernel_for(int inst) {
+    switch (inst) {
+        case ST5_ONE_NF: return fq_st5_kernel<2, 10, false, true, true>;
+        case ST5_ONE: return fq_st5_kernel<2, 10, false, true, false>;
+        case ST5_BLOCKS10: return fq_st5_kernel<2, 10, false, false, false>;
+        case ST5_BLOCKS8: return fq_st5_kernel<2, 8, false, false, false>;
+        case ST5_ANY_KC2: return fq_st5_kernel<2, 0, false, false, false>;
+        case ST5_ANY_KC1: return fq_st5_kernel<1, 0, false, false, false>;
+#ifdef FQ_PROFILE_ABLATION
+        case ST5_ABLATION: return fq_st5_kernel<2, 10, true, false, false>;   // profiling build only (FASTP_GPU_DEBUG_SKIP)
+#endif
+    }
+    return nullptr;
+}
+static bool stats5_no_front(const DevParams& p) {
+    return !p.front_per_read && !(p.front_lane && (p.lane_front1 != 0 || p.lane_front2 != 0));
+}
 static bool lane_plan_supported(const DevParams& p, const HostLuts& luts, int lds_bytes) {
     if (p.front_per_read && !stats5_copies(p, lds_bytes)) return false;   // a front per read: form 5 of the Stats kernel only
     if (!(p.stats_one_pass || p.front_lane || p.corr_lane || p.merge_lane) || p.allow_gap || p.overlapped_out) return false;
@@ -593,6 +620,9 @@ static void fill_arg_templates(fastp_gpu_ctx* ctx) {
     cs.front[0] = dp.front_lane ? dp.lane_front1 : 0; cs.front[1] = dp.front_lane ? dp.lane_front2 : 0;
     cs.st_qual_hist = cl.st_qual_hist; cs.st_kmer = cl.st_kmer; cs.st_cycle = cl.st_cycle; cs.cycles = cl.cycles;
 }
+
+enum { KERNEL_REGS_N = 16 };
+extern "C" int fastp_gpu_debug_kernel_regs(fastp_gpu_ctx* ctx, int32_t* out, int32_t n);   // (below, next to the other debugging aid)
 
 extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fastp_gpu_ctx** out) {
     if (!params || !out) return fail(nullptr, FASTP_GPU_E_INVALID, "null argument");
@@ -704,6 +734,8 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
             ctx->st_form = 5;
             sa.kc = kc5;
             sa.Hs = hb;                     // the table's columns: all of a read's (H16), or a block of them
+            ctx->st5_inst = stats5_inst_for(sa.Hs, sa.kc, sa.H16, stats5_no_front(ctx->dp));
+            ctx->st5_fn = stats5_kernel_for(ctx->st5_inst);
             ctx->st_lds_dwords = o;
             ctx->st_max_reads = CYC_MAX_READS;   // (a list entry holds the trip in 10 bits: 16 wavefronts x (64 / hb >= 4) units per trip, <= 256 trips)
         } else {
@@ -867,7 +899,12 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
                                            (int)((ctx->dp.paired ? 2 : 1) * (33 * (size_t)ctx->cl.cycles + 128 + KMER_BINS) * 4)));
         // a slab per workgroup of the largest launch: rounds of st_blocks for form 4, two rounds for form 5
         ctx->st_max_grid = ctx->st_form == 4 ? (ctx->max_pairs_per_launch + ST4_MAX_READS - 1) / ST4_MAX_READS + ctx->st_blocks : 2 * ctx->st_blocks + 2;
-        if (ctx->st_form == 5) CREATE_TRY(hipFuncSetAttribute((const void*)fq_stats5_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->st_lds_dwords * 4));
+        if (ctx->st_form == 5) {
+            CREATE_TRY(hipFuncSetAttribute((const void*)ctx->st5_fn, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->st_lds_dwords * 4));
+#ifdef FQ_PROFILE_ABLATION
+            CREATE_TRY(hipFuncSetAttribute((const void*)stats5_kernel_for(ST5_ABLATION), hipFuncAttributeMaxDynamicSharedMemorySize, ctx->st_lds_dwords * 4));
+#endif
+        }
         CREATE_TRY(hipMalloc((void**)&ctx->d_st_slabs, (size_t)ctx->st_max_grid * ctx->st_slab_dwords * 4));
 #ifdef FQ_HOSTSIM
         CREATE_TRY(hipStreamCreateWithFlags(&ctx->tail, hipStreamNonBlocking));
@@ -963,6 +1000,22 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
     }
     CREATE_TRY(hipStreamSynchronize(ctx->stream));
     fill_arg_templates(ctx);
+#ifndef FQ_HOSTSIM
+    if (sw.verbose && ctx->split && ctx->st_form == 5) {   // what stays free beside the Stats kernel's waves, and for whom
+        int32_t kr[KERNEL_REGS_N];
+        CREATE_RC(fastp_gpu_debug_kernel_regs(ctx, kr, KERNEL_REGS_N));
+        const int waves = ctx->st_threads / 64 / 4, alloc = (kr[1] + 7) & ~7, left = 512 - waves * alloc;
+        const char* names[4] = {"fq_reduce_kernel", "fq_dup_losers_kernel", "fq_dup_winners_kernel", "fq_dup_finish_kernel"};
+        std::string fits;
+        for (int k = 0; k < 4; k++) {   // a workgroup of the kernel (its launch bound: 256 lanes = a wave per SIMD, 1024 = four) in what is left
+            const int a8 = (kr[4 + 3 * k] + 7) & ~7, wg_waves = std::max(1, kr[5 + 3 * k] / 64 / 4);
+            if (a8 * wg_waves <= left)
+                fits += std::string(fits.empty() ? "" : ", ") + names[k] + " (" + std::to_string(wg_waves) + " x " + std::to_string(a8) + ")";
+        }
+        fprintf(stderr, "fastp_gpu: stats kernel instantiation %d: %d VGPRs (allocated %d), %d waves per SIMD, %d registers per SIMD left; a workgroup fits beside it of: %s\n",
+                ctx->st5_inst, kr[1], alloc, waves, left, fits.empty() ? "none" : fits.c_str());
+    }
+#endif
     fq::timeline("create: end (tables uploaded, bloom filter cleared)");
     return FASTP_GPU_OK;
 }
@@ -974,6 +1027,29 @@ extern "C" int fastp_gpu_debug_phase_cycles(fastp_gpu_ctx* ctx, uint64_t* out16)
     HIP_TRY(ctx, hipDeviceSynchronize());
     HIP_TRY(ctx, hipMemcpy(out16, ctx->d_phase, 16 * sizeof(u64), hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemset(ctx->d_phase, 0, 16 * sizeof(u64)));
+    return FASTP_GPU_OK;
+}
+
+// debugging aid: what the runtime allocates the Stats kernel this context launches and the tail stream's small kernels -
+// out[0] the instantiation of form 5 (ST5_*; -1: form 4), then {VGPRs, max threads per workgroup, static LDS bytes} of the
+// Stats kernel, fq_reduce_kernel, fq_dup_losers_kernel, fq_dup_winners_kernel, fq_dup_finish_kernel.  Whether a wave of a tail
+// kernel fits beside the Stats kernel's four per SIMD is arithmetic on these (granules of 8 of a 512-entry file per SIMD).
+// The emulator has no such attributes: zeros behind out[0].
+extern "C" int fastp_gpu_debug_kernel_regs(fastp_gpu_ctx* ctx, int32_t* out, int32_t n) {
+    if (!ctx || !out || n < KERNEL_REGS_N) return FASTP_GPU_E_INVALID;
+    for (int i = 0; i < n; i++) out[i] = 0;
+    out[0] = ctx->split && ctx->st_form == 5 ? ctx->st5_inst : -1;
+#ifndef FQ_HOSTSIM
+    const void* fns[5] = {ctx->st_form == 5 && ctx->st5_fn ? (const void*)ctx->st5_fn : (const void*)fq_stats_kernel, (const void*)fq_reduce_kernel,
+                          (const void*)fq_dup_losers_kernel, (const void*)fq_dup_winners_kernel, (const void*)fq_dup_finish_kernel};
+    for (int k = 0; k < 5; k++) {
+        hipFuncAttributes fa;
+        HIP_TRY(ctx, hipFuncGetAttributes(&fa, fns[k]));
+        out[1 + 3 * k] = fa.numRegs;
+        out[2 + 3 * k] = fa.maxThreadsPerBlock;
+        out[3 + 3 * k] = (int32_t)fa.sharedSizeBytes;
+    }
+#endif
     return FASTP_GPU_OK;
 }
 
@@ -1175,6 +1251,9 @@ struct LaunchPlan {
     //   dedup_apply behind it
     // DUP_ON_TAIL: the claim ran inside the per-read kernel: what is left of Duplicate (losers / winners / finish) needs nothing of
     //   the Stats kernel and runs beside it on its own stream; the launch stream joins it before anything else touches the records.
+    //   (Beside it as far as the Stats kernel's registers leave room - misc_fold below: losers' and winners' 256-lane workgroups fit
+    //   next to the instantiations without a front trim; finish's 1024-lane workgroup, four waves per SIMD, never does and runs
+    //   when the Stats kernel's workgroups leave, beside the Stats fold.)
     //   Or: behind the text kernel, on its stream (the claim is not fused into a launch that has such units inline or behind).
     // DUP_AT_END: on the launch stream behind the folds (the fused plan; the forms that do not use the tail stream)
     DupPlace dup_place = DUP_NOWHERE;
@@ -1183,12 +1262,16 @@ struct LaunchPlan {
     // the slab folds.  The Stats fold: behind the Stats kernel on the launch stream.  The per-read kernel's MISC_* fold needs that
     // kernel only:
     // MISC_WITH_STATS: the fused plan has one set of slabs, one fold
-    // MISC_FIRST_ON_TAIL: FIRST on the tail stream.  The Stats kernel's workgroups own every CU (a 1024-lane workgroup at 128 VGPRs is
-    //   the whole register file): a kernel on the tail stream gets through when one of the Stats kernel's two rounds of workgroups
-    //   ends, ONE kernel per such moment (profiles/r06_s_step_timeline.txt, r06_t_step_timeline.txt: each tail kernel "takes" 0.43 -
-    //   0.50 ms, 0.01 - 0.03 alone).  Behind Duplicate's kernels - which the Stats kernel's workgroups starve until its last round
-    //   ends (profiles/r06_s_step_timeline.txt: losers 0.45 ms, winners 0.50 ms beside it, 0.01 / 0.03 alone) - it was 27 + 9 us at
-    //   the very end of every step, with nothing else on the chip.
+    // MISC_FIRST_ON_TAIL: FIRST on the tail stream, in front of Duplicate's kernels.  How much of that stream runs BESIDE the Stats
+    //   kernel is a matter of registers: its 1024-lane workgroup is four waves per SIMD, and where the launched instantiation is
+    //   allocated 128 VGPRs (form 5 with a front trim; all of form 5 while it was one kernel with every instantiation as a branch)
+    //   that is the whole 512-entry file - a tail kernel gets through when one of the Stats kernel's two rounds of workgroups ends,
+    //   ONE kernel per such moment (profiles/r06_s_step_timeline.txt, r06_t_step_timeline.txt: each "takes" 0.43 - 0.50 ms, 0.01 -
+    //   0.03 alone), and the rest of the chain is the end of the step with nothing else on the chip.  The instantiations without a
+    //   front trim leave room (120 of 128 at the 2x150 default: 32 registers per SIMD, a 256-lane workgroup of this fold, of losers
+    //   or of winners per CU; ~100 for the general forms) and the chain runs through while the Stats kernel does
+    //   (profiles/r07_a_step_timeline.txt; fastp_gpu_debug_kernel_regs and FASTP_GPU_VERBOSE's line at create say what fits).
+    //   The order stays: behind Duplicate's kernels the fold was 27 + 9 us at the very end of every step.
     // MISC_LAST_ON_TAIL: beside the Stats kernel, behind Duplicate's chain / the text kernel, when that stream is in use
     // MISC_ON_LAUNCH_STREAM: behind the Stats fold
     MiscFold misc_fold = MISC_WITH_STATS;
@@ -1628,8 +1711,13 @@ static int launch_stats(Launch& l) {
     }
     sa.debug_skip = l.a.debug_skip;
     if (l.a.debug_skip & 16u) return 0;   // (profiling builds: no Stats kernel, nothing of it to fold)
-    if (ctx->st_form == 5) hipLaunchKernelGGL(fq_stats5_kernel, dim3(st_grid), dim3(ctx->st_threads), (size_t)ctx->st_lds_dwords * 4, l.st, sa);
-    else hipLaunchKernelGGL(fq_stats_kernel, dim3(st_grid), dim3(ctx->st_threads), (size_t)ctx->st_lds_dwords * 4, l.st, sa);
+    if (ctx->st_form == 5) {
+        stats5_kernel_fn fq_stats5_kernel = ctx->st5_fn;   // (form 5 under its one name, whichever instantiation: what a launch trace shows)
+#ifdef FQ_PROFILE_ABLATION
+        if ((sa.debug_skip & 0xC0u) && sa.Hs == 10 && sa.kc == 2) fq_stats5_kernel = stats5_kernel_for(ST5_ABLATION);
+#endif
+        hipLaunchKernelGGL(fq_stats5_kernel, dim3(st_grid), dim3(ctx->st_threads), (size_t)ctx->st_lds_dwords * 4, l.st, sa);
+    } else hipLaunchKernelGGL(fq_stats_kernel, dim3(st_grid), dim3(ctx->st_threads), (size_t)ctx->st_lds_dwords * 4, l.st, sa);
     HIP_TRY(ctx, hipGetLastError());
     l.st_grid = st_grid;
     return 0;

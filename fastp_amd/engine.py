@@ -479,6 +479,22 @@ class GpuEngine:
         self._check(fn(self.h, out))
         return list(out)
 
+    KERNEL_REGS_NAMES = ("stats", "fq_reduce_kernel", "fq_dup_losers_kernel", "fq_dup_winners_kernel", "fq_dup_finish_kernel")
+    STATS5_INSTANTIATIONS = {0: "one_nf", 1: "one", 2: "blocks10", 3: "blocks8", 4: "any_kc2", 5: "any_kc1", 6: "ablation"}
+
+    def debug_kernel_regs(self):
+        """what the runtime allocates the Stats kernel this context launches and the tail stream's small kernels:
+        {"stats_inst": id of form 5's instantiation (-1: form 4), name: {"vgprs", "max_threads", "static_lds"}} (zeros on the emulator)"""
+        out = (C.c_int32 * 16)()
+        fn = self.lib.fastp_gpu_debug_kernel_regs
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        self._check(fn(self.h, out, 16))
+        d = {"stats_inst": int(out[0])}
+        for k, name in enumerate(self.KERNEL_REGS_NAMES):
+            d[name] = {"vgprs": int(out[1 + 3 * k]), "max_threads": int(out[2 + 3 * k]), "static_lds": int(out[3 + 3 * k])}
+        return d
+
     def plan(self) -> str:
         """which kernels run the worker loop for this context's options"""
         self.lib.fastp_gpu_plan.argtypes = [C.c_void_p]

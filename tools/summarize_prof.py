@@ -16,8 +16,19 @@ src = os.path.join(ROOT, "gpurun_out", "prof")
 dst = os.environ.get("SUMMARIZE_DST") or os.path.join(ROOT, "profiles")   # (on the GPU box: a directory under gpurun_out/, which is what travels back)
 os.makedirs(dst, exist_ok=True)
 
+
+
+def is_stats5(name):
+    """form 5 of the Stats kernel: a kernel per instantiation, fq_st5_kernel<...> (one symbol, fq_stats5_kernel, in older traces)"""
+    return "fq_st5_kernel" in name or name == "fq_stats5_kernel"
+
+
+def is_ours(name):
+    return name.startswith("fq_") or "fq_lane_kernel" in name or is_stats5(name)
+
+
 stats = list(csv.DictReader(open(os.path.join(src, tag, "trace_kernel_stats.csv"))))
-ours = [r for r in stats if r["Name"].startswith("fq_") or "fq_lane_kernel" in r["Name"]]
+ours = [r for r in stats if is_ours(r["Name"])]
 with open(os.path.join(dst, f"{tag}_kernel_stats.csv"), "w", newline="") as f:
     w = csv.DictWriter(f, fieldnames=list(stats[0].keys()))
     w.writeheader()
@@ -31,7 +42,7 @@ tp = os.path.join(src, tag, "trace_kernel_trace.csv")
 trace = list(csv.DictReader(open(tp))) if os.path.exists(tp) else []
 geom = {}
 for r in trace:
-    if (r["Kernel_Name"].startswith("fq_") or "fq_lane_kernel" in r["Kernel_Name"]) and r["Kernel_Name"] not in geom:
+    if is_ours(r["Kernel_Name"]) and r["Kernel_Name"] not in geom:
         geom[r["Kernel_Name"]] = {k: r[k] for k in ("LDS_Block_Size", "Scratch_Size", "VGPR_Count", "Accum_VGPR_Count",
                                                     "SGPR_Count", "Workgroup_Size_X", "Grid_Size_X")}
 
@@ -42,7 +53,7 @@ for kind, counter in (("fetch", "FETCH_SIZE"), ("write", "WRITE_SIZE")):
         continue
     agg = collections.defaultdict(list)
     for r in csv.DictReader(open(p)):
-        if (r["Kernel_Name"].startswith("fq_") or "fq_lane_kernel" in r["Kernel_Name"]) and r["Counter_Name"] == counter:
+        if is_ours(r["Kernel_Name"]) and r["Counter_Name"] == counter:
             agg[r["Kernel_Name"]].append(float(r["Counter_Value"]))
     for k, v in agg.items():
         pmc.setdefault(k, {})[counter + "_KiB_avg"] = sum(v) / len(v)
@@ -72,7 +83,7 @@ for extra in ("bench.log", "phase.log"):
 json.dump(out, open(os.path.join(dst, f"{tag}_summary.json"), "w"), indent=1)
 # what bench.py reports as roofline.traffic: HBM bytes per launch of the kernels that run the worker loop (the fused
 # kernel, or the per-read kernel + the Stats kernel of the split / lane plan), PMC-derived
-main = [k for k in out["kernels"] if k == "fq_fused_kernel" or k.startswith("fq_scan") or "fq_lane_kernel" in k or k in ("fq_stats_kernel", "fq_stats5_kernel")]
+main = [k for k in out["kernels"] if k == "fq_fused_kernel" or k.startswith("fq_scan") or "fq_lane_kernel" in k or k == "fq_stats_kernel" or is_stats5(k)]
 main = [k for k in main if "hbm_bytes_per_launch" in out["kernels"][k]]
 if main:
     tot = {f: sum(out["kernels"][k][f] for k in main) for f in ("hbm_read_bytes_per_launch", "hbm_write_bytes_per_launch", "hbm_bytes_per_launch")}
@@ -91,8 +102,8 @@ for d in sorted(glob.glob(os.path.join(src, tag + "_sq*"))):
     for fcsv in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
         for r in csv.DictReader(open(fcsv)):
             kn = r["Kernel_Name"]
-            if "fq_lane_kernel" in kn or kn in ("fq_stats_kernel", "fq_stats5_kernel", "fq_fused_kernel", "fq_scan_kernel"):
-                sq["fq_lane_kernel" if "fq_lane_kernel" in kn else kn][r["Counter_Name"]].append(float(r["Counter_Value"]))
+            if "fq_lane_kernel" in kn or is_stats5(kn) or kn in ("fq_stats_kernel", "fq_fused_kernel", "fq_scan_kernel"):
+                sq["fq_lane_kernel" if "fq_lane_kernel" in kn else "fq_stats5_kernel" if is_stats5(kn) else kn][r["Counter_Name"]].append(float(r["Counter_Value"]))
 if sq:
     per = {}
     for kn, ctrs in sq.items():
