@@ -339,6 +339,7 @@ struct fastp_gpu_ctx {
     int* d_ovr_len[2] = {nullptr, nullptr};
     u64* d_post_seen = nullptr;
     u32* d_ovr_work = nullptr; size_t ovr_work_cap = 0;   // blocksum | blockbase | n_tasks | tasks
+    int ovr_launches = 0; int ovr_plan[3] = {0, -1, -1};  // launch_overrep's last LDS plan (fastp_gpu_debug_overrep_plan)
     u8* d_def = nullptr; size_t def_cap = 0;              // deflate scratch: member slots | tokens | sizes | offsets | (levels 5..9) chains
     u8* d_eval = nullptr; size_t eval_cap = 0;            // Evaluator pre-pass: census table | hot list | text
     u32* d_ovr_corr = nullptr; size_t ovr_corr_cap = 0;   // correction chains: head[reads] | next[capacity]
@@ -1053,6 +1054,17 @@ extern "C" int fastp_gpu_debug_kernel_regs(fastp_gpu_ctx* ctx, int32_t* out, int
     return FASTP_GPU_OK;
 }
 
+// debugging aid: the LDS plan of the context's most recent overrepresentation launch as launch_overrep chose it - out[0] how many
+// such launches the context has made (0: the rest is {0, -1, -1}), out[1] sym_cap (0: the reads are not staged), out[2] / out[3]
+// table_lds[0] / table_lds[1] (the dword offset of the mate's seed table in LDS; -1: the table is probed in global memory).
+// Which branch of ovr_count_body ran follows from these; the emulator reports what it chose the same way.
+extern "C" int fastp_gpu_debug_overrep_plan(fastp_gpu_ctx* ctx, int32_t* out, int32_t n) {
+    if (!ctx || !out || n < 4) return FASTP_GPU_E_INVALID;
+    out[0] = ctx->ovr_launches;
+    for (int k = 0; k < 3; k++) out[1 + k] = ctx->ovr_plan[k];
+    return FASTP_GPU_OK;
+}
+
 static int ensure(fastp_gpu_ctx* ctx, void** buf, size_t* cap, size_t need) {
     if (*cap >= need) return 0;
     if (*buf) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); HIP_TRY(ctx, hipFree(*buf)); *buf = nullptr; *cap = 0; }
@@ -1168,6 +1180,8 @@ static int launch_overrep(fastp_gpu_ctx* ctx, const KernelArgs& a, int n, hipStr
                     lds_bytes += (int)tb;
                 }
             }
+            ctx->ovr_launches++;
+            ctx->ovr_plan[0] = o.sym_cap; ctx->ovr_plan[1] = o.table_lds[0]; ctx->ovr_plan[2] = o.table_lds[1];
             hipLaunchKernelGGL(fq_ovr_count_kernel, dim3((task_cap + OVR_TPB - 1) / OVR_TPB), dim3(OVR_BLOCK), (size_t)lds_bytes, st, o);
         }
         HIP_TRY(ctx, hipGetLastError());

@@ -22,7 +22,7 @@ EXPORTS = [
     "fastp_gpu_counters_export", "fastp_gpu_counters_import",
     "fastp_gpu_dup_scan_bytes", "fastp_gpu_submit_pass1_device", "fastp_gpu_dup_bitmap_bytes", "fastp_gpu_dup_bitmap_export",
     "fastp_gpu_dup_prefix_set", "fastp_gpu_prefix_or_images", "fastp_gpu_submit_pass2_device", "fastp_gpu_stream_set_origin", "fastp_gpu_overrep_device",
-    "fastp_gpu_device", "fastp_gpu_reset", "fastp_gpu_plan",
+    "fastp_gpu_device", "fastp_gpu_reset", "fastp_gpu_plan", "fastp_gpu_debug_overrep_plan",
     "fastp_gpu_host_alloc", "fastp_gpu_host_free", "fastp_gpu_submit_host_async", "fastp_gpu_wait", "fastp_gpu_poll",
     "fastp_gpu_comm_id", "fastp_gpu_comm_init", "fastp_gpu_comm_init_local", "fastp_gpu_comm_destroy", "fastp_gpu_allreduce",
     "fastp_gpu_exchange_dup_prefix", "fastp_gpu_comm_last_error", "fastp_gpu_dup_bitmap_import", "fastp_gpu_warmup",
@@ -494,6 +494,17 @@ class GpuEngine:
         for k, name in enumerate(self.KERNEL_REGS_NAMES):
             d[name] = {"vgprs": int(out[1 + 3 * k]), "max_threads": int(out[2 + 3 * k]), "static_lds": int(out[3 + 3 * k])}
         return d
+
+    def debug_overrep_plan(self):
+        """the LDS plan of this context's most recent overrepresentation launch as launch_overrep chose it:
+        {"launches": how many so far, "sym_cap": positions of a read staged in LDS (0: none), "table_lds": (dword offset of
+        read 1's / read 2's seed table in LDS, -1: probed in global memory)} - the same from the emulator"""
+        out = (C.c_int32 * 4)()
+        fn = self.lib.fastp_gpu_debug_overrep_plan
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        self._check(fn(self.h, out, 4))
+        return {"launches": int(out[0]), "sym_cap": int(out[1]), "table_lds": (int(out[2]), int(out[3]))}
 
     def plan(self) -> str:
         """which kernels run the worker loop for this context's options"""

@@ -767,6 +767,12 @@ int fastp_gpu_kernel_time(fastp_gpu_ctx* ctx, double* total_ms, int64_t* launche
 #define FASTP_GPU_PLAN_LANE 2
 int fastp_gpu_plan(const fastp_gpu_ctx* ctx);
 
+/* where the overrepresentation counting kernel of the context's most recent launch found its inputs (diagnostic; the
+ * results do not depend on it): out[0] = overrepresentation launches so far, out[1] = positions of a read staged in LDS
+ * (0 = read from global memory), out[2] / out[3] = dword offset of read 1's / read 2's seed table in LDS (-1 = probed in
+ * global memory).  n >= 4. */
+int fastp_gpu_debug_overrep_plan(fastp_gpu_ctx* ctx, int32_t* out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif
