@@ -201,6 +201,19 @@ extern "C" __global__ void __launch_bounds__(256) fq_eval_kmer_kernel(EvalKmerAr
 extern "C" __global__ void __launch_bounds__(256) fq_eval_census_kernel(EvalCensusArgs a) { eval_census_body(a); }
 extern "C" __global__ void __launch_bounds__(256) fq_eval_harvest_kernel(EvalCensusArgs a) { eval_harvest_body(a); }
 extern "C" __global__ void __launch_bounds__(256) fq_eval_text_kernel(EvalCensusArgs a) { eval_text_body(a); }
+extern "C" __global__ void __launch_bounds__(64 * EVAL_MATCH_WAVES) fq_eval_match_kernel(EvalMatchArgs a) {
+    extern __shared__ __attribute__((aligned(16))) u32 fq_lds[];
+    eval_match_body(a, fq_lds);
+}
+extern "C" __global__ void __launch_bounds__(64) fq_eval_replay_kernel(EvalMatchArgs a) {
+    extern __shared__ __attribute__((aligned(16))) u32 fq_lds[];
+    eval_replay_body(a, fq_lds);
+}
+extern "C" __global__ void __launch_bounds__(256) fq_eval_seed_gather_kernel(EvalSeedArgs a) { eval_seed_gather_body(a); }
+extern "C" __global__ void __launch_bounds__(1024) fq_eval_seed_walk_kernel(EvalSeedArgs a) {
+    extern __shared__ __attribute__((aligned(16))) u32 fq_lds[];
+    eval_seed_walk_body(a, fq_lds);
+}
 extern "C" __global__ void __launch_bounds__(256) fq_fmts_corr_kernel(FmtsArgs f) { fmts_corr_body(f); }
 extern "C" __global__ void __launch_bounds__(256) fq_fmts_len_kernel(FmtsArgs f) {
     extern __shared__ u32 fq_lds[];
@@ -2642,6 +2655,166 @@ extern "C" int fastp_gpu_eval_overrep(fastp_gpu_ctx* ctx, const uint8_t* seq, co
         count[i] = kv.second;
         off[++i] = at;
     }
+    return FASTP_GPU_OK;
+}
+
+// Evaluator::checkKnownAdapters: the match kernel over every (read, adapter), the replay of the loop's state machine over
+// the matched pairs, the final choice (:291-305) here.  The list is the caller's; it is walked in std::map order.
+extern "C" int fastp_gpu_eval_known_adapters(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len,
+                                             int32_t n, const char* const* adapters, int32_t n_adapters, int32_t* counts,
+                                             int32_t* mismatches, int64_t* checked_reads, int32_t* best) {
+    if (!ctx || !checked_reads || !best || n < 0 || n_adapters < 0 || (n > 0 && (!seq || !qual || !len)) ||
+        (n_adapters > 0 && (!adapters || !counts || !mismatches)))
+        return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
+    *best = -1;
+    *checked_reads = 0;
+    if (n_adapters > EVAL_MAX_ADAPTERS) return fail(ctx, FASTP_GPU_E_UNSUPPORTED, "more than 1024 known adapters");
+    const int A = n_adapters;
+    std::vector<int> order(A);   // map order -> the caller's index
+    int max_alen = 0;
+    for (int i = 0; i < A; i++) {
+        order[i] = i;
+        if (!adapters[i] || !adapters[i][0]) return fail(ctx, FASTP_GPU_E_INVALID, "empty known adapter");
+        const size_t l = strlen(adapters[i]);
+        if (l > FASTP_GPU_MAX_ADAPTER_LEN) return fail(ctx, FASTP_GPU_E_UNSUPPORTED, "known adapter longer than FASTP_GPU_MAX_ADAPTER_LEN");
+        for (size_t k = 0; k < l; k++)
+            if (!strchr("ACGT", adapters[i][k])) return fail(ctx, FASTP_GPU_E_INVALID, "known adapter with a letter outside ACGT");
+        max_alen = std::max(max_alen, (int)l);
+    }
+    std::sort(order.begin(), order.end(), [&](int x, int y) { return strcmp(adapters[x], adapters[y]) < 0; });
+    for (int i = 1; i < A; i++)
+        if (!strcmp(adapters[order[i - 1]], adapters[order[i]]))
+            return fail(ctx, FASTP_GPU_E_INVALID, "the same known adapter twice (a std::map holds it once)");
+    for (int i = 0; i < A; i++) counts[i] = mismatches[i] = 0;
+    // checkedReads without a list: the loop only counts (and the base limit cannot bind, fq_eval.h)
+    *checked_reads = n > EVAL_CHECK_READS ? EVAL_CHECK_READS + 1 : n;
+    if (A == 0 || n == 0) return FASTP_GPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    EvalMatchArgs a;
+    memset(&a, 0, sizeof(a));
+    a.r.seq = seq;
+    a.r.qual = qual;
+    a.r.len = len;
+    a.r.n = std::min<int>(n, EVAL_CHECK_READS);
+    a.r.seq_stride = (int)fastp_gpu_seq_stride(ctx->dp.max_len);
+    a.r.qual_stride = (int)fastp_gpu_qual_stride(ctx->dp.max_len);
+    a.n_all = n;
+    a.n_adapters = A;
+    a.ad_words = (max_alen + 31) / 32;
+    a.bit_words = (A + 31) / 32;
+    std::vector<u64> words((size_t)A * a.ad_words, 0ull);
+    std::vector<u16> alen((size_t)A);
+    for (int i = 0; i < A; i++) {
+        const char* s = adapters[order[i]];
+        alen[i] = (u16)strlen(s);
+        for (int k = 0; s[k]; k++) {
+            const u64 code = s[k] == 'A' ? 0u : s[k] == 'T' ? 1u : s[k] == 'C' ? 2u : 3u;   // the packed rows' coding
+            words[(size_t)i * a.ad_words + k / 32] |= code << (2 * (k % 32));
+        }
+    }
+    const size_t b_words = words.size() * 8, b_alen = ((size_t)A * 2 + 7) & ~(size_t)7, b_cnt = (size_t)A * 8 + 8,
+                 b_bits = (((size_t)a.r.n * a.bit_words * 4) + 7) & ~(size_t)7, b_mm = (size_t)a.r.n * A;
+    int rc = ensure(ctx, (void**)&ctx->d_eval, &ctx->eval_cap, b_words + b_alen + b_cnt + b_bits + b_mm);
+    if (rc) return rc;
+    u8* base = ctx->d_eval;
+    a.words = (const u64*)base;
+    a.alen = (const u16*)(base + b_words);
+    a.checked = (long long*)(base + b_words + b_alen);
+    a.counts = (int*)(base + b_words + b_alen + 8);
+    a.bits = (u32*)(base + b_words + b_alen + b_cnt);
+    a.mm = base + b_words + b_alen + b_cnt + b_bits;
+    HIP_TRY(ctx, hipMemcpyAsync(base, words.data(), b_words, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(base + b_words, alen.data(), (size_t)A * 2, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));   // (the staging vectors are pageable)
+    hipLaunchKernelGGL(fq_eval_match_kernel, dim3((unsigned)((a.r.n + EVAL_MATCH_WAVES - 1) / EVAL_MATCH_WAVES)), dim3(64 * EVAL_MATCH_WAVES),
+                       (size_t)EVAL_MATCH_WAVES * (EVAL_MATCH_LDS + a.bit_words * 32) * 4, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(fq_eval_replay_kernel, dim3(1), dim3(64), (size_t)A * 8, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<int> res((size_t)2 * A + 2);
+    HIP_TRY(ctx, hipMemcpyAsync(res.data(), a.checked, b_cnt, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    long long checked;
+    memcpy(&checked, res.data(), 8);
+    *checked_reads = checked;
+    int top = -1, max_count = 0;   // :291-299: the first in map order with the strictly largest count
+    for (int i = 0; i < A; i++) {
+        counts[order[i]] = res[2 + i];
+        mismatches[order[i]] = res[2 + A + i];
+        if (res[2 + i] > max_count) {
+            max_count = res[2 + i];
+            top = i;
+        }
+    }
+    if (top >= 0 && (max_count > checked / 50 || (max_count > checked / 200 && res[2 + A + top] < checked))) *best = order[top];
+    return FASTP_GPU_OK;
+}
+
+// Evaluator::getAdapterWithSeed's two scans and the two NucleotideTree::getDominantPath walks for one seed
+extern "C" int fastp_gpu_eval_adapter_seed(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len,
+                                           int32_t n, int32_t trim_tail1, uint32_t seed, char* forward, int32_t* forward_len,
+                                           char* backward, int32_t* backward_len, int32_t* reached_leaf, int64_t* hits) {
+    if (!ctx || !forward || !forward_len || !backward || !backward_len || !reached_leaf || !hits || n < 0 || seed >= (1u << 20) ||
+        (n > 0 && (!seq || !qual || !len)))
+        return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
+    *forward_len = *backward_len = 0;
+    *reached_leaf = 1;
+    *hits = 0;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int64_t READ_LIMIT = 256 * 1024, BASE_LIMIT = 151 * READ_LIMIT;   // evaluator.cpp:313-314
+    std::vector<u16> lens;
+    int rc = eval_admit(ctx, len, n, READ_LIMIT, BASE_LIMIT, lens);
+    if (rc) return rc;
+    EvalSeedArgs a;
+    memset(&a, 0, sizeof(a));
+    a.r.seq = seq;
+    a.r.qual = qual;
+    a.r.len = len;
+    a.r.n = (int)lens.size();
+    a.r.seq_stride = (int)fastp_gpu_seq_stride(ctx->dp.max_len);
+    a.r.qual_stride = (int)fastp_gpu_qual_stride(ctx->dp.max_len);
+    a.shift_tail = std::max(1, trim_tail1);
+    a.span = std::min(480, std::max(1, ctx->dp.max_len - 29));   // positions 20 .. min(len - 10 - shift_tail, 499)
+    a.seed = seed;
+    const long long lanes = (long long)a.r.n * a.span;
+    if (lanes == 0) return FASTP_GPU_OK;
+    // count the hits, size the list by the count, list them
+    const size_t b_head = 8 + 16 + 1024;   // n_hits | path_len[2], reached_leaf | the two paths
+    u64 nh = 0;
+    for (int pass = 0; pass < 2; pass++) {
+        rc = ensure(ctx, (void**)&ctx->d_eval, &ctx->eval_cap, b_head + (size_t)nh * 4);
+        if (rc) return rc;
+        u8* base = ctx->d_eval;
+        a.n_hits = (u64*)base;
+        a.path_len = (int*)(base + 8);
+        a.path = base + 24;
+        a.hits = pass ? (u32*)(base + b_head) : nullptr;
+        a.cap = nh;
+        HIP_TRY(ctx, hipMemsetAsync(base, 0, 24, st));
+        hipLaunchKernelGGL(fq_eval_seed_gather_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, a);
+        HIP_TRY(ctx, hipGetLastError());
+        if (pass) break;
+        HIP_TRY(ctx, hipMemcpyAsync(&nh, a.n_hits, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        *hits = (int64_t)nh;
+        if (nh < 50) return FASTP_GPU_OK;   // NUM_THRESHOLD: both walks end at the root, reachedLeaf stays
+    }
+    const int one = 1;
+    HIP_TRY(ctx, hipMemcpyAsync(a.path_len + 2, &one, 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(fq_eval_seed_walk_kernel, dim3(2), dim3(1024), 16, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    u8 out[16 + 1024];
+    HIP_TRY(ctx, hipMemcpyAsync(out, a.path_len, sizeof(out), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    int head[4];
+    memcpy(head, out, 16);
+    *forward_len = head[0];
+    *backward_len = head[1];
+    *reached_leaf = head[2];
+    memcpy(forward, out + 16, (size_t)head[0]);
+    memcpy(backward, out + 16 + 512, (size_t)head[1]);
     return FASTP_GPU_OK;
 }
 

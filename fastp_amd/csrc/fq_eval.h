@@ -1,9 +1,12 @@
-// fq_eval.h - the Evaluator pre-pass on the device: the two counting loops of
+// fq_eval.h - the Evaluator pre-pass on the device: the loops of
 // /root/reference/src/evaluator.cpp that run over a prefix of the input before any worker starts -
-//   * the 4^10 ten-mer histogram of evalAdapterAndReadNum (evaluator.cpp:377-399), and
+//   * the 4^10 ten-mer histogram of evalAdapterAndReadNum (evaluator.cpp:377-399),
 //   * the substring census of computeOverRepSeq (evaluator.cpp:78-142): every substring of 5 lengths of the
-//     first 1.51 Mbases, counted exactly (the reference keeps a std::map<string,long>).
-// Both read the packed rows a batch already holds in HBM (2-bit bases + the N flag in the quality byte).
+//     first 1.51 Mbases, counted exactly (the reference keeps a std::map<string,long>),
+//   * the loop of checkKnownAdapters (evaluator.cpp:242-289): every known adapter at every position of up to 100,000 reads, and
+//   * the scans and tree walks of getAdapterWithSeed (evaluator.cpp:485-520) for one seed of the histogram.
+// All read the packed rows a batch already holds in HBM (2-bit bases + the N flag in the quality byte).  What the Evaluator
+// decides from the numbers stays on the host.
 #pragma once
 #include "fq_intrin.h"
 #include "fq_types.h"
@@ -169,6 +172,286 @@ FQ_DEV void eval_text_body(const EvalCensusArgs& a) {
     const u8* q = a.r.qual + (size_t)rd * a.r.qual_stride;
     u8* o = a.text + (size_t)k * 152;
     for (int j = (int)gl; j < step; j += 16) o[j] = (u8)"ATCGN"[eval_base(s, q, pos + j)];
+}
+
+// ---- known-adapter check (Evaluator::checkKnownAdapters, evaluator.cpp:220-306) -----------------------------
+// Two steps whose composition is the reference's sequential loop.  The inner loop (:266-287) - the first position of
+// a read at which an adapter fits with at most cmplen / 16 mismatches - does not depend on the loop's running state,
+// so eval_match_body computes it for every (read, adapter); eval_replay_body then walks the matched pairs in read
+// order and in std::map order inside a read, with the pruning rule (:263) and the exits (:252-255) of the loop.
+// Adapters are given sorted (map order) as 2-bit words, 32 bases to a u64, base i in bits [2(i%32), 2(i%32)+1].
+enum { EVAL_AD_WORDS = 8,        // 256 bases = FASTP_GPU_MAX_ADAPTER_LEN
+       EVAL_MATCH_WAVES = 4,     // reads (wavefronts) per workgroup of the match kernel
+       EVAL_MATCH_LDS = 48 + 48 + 32,   // dwords per wavefront: bases | N mask | matched bitset, then a dword per adapter
+       EVAL_MAX_ADAPTERS = 1024,
+       EVAL_CHECK_READS = 100000 };      // MAX_CHECK_READS (:226)
+struct EvalMatchArgs {
+    EvalReads r;             // r.n: the reads the check can reach (at most EVAL_CHECK_READS)
+    const u64* words;        // [n_adapters][ad_words]
+    const u16* alen;         // [n_adapters]
+    int n_adapters, ad_words, bit_words;   // bit_words = ceil(n_adapters / 32)
+    u32* bits;               // [n][bit_words]  bit a: adapter a matched the read
+    u8* mm;                  // [n][n_adapters] its mismatches (written for matched pairs only)
+    // replay
+    int n_all;               // reads the caller has (the loop's `num`)
+    int* counts;             // [n_adapters] possibleCounts | [n_adapters] mismatches
+    long long* checked;      // [1] checkedReads
+};
+
+FQ_DEV u64 eval_pairs_mask(int c) {   // the low bit of each of the first c (0..32) base pairs
+    return c >= 32 ? 0x5555555555555555ull : (((1ull << (2 * (c < 0 ? 0 : c))) - 1ull) & 0x5555555555555555ull);
+}
+
+// A wavefront per read, a lane per position, 64 positions to a tile, tiles in ascending order.  The read is staged once in
+// LDS as 2-bit words and an N mask; a lane funnel-shifts its window out of them into registers, one u64 per 32 bases, and
+// keeps it for all adapters, which arrive as wave-uniform words.  A lane whose position fits says so with an LDS minimum on
+// pos << 8 | mismatches: the smallest position wins and brings its own count.  Fits are rare, so almost no lane gets there.
+FQ_DEV void eval_match_body(const EvalMatchArgs& a, u32* lds) {
+    const int lane = lane_id(), rd = block_id() * EVAL_MATCH_WAVES + wave_id();
+    if (rd >= a.r.n) return;
+    u32* sq = lds + wave_id() * (EVAL_MATCH_LDS + a.bit_words * 32);   // 32 dwords of bases (512) + 16 of zeros: a window may start at 503
+    u32* nm = sq + 48;                            // the N flags spread to the low bit of each base's pair
+    u32* done = nm + 48;                          // [32] adapters that fitted in the tiles so far
+    u32* first = done + 32;                       // [bit_words * 32] pos << 8 | mismatches of the first fit, ~0: none
+    const int rlen = a.r.len[rd] < 512 ? a.r.len[rd] : 512;   // (FASTP_GPU_MAX_READ_LEN: what the stage holds)
+    const u8* s = a.r.seq + (size_t)rd * a.r.seq_stride;
+    const u8* q = a.r.qual + (size_t)rd * a.r.qual_stride;
+    if (lane < 48) {   // dword `lane`: bases 16 * lane .. + 15
+        u32 w = 0, m = 0;
+        if (16 * lane < rlen) {
+            for (int k = 0; k < 4; k++)
+                if (4 * lane + k < a.r.seq_stride) w |= (u32)s[4 * lane + k] << (8 * k);
+            for (int k = 0; k < 16; k++)
+                if (16 * lane + k < rlen) m |= (u32)(q[16 * lane + k] >> 7) << (2 * k);
+        }
+        sq[lane] = w;
+        nm[lane] = m;
+    }
+    if (lane < 32) done[lane] = 0u;
+    for (int k = lane; k < a.bit_words * 32; k += 64) first[k] = 0xFFFFFFFFu;
+    wave_sync();
+    const int npos = rlen - 8;   // for(pos = 0; pos < rlen - matchReq; pos++)
+    u32* bits = a.bits + (size_t)rd * a.bit_words;
+    if (npos <= 0) {
+        if (lane < a.bit_words) bits[lane] = 0u;
+        return;
+    }
+    if (lane >= npos && lane >= a.bit_words) return;    // a lane without a position in any tile and without a word to fold
+    for (int tile = 0; tile * 64 < npos; tile++) {
+        const int pos = tile * 64 + lane;
+        const bool has_pos = pos < npos;
+        // the read from `pos` on, as the adapters are laid out; bases past its end take no part in any comparison
+        u64 R[EVAL_AD_WORDS], V[EVAL_AD_WORDS], N[EVAL_AD_WORDS];
+        const u32 sh = 2u * (u32)(pos & 15);
+#pragma unroll
+        for (int w = 0; w < EVAL_AD_WORDS; w++) {
+            R[w] = V[w] = N[w] = 0ull;
+            if (w < a.ad_words && has_pos) {
+                const int i0 = (pos >> 4) + 2 * w;   // <= 31 + 14, + 2 < 48
+                R[w] = (u64)alignbit(sq[i0 + 1], sq[i0], sh) | ((u64)alignbit(sq[i0 + 2], sq[i0 + 1], sh) << 32);
+                V[w] = eval_pairs_mask(rlen - pos - 32 * w);
+                N[w] = ((u64)alignbit(nm[i0 + 1], nm[i0], sh) | ((u64)alignbit(nm[i0 + 2], nm[i0 + 1], sh) << 32)) & V[w];
+            }
+        }
+        if (has_pos)
+            for (int g = 0; g < a.bit_words; g++) {
+                const u32 dn = tile ? done[g] : 0u;
+                for (int j = 0; j < 32; j++) {
+                    const int ad = g * 32 + j;
+                    if (ad >= a.n_adapters) break;
+                    if ((dn >> j) & 1u) continue;        // its first position lies in an earlier tile
+                    const int alen = (int)a.alen[ad];
+                    if (alen >= rlen) continue;          // :260
+                    const int nw = (alen + 31) >> 5;
+                    const u64* aw = a.words + (size_t)ad * a.ad_words;
+                    int mism = 0;
+#pragma unroll
+                    for (int w = 0; w < EVAL_AD_WORDS; w++)
+                        if (w < nw) {
+                            const u64 x = R[w] ^ aw[w];
+                            // a differing base or an N, inside the read and inside the adapter
+                            mism += popc64((((x | (x >> 1)) & V[w]) | N[w]) & eval_pairs_mask(alen - 32 * w));
+                        }
+                    const int cmplen = rlen - pos < alen ? rlen - pos : alen;
+                    if (mism <= (cmplen >> 4)) lds_min_u32(&first[ad], ((u32)pos << 8) | (u32)mism);   // mism <= 256 / 16
+                }
+            }
+        wave_sync();
+        if (lane < a.bit_words) {
+            u32 dn = 0u;
+            for (int j = 0; j < 32; j++) dn |= (u32)(first[lane * 32 + j] != 0xFFFFFFFFu) << j;
+            done[lane] = dn;
+        }
+        wave_sync();
+    }
+    if (lane < a.bit_words) {
+        bits[lane] = done[lane];
+        u8* mm = a.mm + (size_t)rd * a.n_adapters;
+        for (int ad = lane * 32; ad < lane * 32 + 32 && ad < a.n_adapters; ad++)
+            if (first[ad] != 0xFFFFFFFFu) mm[ad] = (u8)first[ad];
+    }
+}
+
+// One wavefront.  Only matched pairs change the loop's state, so reads are taken 64 at a time (a lane each) and lane 0
+// walks the set bits of the ones that matched something.  LDS: counts | mismatches.
+// The exits: `checkedReads > 100000` is read index 100000; `checkedBases > 100000000` cannot bind before it while a
+// read has at most FASTP_GPU_MAX_READ_LEN = 512 bases (100000 * 512 < 10^8) - kept, on a 64-bit sum, for the day that
+// limit moves; `curMaxCount > 1000` is seen at the read after the one that raised it.
+FQ_DEV void eval_replay_body(const EvalMatchArgs& a, u32* lds) {
+    const int lane = lane_id(), A = a.n_adapters;
+    int* cnt = (int*)lds;
+    int* mis = cnt + A;
+    for (int k = lane; k < 2 * A; k += 64) cnt[k] = 0;
+    wave_sync();
+    long long bases = 0, checked = a.n_all;
+    int cur_max = 0;        // lane 0's
+    for (int base = 0; base < a.n_all; base += 64) {
+        const int i = base + lane;
+        const bool ok = i < a.n_all;
+        u32 cum = ok ? (u32)a.r.len[i] : 0u;
+        for (int d = 1; d < 64; d <<= 1) {
+            const u32 o = shfl(cum, lane >= d ? lane - d : lane);
+            if (lane >= d) cum += o;
+        }
+        const u64 over = ballot(ok && (i >= EVAL_CHECK_READS || bases + (long long)cum > 100000000ll));
+        const int cut = over ? ffs64(over) - 1 : 64;   // the read at which the loop leaves: counted, not looked at
+        bool any = false;
+        if (ok && lane < cut)
+            for (int g = 0; g < a.bit_words; g++) any |= a.bits[(size_t)i * a.bit_words + g] != 0u;
+        u64 ev = ballot(any);
+        bool stop = false;
+        if (lane == 0) {
+            while (ev) {
+                const int e = ffs64(ev) - 1;
+                ev &= ev - 1ull;
+                const size_t rd = (size_t)(base + e);
+                for (int g = 0; g < a.bit_words; g++) {
+                    u32 w = a.bits[rd * a.bit_words + g];
+                    while (w) {
+                        const int ad = g * 32 + ffs32(w) - 1;
+                        w &= w - 1u;
+                        if (cur_max > 20 && cnt[ad] < cur_max / 10) continue;   // :263
+                        const int c = ++cnt[ad];
+                        if (cur_max < c) cur_max = c;
+                        mis[ad] += (int)a.mm[rd * A + ad];
+                    }
+                }
+                if (cur_max > 1000) {   // :254, at the next read if there is one
+                    checked = (long long)rd + 2 < a.n_all ? (long long)rd + 2 : a.n_all;
+                    stop = true;
+                    break;
+                }
+            }
+            if (!stop && over) {
+                checked = base + cut + 1;
+                stop = true;
+            }
+        }
+        bases += (long long)shfl(cum, 63);
+        if (ballot(stop)) break;
+    }
+    wave_sync();
+    for (int k = lane; k < 2 * A; k += 64) a.counts[k] = cnt[k];
+    if (lane == 0) *a.checked = checked;
+}
+
+// ---- seed extension (Evaluator::getAdapterWithSeed evaluator.cpp:485-520, NucleotideTree nucleotidetree.cpp:42-88) ----
+// The two scans find the same (read, pos) hits; a tree's dominant path only needs, per depth, how many of the hits that
+// followed the path so far carry each base there.  eval_seed_gather_body lists the hits (or counts them: hits == nullptr),
+// eval_seed_walk_body walks both directions, one workgroup each, over its lanes' share of the list.
+//   hit word: read << 9 | pos (pos < 500); bit 31 / 30: left the forward / backward path
+struct EvalSeedArgs {
+    EvalReads r;
+    int shift_tail, span;
+    u32 seed;
+    u32* hits;               // [cap] or nullptr
+    u64* n_hits;             // [1]
+    u64 cap;
+    // walk
+    u8* path;                // [2][512] forward | backward
+    int* path_len;           // [2], then [2] = 1 unless a walk ended without a dominant base
+};
+
+FQ_DEV void eval_seed_gather_body(const EvalSeedArgs& a) {
+    const long long t = (long long)block_id() * block_threads() + thread_id();
+    const int rd = (int)(t / a.span), pos = 20 + (int)(t % a.span);   // span <= 480: pos < MAX_SEARCH_LENGTH
+    if (rd >= a.r.n) return;
+    const int rlen = a.r.len[rd];
+    if (pos > rlen - 10 - a.shift_tail) return;
+    const u8* s = a.r.seq + (size_t)rd * a.r.seq_stride;
+    const u8* q = a.r.qual + (size_t)rd * a.r.qual_stride;
+    u32 nflag = 0;
+    for (int k = 0; k < 10; k++) nflag |= q[pos + k];
+    if (nflag & 0x80u) return;
+    const int b = pos >> 2, nb = ((pos + 9) >> 2) - b;
+    u32 w = 0;
+    for (int k = 0; k <= nb; k++) w |= (u32)s[b + k] << (8 * k);
+    if (eval_reverse_pairs20((w >> (2 * (pos & 3))) & 0xFFFFFu) != a.seed) return;
+    const u64 k = __hip_atomic_fetch_add(a.n_hits, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (a.hits && k < a.cap) a.hits[k] = ((u32)rd << 9) | (u32)pos;
+}
+
+// the base (0..3) depth d of a hit's sequence holds, 4: the sequence has ended (its end, or an N: addSeq :45)
+FQ_DEV u32 eval_seed_base(const EvalSeedArgs& a, u32 hit, int dir, int d) {
+    const int rd = (int)((hit >> 9) & 0x1FFFFFu), pos = (int)(hit & 511u);
+    int j;
+    if (dir == 0) {
+        j = pos + 10 + d;
+        if (j >= (int)a.r.len[rd] - a.shift_tail) return 4u;
+    } else {
+        j = pos - 1 - d;
+        if (j < 0) return 4u;
+    }
+    return eval_base(a.r.seq + (size_t)rd * a.r.seq_stride, a.r.qual + (size_t)rd * a.r.qual_stride, j);
+}
+
+FQ_DEV void eval_seed_walk_body(const EvalSeedArgs& a, u32* lds) {
+    const int dir = block_id(), tid = thread_id(), T = block_threads();
+    const u32 dead = dir == 0 ? 0x80000000u : 0x40000000u;
+    const u64 nh = *a.n_hits < a.cap ? *a.n_hits : a.cap;
+    u8* path = a.path + 512 * dir;
+    int depth = 0;
+    u32 last = 0;
+    bool leaf = true;
+    for (; depth < 512; depth++) {
+        if (tid < 4) lds[tid] = 0u;
+        block_sync();
+        u32 c[4] = {0u, 0u, 0u, 0u};
+        for (u64 k = (u64)tid; k < nh; k += (u64)T) {
+            const u32 h = __hip_atomic_load(&a.hits[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (h & dead) continue;
+            u32 b = 4u;
+            if (depth == 0 || eval_seed_base(a, h, dir, depth - 1) == last) b = eval_seed_base(a, h, dir, depth);
+            if (b > 3u) {
+                g_atomic_or_u32(&a.hits[k], dead);   // (the other direction's workgroup owns the other bit of the word)
+                continue;
+            }
+            c[0] += b == 0u; c[1] += b == 1u; c[2] += b == 2u; c[3] += b == 3u;
+        }
+        for (int b = 0; b < 4; b++)
+            if (c[b]) lds_add_u32(&lds[b], c[b]);
+        block_sync();
+        const u32 n0 = lds[0], n1 = lds[1], n2 = lds[2], n3 = lds[3];
+        block_sync();
+        const u32 total = n0 + n1 + n2 + n3;
+        if (total < 50u) break;                      // NUM_THRESHOLD
+        // children[base & 7]: A, C, T, G; at most one base can hold 95 %
+        const u32 n[4] = {n0, n1, n2, n3};
+        const int order[4] = {0, 2, 1, 3};
+        int pick = -1;
+        for (int o = 0; o < 4 && pick < 0; o++)
+            if ((double)n[order[o]] / (double)total >= 0.95) pick = order[o];
+        if (pick < 0) {
+            leaf = false;
+            break;
+        }
+        last = (u32)pick;
+        if (tid == 0) path[depth] = (u8)"ATCG"[pick];
+    }
+    if (tid == 0) {
+        a.path_len[dir] = depth;
+        if (!leaf) g_atomic_exch_u32((u32*)&a.path_len[2], 0u);
+    }
 }
 
 }  // namespace fq

@@ -17,7 +17,7 @@ _LIBS: dict[str, C.CDLL] = {}
 EXPORTS = [
     "fastp_gpu_default_params", "fastp_gpu_seq_stride", "fastp_gpu_qual_stride", "fastp_gpu_cycles_for",
     "fastp_gpu_counter_layout_for", "fastp_gpu_counter_layout_for_params", "fastp_gpu_create", "fastp_gpu_destroy", "fastp_gpu_last_error",
-    "fastp_gpu_pack_reads", "fastp_gpu_pack_reads_x", "fastp_gpu_bgzf_index", "fastp_gpu_inflate_bgzf", "fastp_gpu_parse_fastq", "fastp_gpu_parse_exotic", "fastp_gpu_phred64_to_33", "fastp_gpu_host_writes_overlapped", "fastp_gpu_format_fastq", "fastp_gpu_format_streams", "fastp_gpu_format_all_streams", "fastp_gpu_deflate_bgzf", "fastp_gpu_deflate_bgzf_level", "fastp_gpu_device_alloc", "fastp_gpu_device_free", "fastp_gpu_device_upload", "fastp_gpu_device_download", "fastp_gpu_eval_seq_len", "fastp_gpu_eval_adapter_kmers", "fastp_gpu_eval_overrep", "fastp_gpu_submit_host", "fastp_gpu_submit_device", "fastp_gpu_synchronize",
+    "fastp_gpu_pack_reads", "fastp_gpu_pack_reads_x", "fastp_gpu_bgzf_index", "fastp_gpu_inflate_bgzf", "fastp_gpu_parse_fastq", "fastp_gpu_parse_exotic", "fastp_gpu_phred64_to_33", "fastp_gpu_host_writes_overlapped", "fastp_gpu_format_fastq", "fastp_gpu_format_streams", "fastp_gpu_format_all_streams", "fastp_gpu_deflate_bgzf", "fastp_gpu_deflate_bgzf_level", "fastp_gpu_device_alloc", "fastp_gpu_device_free", "fastp_gpu_device_upload", "fastp_gpu_device_download", "fastp_gpu_eval_seq_len", "fastp_gpu_eval_adapter_kmers", "fastp_gpu_eval_overrep", "fastp_gpu_eval_known_adapters", "fastp_gpu_eval_adapter_seed", "fastp_gpu_submit_host", "fastp_gpu_submit_device", "fastp_gpu_synchronize",
     "fastp_gpu_counters_device", "fastp_gpu_counters", "fastp_gpu_kernel_time",
     "fastp_gpu_counters_export", "fastp_gpu_counters_import",
     "fastp_gpu_dup_scan_bytes", "fastp_gpu_submit_pass1_device", "fastp_gpu_dup_bitmap_bytes", "fastp_gpu_dup_bitmap_export",
@@ -416,6 +416,65 @@ class GpuEngine:
             return rc, int(ns.value)
         raw = text.raw
         return rc, [(raw[off[i]:off[i + 1]], int(cnt[i])) for i in range(ns.value)]
+
+    def eval_known_adapters(self, seq_ptr, qual_ptr, len_ptr, n, adapters, check=True):
+        """Evaluator::checkKnownAdapters over `adapters` (a list of bytes): returns (rc, counts int32[len(adapters)],
+        mismatches int32[len(adapters)], checked_reads, best) - best an index into `adapters` or -1"""
+        fn = self.lib.fastp_gpu_eval_known_adapters
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int32,
+                       C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        na = len(adapters)
+        arr = (C.c_char_p * max(1, na))(*[bytes(x) for x in adapters])
+        counts = np.zeros(max(1, na), dtype=np.int32)
+        mism = np.zeros(max(1, na), dtype=np.int32)
+        checked, best = C.c_int64(0), C.c_int32(-1)
+        rc = fn(self.h, seq_ptr, qual_ptr, len_ptr, n, arr, na, counts.ctypes.data, mism.ctypes.data, C.byref(checked),
+                C.byref(best))
+        if check:
+            self._check(rc)
+        return rc, counts[:na], mism[:na], int(checked.value), int(best.value)
+
+    def eval_adapter_seed(self, seq_ptr, qual_ptr, len_ptr, n, trim_tail1, seed, check=True):
+        """the scans and dominant-path walks of Evaluator::getAdapterWithSeed for one seed (a bin of eval_adapter_kmers):
+        returns (rc, forward bytes, backward bytes - as the tree returns it, not reversed -, reached_leaf, hits)"""
+        fn = self.lib.fastp_gpu_eval_adapter_seed
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p,
+                       C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+        fwd, bwd = C.create_string_buffer(abi.MAX_READ_LEN), C.create_string_buffer(abi.MAX_READ_LEN)
+        nf, nb, leaf, hits = C.c_int32(0), C.c_int32(0), C.c_int32(1), C.c_int64(0)
+        rc = fn(self.h, seq_ptr, qual_ptr, len_ptr, n, trim_tail1, seed, fwd, C.byref(nf), bwd, C.byref(nb), C.byref(leaf),
+                C.byref(hits))
+        if check:
+            self._check(rc)
+        return rc, fwd.raw[:nf.value], bwd.raw[:nb.value], bool(leaf.value), int(hits.value)
+
+    # ---- device memory through the engine (fastp_gpu_device_*): for hosts that hold no HIP runtime of their own ----
+    def device_alloc(self, nbytes: int) -> int:
+        fn = self.lib.fastp_gpu_device_alloc
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
+        p = C.c_void_p()
+        self._check(fn(self.h, nbytes, C.byref(p)))
+        return int(p.value)
+
+    def device_free(self, ptr: int):
+        fn = self.lib.fastp_gpu_device_free
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p]
+        self._check(fn(self.h, ptr))
+
+    def device_upload(self, dst_ptr: int, data):
+        fn = self.lib.fastp_gpu_device_upload
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        a = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8))
+        self._check(fn(self.h, dst_ptr, a.ctypes.data, a.size))
+
+    def device_download(self, src_ptr: int, nbytes: int) -> np.ndarray:
+        fn = self.lib.fastp_gpu_device_download
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        out = np.zeros(nbytes, dtype=np.uint8)
+        self._check(fn(self.h, out.ctypes.data, src_ptr, nbytes))
+        return out
 
     def synchronize(self):
         self._check(self.lib.fastp_gpu_synchronize(self.h))

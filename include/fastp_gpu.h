@@ -587,7 +587,9 @@ int fastp_gpu_deflate_bgzf_level(fastp_gpu_ctx* ctx, const uint8_t* text, int64_
  * The loops of src/evaluator.cpp that scan a prefix of the input before the workers start, run on packed
  * rows already in HBM (DEVICE pointers seq / qual / len as in fastp_gpu_batch, one mate at a time; n reads
  * are available - the reference's own read / base limits are applied inside).  What the reference does with
- * the numbers afterwards (top-10 seeds, NucleotideTree walks, known-adapter names) stays in its Evaluator.
+ * the numbers afterwards (the 10000-read gate, the top-10 seeds and their fold / complexity tests, the assembly
+ * of the adapter from a seed's two paths, known-adapter names) stays in its Evaluator: these calls are its counting
+ * and scanning loops, not its decisions (fastp_amd/evaluator.py strings them together for hosts without one).
  *
  * fastp_gpu_eval_seq_len: Evaluator::computeSeqLen (evaluator.cpp:54-76) - the longest of the first 1000 reads.
  *
@@ -610,6 +612,35 @@ int fastp_gpu_eval_adapter_kmers(fastp_gpu_ctx* ctx, const uint8_t* seq, const u
 int fastp_gpu_eval_overrep(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len, int32_t n,
                            int32_t seq_len, char* text, int64_t text_capacity, int64_t* off /* [max_seqs + 1] */,
                            int64_t* count /* [max_seqs] */, int32_t max_seqs, int32_t* n_seqs);
+
+/* fastp_gpu_eval_known_adapters: the loop of Evaluator::checkKnownAdapters (evaluator.cpp:242-305) over the caller's
+ * list (HOST strings; the reference passes the keys of getKnownAdapter()).  Every adapter is tried at every position
+ * pos < len - 8 of a read it is shorter than: the first position at which at most cmplen / 16 of the first
+ * cmplen = min(len - pos, adapter length) bases differ counts (an N in the read differs from every base).  The loop's
+ * order is kept: reads in input order, adapters in std::map order (byte order of the strings, whatever order the list
+ * is in), an adapter skipped once curMaxCount > 20 and its count < curMaxCount / 10, the loop left after 100000 reads
+ * or once curMaxCount > 1000.  Results (HOST), indexed as the caller's list: counts[i] / mismatches[i] =
+ * possibleCounts / mismatches of adapter i, *checked_reads = checkedReads, *best = the adapter the function returns
+ * (:291-305: the first in map order with the largest count, if that is > checked / 50, or > checked / 200 with fewer
+ * than `checked` mismatches) or -1.  The `records < 10000` gate (:357) and the `size() > 8` test on the result (:367)
+ * are the caller's.  FASTP_GPU_E_INVALID: an empty string, a letter outside ACGT, the same string twice (the map
+ * would hold it once).  FASTP_GPU_E_UNSUPPORTED: more than FASTP_GPU_MAX_ADAPTER_LEN bases, more than 1024 adapters.
+ * n_adapters == 0 or n == 0: *best = -1.
+ *
+ * fastp_gpu_eval_adapter_seed: what Evaluator::getAdapterWithSeed (evaluator.cpp:485-520) computes from the reads
+ * for one seed (a bin of the histogram above; reads admitted as there).  A hit is a (read, pos) with 20 <= pos <=
+ * len - 10 - max(1, trim_tail1), pos < 500, whose ten bases are the seed's; *hits counts them.  forward /
+ * backward (HOST char[FASTP_GPU_MAX_READ_LEN], not terminated) are NucleotideTree::getDominantPath
+ * (nucleotidetree.cpp:57-88) of the tree of the hits' bases [pos + 10, len - max(1, trim_tail1)) and of the tree of
+ * their bases pos - 1 down to 0, each sequence cut at its first N: at every depth the base that at least 95 % of the
+ * sequences still on the path carry, until fewer than 50 are left; *reached_leaf = 0 if either walk ended because no
+ * base had 95 %, else 1.  backward is the path as the tree returns it (the caller reverses it, :522). */
+int fastp_gpu_eval_known_adapters(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len,
+                                  int32_t n, const char* const* adapters, int32_t n_adapters, int32_t* counts /* [n_adapters] */,
+                                  int32_t* mismatches /* [n_adapters] */, int64_t* checked_reads, int32_t* best);
+int fastp_gpu_eval_adapter_seed(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len,
+                                int32_t n, int32_t trim_tail1, uint32_t seed, char* forward, int32_t* forward_len,
+                                char* backward, int32_t* backward_len, int32_t* reached_leaf, int64_t* hits);
 
 /* Process one batch whose buffers (and result buffers) live in HOST memory:
  * H2D copy, kernels, D2H copy, synchronous. */

@@ -86,4 +86,34 @@ timed("eval_adapter_kmers", lambda: g.eval_adapter_kmers(mem.ptr(m0["seq"]), mem
       min(c["n"], 256 * 1024) * 150)
 sl = g.eval_seq_len(mem.ptr(m0["lens"]), c["n"])
 timed("eval_overrep", lambda: g.eval_overrep(mem.ptr(m0["seq"]), mem.ptr(m0["qual"]), mem.ptr(m0["lens"]), c["n"], sl), 1510000)
+# checkKnownAdapters: 100,000 random 150-base reads against 234 synthetic adapters of 19..119 bases (mean 55: the shape of the
+# reference's list), once with no adapter in the reads and once with one read in 20 carrying one; then one seed's extension
+rng = np.random.default_rng(2)
+acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+alens = np.clip(np.rint(rng.gamma(4.0, 55.0 / 4.0, size=234)), 19, 119).astype(int)
+adapters = [bytes(acgt[rng.integers(0, 4, size=int(k))]) for k in alens]
+kn, kL = 100000, 150
+for every in (0, 20):
+    seq = acgt[rng.integers(0, 4, size=(kn, kL + 2))]
+    for i in (range(0, kn, every) if every else ()):
+        a = np.frombuffer(adapters[int(rng.integers(0, 234))], dtype=np.uint8)
+        at = int(rng.integers(20, 120))
+        m = min(len(a), kL - at)
+        seq[i, at:at + m] = a[:m]
+    qual = np.full((kn, kL + 2), ord("I"), dtype=np.uint8)
+    fq = synth.to_fastq(seq, qual, np.full(kn, kL, dtype=np.int32), 1)
+    ck = format_util._prepare(g, mem, fq, fq, 150)["mates"][0]
+    rows = (mem.ptr(ck["seq"]), mem.ptr(ck["qual"]), mem.ptr(ck["lens"]))
+    box = {}
+    def known():
+        box["r"] = g.eval_known_adapters(*rows, kn, adapters)
+    timed(f"eval_known_adapters ({'no adapters' if not every else 'one read in %d carries one' % every})", known, kn * kL, reps=3)
+    print("checked reads", box["r"][3], "largest count", int(box["r"][1].max()), "best", box["r"][4])
+    seed = 0
+    for ch in adapters[0][:10]:   # Evaluator::seq2int of the first adapter's head
+        seed = (seed << 2) | b"ATCG".index(ch)
+    def ext():
+        box["s"] = g.eval_adapter_seed(*rows, kn, 0, seed)
+    timed("eval_adapter_seed (the head of adapter 0)", ext, kn * kL, reps=3)
+    print("hits", box["s"][4], "forward", len(box["s"][1]), "backward", len(box["s"][2]))
 g.close()
