@@ -246,6 +246,11 @@ extern "C" __global__ void __launch_bounds__(64 * TEXT_WAVES) fq_text_kernel(Tex
 }
 extern "C" __global__ void __launch_bounds__(256) fq_text_mask_kernel(TextMaskArgs m) { text_mask_body(m); }
 extern "C" __global__ void __launch_bounds__(256) fq_reduce_kernel(ReduceArgs r) { reduce_body(r); }
+// the Stats fold of a launch with more than REDUCE_GROUP Stats slabs (fold_slabs); runs behind the Stats kernel, not beside it
+extern "C" __global__ void __launch_bounds__(WIDE_THREADS) fq_reduce_wide_kernel(ReduceArgs r) {
+    extern __shared__ u32 fq_lds[];  // WIDE_LDS_DWORDS: the partial sums of a workgroup's waves
+    reduce_wide_body(r, fq_lds);
+}
 extern "C" __global__ void __launch_bounds__(256) fq_dup_claim_kernel(DupArgs d) { dup_claim_body(d); }
 extern "C" __global__ void __launch_bounds__(256) fq_dup_losers_kernel(DupArgs d) { dup_losers_body(d); }
 extern "C" __global__ void __launch_bounds__(256) fq_dup_winners_kernel(DupArgs d) { dup_winners_body(d); }
@@ -302,6 +307,8 @@ struct fastp_gpu_ctx {
     u32* d_corr_chain = nullptr; size_t corr_chain_cap = 0;  // their per-read chains: head[reads] | next[capacity]
     int st_form = 4, st_max_reads = CYC_MAX_READS, st_max_grid = 0;   // the Stats kernel's form: 5 (fq_stats5.h) where it fits, else 4 (fq_stats.h)
     stats5_kernel_fn st5_fn = nullptr; int st5_inst = -1;   // form 5: the instantiation this context launches (stats5_inst_for), chosen at create
+    int finish_threads = 1024;   // fq_dup_finish_kernel's workgroup: the largest whose waves fit beside the Stats kernel's (finish_threads_beside, at create)
+    int last_stats_fold = -1;    // which fold the most recent launch's Stats fold took (FOLD_GROUPS / FOLD_WIDE; -1: none yet)
     // Argument blocks with their constant part filled once (fill_arg_templates, at the end of fastp_gpu_create): a launch copies the
     // block and sets what differs per launch - pointers, n, first, units per block, debug_skip.  The Stats kernel's geometry (H, Hs,
     // kc, H16, its LDS offsets) lives in t_stats only: create's sizing writes it there.
@@ -1015,19 +1022,30 @@ extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fast
     CREATE_TRY(hipStreamSynchronize(ctx->stream));
     fill_arg_templates(ctx);
 #ifndef FQ_HOSTSIM
-    if (sw.verbose && ctx->split && ctx->st_form == 5) {   // what stays free beside the Stats kernel's waves, and for whom
+    if (ctx->split && ctx->st_form == 5) {   // what stays free beside the Stats kernel's waves, and for whom
         int32_t kr[KERNEL_REGS_N];
         CREATE_RC(fastp_gpu_debug_kernel_regs(ctx, kr, KERNEL_REGS_N));
         const int waves = ctx->st_threads / 64 / 4, alloc = (kr[1] + 7) & ~7, left = 512 - waves * alloc;
-        const char* names[4] = {"fq_reduce_kernel", "fq_dup_losers_kernel", "fq_dup_winners_kernel", "fq_dup_finish_kernel"};
-        std::string fits;
-        for (int k = 0; k < 4; k++) {   // a workgroup of the kernel (its launch bound: 256 lanes = a wave per SIMD, 1024 = four) in what is left
-            const int a8 = (kr[4 + 3 * k] + 7) & ~7, wg_waves = std::max(1, kr[5 + 3 * k] / 64 / 4);
-            if (a8 * wg_waves <= left)
-                fits += std::string(fits.empty() ? "" : ", ") + names[k] + " (" + std::to_string(wg_waves) + " x " + std::to_string(a8) + ")";
+        // Duplicate's finish is a grid-stride loop over the units: any workgroup size does.  As 1024 lanes (four waves per SIMD) it
+        // never fitted what the Stats kernel leaves, waited for that kernel's workgroups to go and ended the step behind it; the
+        // largest size that fits runs beside it like losers and winners do.  Nothing fits beside a 128-VGPR instantiation: 1024 stays.
+        // Paired contexts only: a single-end unit has half the bases, the Stats kernel ends BEFORE Duplicate's chain does (10 M reads:
+        // 540 us against 40 + 230 + 320), and alone on the chip finish is slower in small workgroups - 234 us against 67, four times
+        // the workgroups and as many adds to one counter (profiles/r08_a_step_tail.txt: the single-end step was 8 - 10 % slower).
+        const int finish_a8 = (kr[13] + 7) & ~7;
+        for (int t = 1024; t >= 256 && ctx->dp.paired; t >>= 1)
+            if (kr[13] > 0 && t <= kr[14] && (t / 256) * finish_a8 <= left) { ctx->finish_threads = t; break; }
+        if (sw.verbose) {
+            const char* names[4] = {"fq_reduce_kernel", "fq_dup_losers_kernel", "fq_dup_winners_kernel", "fq_dup_finish_kernel"};
+            std::string fits;
+            for (int k = 0; k < 4; k++) {   // a workgroup of the kernel as launched (256 lanes = a wave per SIMD, 1024 = four) in what is left
+                const int a8 = (kr[4 + 3 * k] + 7) & ~7, wg_waves = std::max(1, (k == 3 ? ctx->finish_threads : kr[5 + 3 * k]) / 64 / 4);
+                if (a8 * wg_waves <= left)
+                    fits += std::string(fits.empty() ? "" : ", ") + names[k] + " (" + std::to_string(wg_waves) + " x " + std::to_string(a8) + ")";
+            }
+            fprintf(stderr, "fastp_gpu: stats kernel instantiation %d: %d VGPRs (allocated %d), %d waves per SIMD, %d registers per SIMD left; a workgroup fits beside it of: %s; fq_dup_finish_kernel runs as %d lanes\n",
+                    ctx->st5_inst, kr[1], alloc, waves, left, fits.empty() ? "none" : fits.c_str(), ctx->finish_threads);
         }
-        fprintf(stderr, "fastp_gpu: stats kernel instantiation %d: %d VGPRs (allocated %d), %d waves per SIMD, %d registers per SIMD left; a workgroup fits beside it of: %s\n",
-                ctx->st5_inst, kr[1], alloc, waves, left, fits.empty() ? "none" : fits.c_str());
     }
 #endif
     fq::timeline("create: end (tables uploaded, bloom filter cleared)");
@@ -1614,7 +1632,10 @@ static int dup_decide(Launch& l, const DupArgs& d, bool claimed, hipStream_t st)
     HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(fq_dup_winners_kernel, dim3(g2), dim3(256), 0, st, d);
     HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(fq_dup_finish_kernel, dim3(std::max(1, (l.n + 1023) / 1024)), dim3(1024), 16, st, d);
+    // (1024 unless a smaller workgroup is what fits beside the Stats kernel, fastp_gpu_create - and this launch's finish runs there:
+    // on the tail stream, in front of a Stats kernel; alone on the chip the large workgroup is the faster one)
+    const int ft = st == ctx->tail && l.p.stats ? ctx->finish_threads : 1024;
+    hipLaunchKernelGGL(fq_dup_finish_kernel, dim3(std::max(1, (l.n + ft - 1) / ft)), dim3(ft), 16, st, d);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -1804,16 +1825,20 @@ static int launch_corr_stats(Launch& l) {
 
 // The slab folds.  FOLD_STATS in a split plan: the Stats kernel's slabs (per-cycle u64s, k-mer counters, one histogram counter per
 // (slot, character)); FOLD_MISC: the per-read kernel's slabs, the MISC_* counters only; both at once: the fused kernel's slabs
+// Which kernel: FOLD_GROUPS is fq_reduce_kernel (a lane per slab element and group of REDUCE_GROUP slabs, a serial walk), FOLD_WIDE
+// fq_reduce_wide_kernel (the same item over a larger group, split over a workgroup's waves, WIDE_UNROLL loads in flight; Stats slabs only).  FOLD_AUTO, what a launch asks for:
+// the wide one where the Stats fold has more than one slab group, i.e. where the serial walk is REDUCE_GROUP loads long and the
+// grid under a wave per SIMD; every smaller fold and every MISC fold is fq_reduce_kernel as before.
 enum { FOLD_STATS = 1, FOLD_MISC = 2 };
-static int fold(Launch& l, int parts, hipStream_t st) {
-    fastp_gpu_ctx* ctx = l.ctx;
-    const bool lane = l.p.kernel == K_LANE;
+enum { FOLD_AUTO = -1, FOLD_GROUPS = 0, FOLD_WIDE = 1 };
+// stats_slabs / nblocks: the slabs of a FOLD_STATS fold (the launch's own, or a caller's: fastp_gpu_debug_stats_fold)
+static int fold_slabs(fastp_gpu_ctx* ctx, int parts, bool lane, const u32* stats_slabs, int nblocks, hipStream_t st, int which) {
     ReduceArgs r = ctx->t_reduce;
     r.parts = parts;
     if (parts == FOLD_STATS) {
-        r.slabs = ctx->d_st_slabs;
+        r.slabs = stats_slabs;
         r.slab_dwords = ctx->st_slab_dwords;
-        r.nblocks = l.st_grid;
+        r.nblocks = nblocks;
         r.off_kmer = 4 * N_CLS * ctx->L.Cp * 2;
         r.off_qh = r.off_kmer + 4 * KMER_BINS;
         r.qh_stride = 1;
@@ -1821,7 +1846,7 @@ static int fold(Launch& l, int parts, hipStream_t st) {
     } else {
         r.slabs = lane ? ctx->d_ln_slabs : ctx->d_slabs;
         r.slab_dwords = lane ? ctx->ln_lds.n_misc : ctx->slab_dwords;
-        r.nblocks = lane ? l.ln_grid : l.grid;
+        r.nblocks = nblocks;
         r.off_misc = lane ? 0 : ctx->L.acc_misc - ctx->L.acc_cyc;
         r.off_kmer = ctx->L.acc_kmer - ctx->L.acc_cyc;
         r.off_qh = ctx->L.acc_qh - ctx->L.acc_cyc;
@@ -1831,10 +1856,42 @@ static int fold(Launch& l, int parts, hipStream_t st) {
     if (r.nblocks <= 0) return 0;
     const int n_stats = 4 * N_CLS * ctx->L.Cp + 4 * KMER_BINS + 4 * 128, n_misc = MISC_ISIZE + r.isize_max + 1 + (r.merge_tail ? (int)KMER_BINS : 0);
     const int items = ((parts & FOLD_STATS) ? n_stats : 0) + ((parts & FOLD_MISC) ? n_misc : 0);
-    const int rgroups = (r.nblocks + REDUCE_GROUP - 1) / REDUCE_GROUP;
-    hipLaunchKernelGGL(fq_reduce_kernel, dim3(((items + 255) / 256) * rgroups), dim3(256), 0, st, r);
+    const bool wide = parts == FOLD_STATS && (which == FOLD_WIDE || (which == FOLD_AUTO && r.nblocks > REDUCE_GROUP));
+    if (parts == FOLD_STATS) ctx->last_stats_fold = wide ? FOLD_WIDE : FOLD_GROUPS;
+    if (wide) {
+        const int wgroups = (r.nblocks + WIDE_GROUP - 1) / WIDE_GROUP;
+        hipLaunchKernelGGL(fq_reduce_wide_kernel, dim3(((items + WIDE_ITEMS - 1) / WIDE_ITEMS) * wgroups), dim3(WIDE_THREADS), (size_t)WIDE_LDS_DWORDS * 4, st, r);
+    } else {
+        const int rgroups = (r.nblocks + REDUCE_GROUP - 1) / REDUCE_GROUP;
+        hipLaunchKernelGGL(fq_reduce_kernel, dim3(((items + 255) / 256) * rgroups), dim3(256), 0, st, r);
+    }
     HIP_TRY(ctx, hipGetLastError());
     return 0;
+}
+static int fold(Launch& l, int parts, hipStream_t st) {
+    const bool lane = l.p.kernel == K_LANE;
+    return fold_slabs(l.ctx, parts, lane, l.ctx->d_st_slabs, parts == FOLD_STATS ? l.st_grid : lane ? l.ln_grid : l.grid, st, FOLD_AUTO);
+}
+
+// debugging aid (not part of the drop-in surface): the Stats fold on its own, and what the context chose for the step's tail.
+// slabs != nullptr: fold `nblocks` device slabs of this context's Stats-slab layout ([nblocks][info[2]] dwords, 8-byte aligned: per
+// slot, cycle (info[3] of them, the first info[4] in use) and class one packed u64, then 4 x KMER_BINS and 4 x 128 counters) into
+// the context's counter block, on the context's stream, through fold_slabs as a launch does: which = 0 fq_reduce_kernel, 1 the wide
+// fold, -1 what a launch of that many slabs takes.  The slabs stay the caller's and must outlive the fold (fastp_gpu_synchronize).
+// info (n >= 9): {fq_dup_finish_kernel's workgroup size, the fold the most recent Stats fold took (0 / 1 as above, -1: none yet),
+// slab dwords, Cp, C, REDUCE_GROUP, WIDE_GROUP, WIDE_UNROLL, WIDE_PARTS}.
+extern "C" int fastp_gpu_debug_stats_fold(fastp_gpu_ctx* ctx, const void* slabs, int32_t nblocks, int32_t which, int32_t* info, int32_t n) {
+    if (!ctx || !info || n < 9) return FASTP_GPU_E_INVALID;
+    if (slabs) {
+        if (!ctx->split || ctx->st_slab_dwords <= 0) return fail(ctx, FASTP_GPU_E_INVALID, "the context has no Stats slabs");
+        if (nblocks < 0 || which < FOLD_AUTO || which > FOLD_WIDE || ((size_t)slabs & 7)) return fail(ctx, FASTP_GPU_E_INVALID, "bad slab fold arguments");
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const int rc = fold_slabs(ctx, FOLD_STATS, false, (const u32*)slabs, nblocks, ctx->stream, which);
+        if (rc) return rc;
+    }
+    const int32_t out[9] = {ctx->finish_threads, ctx->last_stats_fold, ctx->st_slab_dwords, ctx->L.Cp, ctx->L.C, REDUCE_GROUP, WIDE_GROUP, WIDE_UNROLL, WIDE_PARTS};
+    for (int i = 0; i < 9; i++) info[i] = out[i];
+    return FASTP_GPU_OK;
 }
 
 // the tail stream goes on from where the launch stream is now

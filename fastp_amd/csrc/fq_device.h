@@ -2412,6 +2412,45 @@ struct ReduceArgs {
 #endif
 enum { REDUCE_GROUP = FQ_REDUCE_GROUP };
 
+// where a folded sum goes (reduce_body and reduce_wide_body share the mapping).  A per-cycle cell of (slot, cycle c, class):
+FQ_DEV void reduce_emit_cycle(const ReduceArgs& r, int slot, int c, int cls, int64_t cnt, int64_t q20, int64_t q30, int64_t qs) {
+    const int64_t CC = r.cycles;
+    const int bin = (int)sym_bin((u32)cls);  // 'A'&7=1 'T'&7=4 'C'&7=3 'G'&7=7 'N'&7=6
+    const bool tail = r.merge_tail && slot == 3;
+    for (int tgt = tail ? 1 : slot; tgt >= 0; tgt -= 1) {
+        int64_t* st = r.ctr + r.o_stats[tgt] + r.st_cycle;  // Stats::mCycleBuffer layout (stats.cpp:54-63)
+        // the POST Stats of a front-trimmed mate: cycle c of the original read is cycle c - front of the read that is written out
+        const int cc = (r.one_pass && (tgt & 1)) ? c - r.front[tgt >> 1] : c;
+        if (cc >= 0) {
+            if (q30) g_atomic_add_i64(&st[(0 * 8 + bin) * CC + cc], q30);  // mCycleQ30Bases
+            if (q20) g_atomic_add_i64(&st[(1 * 8 + bin) * CC + cc], q20);  // mCycleQ20Bases
+            g_atomic_add_i64(&st[(2 * 8 + bin) * CC + cc], cnt);           // mCycleBaseContents
+            g_atomic_add_i64(&st[(3 * 8 + bin) * CC + cc], qs);            // mCycleBaseQual
+            g_atomic_add_i64(&st[32 * CC + cc], cnt);                      // mCycleTotalBase
+            g_atomic_add_i64(&st[33 * CC + cc], qs);                       // mCycleTotalQual
+        }
+        if (tail || !(r.one_pass && (tgt & 1))) break;  // kept -> also the PRE Stats of the mate
+    }
+}
+// ... a 5-mer counter, k = slot * KMER_BINS + the LDS index of the 5-mer
+FQ_DEV void reduce_emit_kmer(const ReduceArgs& r, int k, int64_t sum) {
+    const int slot = k / KMER_BINS, km = k - slot * KMER_BINS;
+    // LDS index has the earliest base in the low bits; fastp's has it in the high bits
+    const u32 fk = ((km & 3u) << 8) | (((km >> 2) & 3u) << 6) | (((km >> 4) & 3u) << 4) | (((km >> 6) & 3u) << 2) |
+                   ((km >> 8) & 3u);
+    if (r.merge_tail && slot == 3) { g_atomic_add_i64(&r.ctr[r.o_stats[1] + r.st_kmer + fk], sum); return; }
+    g_atomic_add_i64(&r.ctr[r.o_stats[slot] + r.st_kmer + fk], sum);
+    if (r.one_pass && (slot & 1)) g_atomic_add_i64(&r.ctr[r.o_stats[slot - 1] + r.st_kmer + fk], sum);
+}
+// ... a quality histogram counter, k = slot * 128 + the quality character
+FQ_DEV void reduce_emit_qhist(const ReduceArgs& r, int k, int64_t sum) {
+    const int slot = k / 128, q = k - slot * 128;
+    if (q == 0) return;  // character 0 = "no base" (bytes past a read's end): never a real quality (>= '!')
+    if (r.merge_tail && slot == 3) { g_atomic_add_i64(&r.ctr[r.o_stats[1] + r.st_qual_hist + q], sum); return; }
+    g_atomic_add_i64(&r.ctr[r.o_stats[slot] + r.st_qual_hist + q], sum);
+    if (r.one_pass && (slot & 1)) g_atomic_add_i64(&r.ctr[r.o_stats[slot - 1] + r.st_qual_hist + q], sum);
+}
+
 FQ_DEV void reduce_body(const ReduceArgs& r) {
     const LdsLayout& L = r.L;
     const int C = L.C, Cp = L.Cp;
@@ -2427,7 +2466,6 @@ FQ_DEV void reduce_body(const ReduceArgs& r) {
     item += lo;
     const int b0 = g * REDUCE_GROUP, b1 = imin(r.nblocks, b0 + REDUCE_GROUP);
     if (b0 >= b1) return;
-    const int64_t CC = r.cycles;
     if (item < n_cyc) {
         const int slot = item / (N_CLS * Cp);   // cyc_index: [slot][cycle][class]
         const int rem = item - slot * N_CLS * Cp;
@@ -2443,22 +2481,7 @@ FQ_DEV void reduce_body(const ReduceArgs& r) {
             qs += (int64_t)(v >> CYC_QSUM_SHIFT);
         }
         if (!(cnt | qs)) return;
-        const int bin = (int)sym_bin((u32)cls);  // 'A'&7=1 'T'&7=4 'C'&7=3 'G'&7=7 'N'&7=6
-        const bool tail = r.merge_tail && slot == 3;
-        for (int tgt = tail ? 1 : slot; tgt >= 0; tgt -= 1) {
-            int64_t* st = r.ctr + r.o_stats[tgt] + r.st_cycle;  // Stats::mCycleBuffer layout (stats.cpp:54-63)
-            // the POST Stats of a front-trimmed mate: cycle c of the original read is cycle c - front of the read that is written out
-            const int cc = (r.one_pass && (tgt & 1)) ? c - r.front[tgt >> 1] : c;
-            if (cc >= 0) {
-                if (q30) g_atomic_add_i64(&st[(0 * 8 + bin) * CC + cc], q30);  // mCycleQ30Bases
-                if (q20) g_atomic_add_i64(&st[(1 * 8 + bin) * CC + cc], q20);  // mCycleQ20Bases
-                g_atomic_add_i64(&st[(2 * 8 + bin) * CC + cc], cnt);           // mCycleBaseContents
-                g_atomic_add_i64(&st[(3 * 8 + bin) * CC + cc], qs);            // mCycleBaseQual
-                g_atomic_add_i64(&st[32 * CC + cc], cnt);                      // mCycleTotalBase
-                g_atomic_add_i64(&st[33 * CC + cc], qs);                       // mCycleTotalQual
-            }
-            if (tail || !(r.one_pass && (tgt & 1))) break;  // kept -> also the PRE Stats of the mate
-        }
+        reduce_emit_cycle(r, slot, c, cls, cnt, q20, q30, qs);
         return;
     }
     int src;   // dword of the slab that holds the item
@@ -2469,21 +2492,9 @@ FQ_DEV void reduce_body(const ReduceArgs& r) {
     for (int b = b0; b < b1; b++) sum += (int64_t)r.slabs[(size_t)b * r.slab_dwords + src];
     if (!sum) return;
     if (item < n_cyc + n_kmer) {
-        const int k = item - n_cyc;
-        const int slot = k / KMER_BINS, km = k - slot * KMER_BINS;
-        // LDS index has the earliest base in the low bits; fastp's has it in the high bits
-        const u32 fk = ((km & 3u) << 8) | (((km >> 2) & 3u) << 6) | (((km >> 4) & 3u) << 4) | (((km >> 6) & 3u) << 2) |
-                       ((km >> 8) & 3u);
-        if (r.merge_tail && slot == 3) { g_atomic_add_i64(&r.ctr[r.o_stats[1] + r.st_kmer + fk], sum); return; }
-        g_atomic_add_i64(&r.ctr[r.o_stats[slot] + r.st_kmer + fk], sum);
-        if (r.one_pass && (slot & 1)) g_atomic_add_i64(&r.ctr[r.o_stats[slot - 1] + r.st_kmer + fk], sum);
+        reduce_emit_kmer(r, item - n_cyc, sum);
     } else if (item < n_stats) {
-        const int k = item - n_cyc - n_kmer;
-        const int slot = k / 128, q = k - slot * 128;
-        if (q == 0) return;  // character 0 = "no base" (bytes past a read's end): never a real quality (>= '!')
-        if (r.merge_tail && slot == 3) { g_atomic_add_i64(&r.ctr[r.o_stats[1] + r.st_qual_hist + q], sum); return; }
-        g_atomic_add_i64(&r.ctr[r.o_stats[slot] + r.st_qual_hist + q], sum);
-        if (r.one_pass && (slot & 1)) g_atomic_add_i64(&r.ctr[r.o_stats[slot - 1] + r.st_qual_hist + q], sum);
+        reduce_emit_qhist(r, item - n_cyc - n_kmer, sum);
     } else {
         const int k = item - n_stats;
         int64_t dst;
@@ -2501,6 +2512,121 @@ FQ_DEV void reduce_body(const ReduceArgs& r) {
         else dst = r.o_stats[1] + r.st_kmer + (k - (MISC_ISIZE + r.isize_max + 1));   // (merge_tail) the junction 5-mers
         g_atomic_add_i64(&r.ctr[dst], sum);
     }
+}
+
+// The wide fold: the Stats kernel's slabs (parts == 1) of a launch with more than one slab group.  reduce_body walks its
+// group in a loop of unknown length, so the compiler keeps one load in flight per lane, and the fold's grid is under one
+// wave per SIMD: the fold ran at the memory system's latency (512 slabs of 43 KB in 68 - 84 us, 5 % of the copy rate).
+// Here a lane issues WIDE_UNROLL independent loads before it sums them, and a per-cycle cell is one 8-byte load (a
+// slab's dword count is even, so a cell is 8-byte aligned in every slab).  What the loads leave is the atomics: about
+// 2 us per slab group, whatever its size (every group adds to the same 3 * 10^4 counters), so smaller groups - more
+// lanes - were slower, not faster.  Hence large groups (WIDE_GROUP slabs), and the lanes come from splitting a group's
+// slabs over the WIDE_PARTS waves of a workgroup: wave p sums slabs p, p + WIDE_PARTS, ... of the group for the
+// workgroup's 256 / WIDE_PARTS items, the partial sums meet in LDS and the first wave adds them to the counters.
+// Measured alone on the chip, 512 slabs of the 2x150 layout (profiles/r08_a_step_tail.txt): fq_reduce_kernel 69 us;
+// one part, groups of 16 / 32 / 64 / 128: 74 / 41 / 27 / 23 us; two parts, 128 / 256: 18 / 18; four parts, 128 / 256 /
+// 512: 18 / 16 / 20; unroll 8 instead of 16 costs 0.5 - 3 us everywhere.
+// Same work item, same counter mapping, same zero sums skipped as reduce_body - the two must stay one mapping
+// (tests/test_stats_fold.py holds them together int64 for int64).  It is a kernel of its own: fq_reduce_kernel has to fit
+// beside the Stats kernel (<= 32 VGPRs, the MISC fold), this one runs behind it.
+#ifndef FQ_WIDE_GROUP
+#define FQ_WIDE_GROUP 256
+#endif
+#ifndef FQ_WIDE_UNROLL
+#define FQ_WIDE_UNROLL 16
+#endif
+#ifndef FQ_WIDE_PARTS
+#define FQ_WIDE_PARTS 4
+#endif
+enum { WIDE_GROUP = FQ_WIDE_GROUP, WIDE_UNROLL = FQ_WIDE_UNROLL, WIDE_PARTS = FQ_WIDE_PARTS, WIDE_THREADS = 256, WIDE_ITEMS = WIDE_THREADS / WIDE_PARTS };
+static_assert(WIDE_GROUP >= 1 && WIDE_GROUP <= 1023, "a group's qsum (22 bits a slab) is summed in 32 bits");
+static_assert(WIDE_PARTS >= 1 && WIDE_ITEMS * WIDE_PARTS == WIDE_THREADS && WIDE_ITEMS % 64 == 0, "a part is whole waves");
+enum { WIDE_LDS_DWORDS = (WIDE_PARTS - 1) * 4 * WIDE_ITEMS };   // [part - 1][4][item]: the partial sums of parts 1 ..
+
+// lds: WIDE_LDS_DWORDS; workgroups of WIDE_THREADS lanes, ceil(items / WIDE_ITEMS) per slab group
+FQ_DEV void reduce_wide_body(const ReduceArgs& r, u32* lds) {
+    const LdsLayout& L = r.L;
+    const int C = L.C, Cp = L.Cp;
+    const int n_cyc = 4 * N_CLS * Cp, n_kmer = 4 * KMER_BINS, n_qh = 4 * 128;
+    const int n_stats = n_cyc + n_kmer + n_qh;
+    const int chunks = (n_stats + WIDE_ITEMS - 1) / WIDE_ITEMS;  // workgroups per slab group
+    const int g = block_id() / chunks;
+    const int part = thread_id() / WIDE_ITEMS, li = thread_id() - part * WIDE_ITEMS;
+    const int item = (block_id() - g * chunks) * WIDE_ITEMS + li;
+    const int b0 = g * WIDE_GROUP + part, b1 = imin(r.nblocks, (g + 1) * WIDE_GROUP);
+    int left = b0 < b1 ? (b1 - b0 + WIDE_PARTS - 1) / WIDE_PARTS : 0;   // slabs of this part: b0, b0 + WIDE_PARTS, ...
+    const bool cyc = item < n_cyc;
+    int slot = 0, c = 0, cls = 0;
+    // a per-cycle cell: cnt, q20, q30, qsum (<= WIDE_GROUP x (2^14 - 1), x (2^22 - 1)); else: the low and the high half of the sum
+    u32 a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+    if (cyc) {
+        slot = item / (N_CLS * Cp);   // cyc_index: [slot][cycle][class]
+        const int rem = item - slot * N_CLS * Cp;
+        c = rem / N_CLS;
+        cls = rem - c * N_CLS;
+        if (c >= C) left = 0;
+        const size_t step = (size_t)(r.slab_dwords >> 1) * WIDE_PARTS;
+        const u64* s = (const u64*)r.slabs + (size_t)b0 * (size_t)(r.slab_dwords >> 1) + item;
+        for (; left >= WIDE_UNROLL; left -= WIDE_UNROLL, s += WIDE_UNROLL * step) {
+            u64 v[WIDE_UNROLL];
+#pragma unroll
+            for (int k = 0; k < WIDE_UNROLL; k++) v[k] = s[(size_t)k * step];
+#pragma unroll
+            for (int k = 0; k < WIDE_UNROLL; k++) {
+                a0 += (u32)v[k] & 0x3FFFu;
+                a1 += (u32)(v[k] >> CYC_Q20_SHIFT) & 0x3FFFu;
+                a2 += (u32)(v[k] >> CYC_Q30_SHIFT) & 0x3FFFu;
+                a3 += (u32)(v[k] >> CYC_QSUM_SHIFT);
+            }
+        }
+        for (; left > 0; left--, s += step) {
+            const u64 v = s[0];
+            a0 += (u32)v & 0x3FFFu;
+            a1 += (u32)(v >> CYC_Q20_SHIFT) & 0x3FFFu;
+            a2 += (u32)(v >> CYC_Q30_SHIFT) & 0x3FFFu;
+            a3 += (u32)(v >> CYC_QSUM_SHIFT);
+        }
+    } else if (item < n_stats) {
+        const int src = item < n_cyc + n_kmer ? r.off_kmer + (item - n_cyc) : r.off_qh + (item - n_cyc - n_kmer) * r.qh_stride + r.qh_count;
+        const size_t step = (size_t)r.slab_dwords * WIDE_PARTS;
+        const u32* s = r.slabs + (size_t)b0 * r.slab_dwords + src;
+        u64 sum = 0;
+        for (; left >= WIDE_UNROLL; left -= WIDE_UNROLL, s += WIDE_UNROLL * step) {
+            u32 v[WIDE_UNROLL];
+#pragma unroll
+            for (int k = 0; k < WIDE_UNROLL; k++) v[k] = s[(size_t)k * step];
+#pragma unroll
+            for (int k = 0; k < WIDE_UNROLL; k++) sum += (u64)v[k];
+        }
+        for (; left > 0; left--, s += step) sum += (u64)s[0];
+        a0 = (u32)sum;
+        a1 = (u32)(sum >> 32);
+    }
+    if (WIDE_PARTS > 1) {
+        if (part) {
+            u32* o = lds + (part - 1) * 4 * WIDE_ITEMS + li;
+            o[0] = a0; o[WIDE_ITEMS] = a1; o[2 * WIDE_ITEMS] = a2; o[3 * WIDE_ITEMS] = a3;
+        }
+        block_sync();
+    }
+    if (part || item >= n_stats) return;
+    if (cyc) {
+        for (int p = 0; p < WIDE_PARTS - 1; p++) {
+            const u32* o = lds + p * 4 * WIDE_ITEMS + li;
+            a0 += o[0]; a1 += o[WIDE_ITEMS]; a2 += o[2 * WIDE_ITEMS]; a3 += o[3 * WIDE_ITEMS];
+        }
+        if (!(a0 | a3)) return;
+        reduce_emit_cycle(r, slot, c, cls, (int64_t)a0, (int64_t)a1, (int64_t)a2, (int64_t)a3);
+        return;
+    }
+    u64 sum = (u64)a0 | ((u64)a1 << 32);
+    for (int p = 0; p < WIDE_PARTS - 1; p++) {
+        const u32* o = lds + p * 4 * WIDE_ITEMS + li;
+        sum += (u64)o[0] | ((u64)o[WIDE_ITEMS] << 32);
+    }
+    if (!sum) return;
+    if (item < n_cyc + n_kmer) reduce_emit_kmer(r, item - n_cyc, (int64_t)sum);
+    else reduce_emit_qhist(r, item - n_cyc - n_kmer, (int64_t)sum);
 }
 
 

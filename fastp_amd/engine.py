@@ -554,6 +554,25 @@ class GpuEngine:
             d[name] = {"vgprs": int(out[1 + 3 * k]), "max_threads": int(out[2 + 3 * k]), "static_lds": int(out[3 + 3 * k])}
         return d
 
+    STATS_FOLDS = {-1: None, 0: "groups", 1: "wide"}
+
+    def debug_stats_fold(self, slabs_ptr: int = 0, nblocks: int = 0, which: str = "auto"):
+        """the Stats fold on its own, and what the context chose for the step's tail.  With slabs_ptr (device memory, 8-byte
+        aligned, [nblocks][slab_dwords] uint32 in the layout the returned dict describes) the slabs are folded into the
+        context's counter block on its stream - which = "groups": fq_reduce_kernel, "wide": fq_reduce_wide_kernel, "auto": what
+        a launch with that many Stats slabs takes; synchronize() before the slabs are freed.  Returns {"finish_threads":
+        fq_dup_finish_kernel's workgroup size, "last_stats_fold": "groups" / "wide" / None, "slab_dwords", "cp" (cycles a
+        slab has cells for), "c" (cycles in use), "reduce_group", "wide_group", "wide_unroll", "wide_parts"}"""
+        out = (C.c_int32 * 9)()
+        fn = self.lib.fastp_gpu_debug_stats_fold
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
+        self._check(fn(self.h, slabs_ptr or None, nblocks, {"auto": -1, "groups": 0, "wide": 1}[which], out, 9))
+        keys = ("finish_threads", "last_stats_fold", "slab_dwords", "cp", "c", "reduce_group", "wide_group", "wide_unroll", "wide_parts")
+        d = {k: int(v) for k, v in zip(keys, out)}
+        d["last_stats_fold"] = self.STATS_FOLDS[d["last_stats_fold"]]
+        return d
+
     def debug_overrep_plan(self):
         """the LDS plan of this context's most recent overrepresentation launch as launch_overrep chose it:
         {"launches": how many so far, "sym_cap": positions of a read staged in LDS (0: none), "table_lds": (dword offset of
