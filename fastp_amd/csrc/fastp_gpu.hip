@@ -22,6 +22,7 @@
 #include "fq_deflate.h"
 #include "fq_inflate_wave.h"
 #include "fq_host.h"
+#include "fq_census.h"
 
 using namespace fq;
 
@@ -240,6 +241,20 @@ extern "C" __global__ void __launch_bounds__(256, 6) fq_fmts7_write_kernel(FmtsA
     extern __shared__ u32 fq_lds[];
     fmts_write_body<FMTS_ALL_STREAMS, 3>(f, fq_lds);
 }
+// the adapter census (fq_census.h): a kernel per phase - the boundary is what hands one phase's writes to the next
+extern "C" __global__ void __launch_bounds__(CS_BLOCK) fq_census_gather_kernel(CsArgs a) { cs_gather_units_body(a); }
+extern "C" __global__ void __launch_bounds__(CS_BLOCK) fq_census_events_kernel(CsArgs a) { cs_gather_events_body(a); }
+extern "C" __global__ void __launch_bounds__(CS_BLOCK) fq_census_hash_kernel(CsArgs a) { cs_hash_body(a); }
+extern "C" __global__ void __launch_bounds__(CS_BLOCK) fq_census_lookup_kernel(CsArgs a) { cs_lookup_body(a); }
+extern "C" __global__ void __launch_bounds__(CS_BLOCK) fq_census_insert_kernel(CsArgs a) { cs_insert_body(a); }
+extern "C" __global__ void __launch_bounds__(CS_BLOCK) fq_census_first_kernel(CsArgs a) { cs_first_body(a); }
+extern "C" __global__ void __launch_bounds__(CS_BLOCK) fq_census_verify_kernel(CsArgs a) { cs_verify_body(a); }
+extern "C" __global__ void __launch_bounds__(256) fq_census_hist_kernel(CsArgs a) {
+    extern __shared__ u32 fq_lds[];  // 256 dwords: the workgroup's histogram
+    cs_hist_body(a, fq_lds);
+}
+extern "C" __global__ void __launch_bounds__(CS_BLOCK) fq_census_admit_kernel(CsArgs a) { cs_admit_body(a); }
+extern "C" __global__ void __launch_bounds__(CS_BLOCK) fq_census_pair_kernel(CsArgs a) { cs_pair_verdict_body(a); }
 extern "C" __global__ void __launch_bounds__(64 * TEXT_WAVES) fq_text_kernel(TextArgs e) {
     extern __shared__ __attribute__((aligned(16))) u32 fq_lds[];
     text_body(*kernel_args(&e), fq_lds);
@@ -283,6 +298,8 @@ struct Switches {
     int inflate;              // FASTP_GPU_INFLATE=lane (1) | wave (2) forces an inflate kernel (0: by size): the parity tests
     int debug_skip;           // FQ_PROFILE_ABLATION builds only (tools/build_ablation.sh, tools/phase_pmc.sh); bench.py refuses it
     int phase_timing;         // per-phase cycle counters: fastp_amd/engine.py, tools/phase_prof.py
+    int census_hash_bits;     // FASTP_GPU_DEBUG_CENSUS_HASH_BITS=<k>: the adapter census keeps the low k bits of its hashes, so that
+                              // different strings share one (the collision path): tests/test_adapter_census.py
 };
 
 struct fastp_gpu_ctx {
@@ -393,6 +410,13 @@ struct fastp_gpu_ctx {
         hipStream_t copy = nullptr;
     } aslot[FASTP_GPU_ASYNC_SLOTS];
     u64* d_phase = nullptr;   // optional per-phase cycle counters (FASTP_GPU_PHASE_TIMING=1)
+    // adapter census (fq_census.h): FilterResult::mAdapter1 / mAdapter2 as two persistent tables, allocated at the first use
+    u8* d_cs_map[2] = {nullptr, nullptr};
+    CsMap cs_map[2] = {};
+    u32 cs_entries[2] = {0, 0};                             // host mirror of the tables' sizes
+    u8* d_cs_blob = nullptr;                                // adapter sequences as bytes | offsets | lengths
+    u8* d_cs_items = nullptr; size_t cs_items_cap = 0;      // a launch's item list | counters | select histogram
+    u8* d_cs_slots = nullptr; size_t cs_slots_cap = 0;      // a launch's dedupe table
     // timing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending_events;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
@@ -436,6 +460,7 @@ static Switches read_switches() {
     w.inflate = !how ? 0 : !strcmp(how, "lane") ? 1 : !strcmp(how, "wave") ? 2 : 3;   // (3: a word that is neither - the wave kernel where it fits)
     w.debug_skip = env_int("FASTP_GPU_DEBUG_SKIP", 0);
     w.phase_timing = env_int("FASTP_GPU_PHASE_TIMING", 0);
+    w.census_hash_bits = env_int("FASTP_GPU_DEBUG_CENSUS_HASH_BITS", 0);
     return w;
 }
 
@@ -482,6 +507,7 @@ extern "C" void fastp_gpu_destroy(fastp_gpu_ctx* ctx) {
                     ctx->d_ovr_table[0], ctx->d_ovr_table[1], ctx->d_ovr_sym[0], ctx->d_ovr_sym[1], ctx->d_ovr_len[0],
                     ctx->d_ovr_len[1], ctx->d_post_seen, ctx->d_ovr_work, ctx->d_parse, ctx->d_fmt, ctx->d_prefix, ctx->d_inf, ctx->d_ovr_corr, ctx->d_eval, ctx->d_def, ctx->d_setw, ctx->d_cfilter,
                     ctx->d_st_slabs, ctx->d_swin[0], ctx->d_swin[1], ctx->d_ln_slabs,
+                    ctx->d_cs_map[0], ctx->d_cs_map[1], ctx->d_cs_blob, ctx->d_cs_items, ctx->d_cs_slots,
                     ctx->d_corr_int, ctx->d_corr_chain, ctx->d_x_unit, ctx->d_x_len, ctx->d_x_skip, ctx->d_al[0], ctx->d_al[1], ctx->d_al[2], ctx->d_al[3], ctx->d_x_text[0], ctx->d_x_text[1], ctx->d_x_off[0], ctx->d_x_off[1]};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
@@ -2552,6 +2578,378 @@ extern "C" int fastp_gpu_format_all_streams(fastp_gpu_ctx* ctx, int32_t n, const
     return format_streams_impl(ctx, FMTS_ALL_STREAMS, n, m1, m2, pair, corrections, n_corrections, opts, out, out_capacity, out_len);
 }
 
+// ---- adapter census (fq_census.h) -----------------------------------------------------------------------------------------
+// One persistent table per map in one allocation: ehash | ecount | index | eoff | elen | ctl | arena (a key is at most
+// FASTP_GPU_MAX_READ_LEN bytes: a piece of a sequence line or of an adapter sequence).
+static const size_t CS_KEY_MAX = FASTP_GPU_MAX_READ_LEN;
+static u64 cs_hash_mask(const fastp_gpu_ctx* ctx) {
+    const int k = ctx->sw.census_hash_bits;
+    return (k <= 0 || k >= 64) ? ~(u64)0 : (((u64)1 << k) - 1);
+}
+static u64 cs_host_hash(const u8* p, u32 len, u64 mask) {
+    u64 sum = 0;
+    for (u32 k = 0; k < len; k++) sum += cs_term(k, p[k], 0);
+    return cs_finish(sum, len, 0, mask);
+}
+static size_t cs_map_header_bytes() {
+    return (size_t)CS_MAX_ENTRIES * 16 + (size_t)CS_INDEX_SLOTS * 4 + (size_t)CS_MAX_ENTRIES * 8 + 16;
+}
+static int cs_ensure_maps(fastp_gpu_ctx* ctx) {
+    if (ctx->d_cs_map[0]) return 0;
+    const size_t E = CS_MAX_ENTRIES, head = cs_map_header_bytes(), arena = E * CS_KEY_MAX;
+    for (int w = 0; w < 2; w++) {
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_cs_map[w], head + arena));
+        u8* b = ctx->d_cs_map[w];
+        CsMap& m = ctx->cs_map[w];
+        m.ehash = (u64*)b;
+        m.ecount = m.ehash + E;
+        m.index = (u32*)(m.ecount + E);
+        m.eoff = m.index + CS_INDEX_SLOTS;
+        m.elen = m.eoff + E;
+        m.ctl = m.elen + E;
+        m.arena = (u8*)(m.ctl + 4);
+        m.arena_cap = (u32)arena;
+        HIP_TRY(ctx, hipMemsetAsync(b, 0, head, ctx->stream));
+        ctx->cs_entries[w] = 0;
+    }
+    // the adapter sequences a string with adapter_pos < 0 is cut from: -a, --adapter_sequence_r2, the --adapter_fasta entries
+    std::vector<const std::string*> seqs = {&ctx->adapter1, &ctx->adapter2};
+    for (auto& f : ctx->fasta_strings) seqs.push_back(&f);
+    std::vector<u32> off(seqs.size()), len(seqs.size());
+    std::string bytes;
+    for (size_t k = 0; k < seqs.size(); k++) {
+        off[k] = (u32)bytes.size();
+        len[k] = (u32)seqs[k]->size();
+        bytes += *seqs[k];
+    }
+    const size_t tab = seqs.size() * 4, total = 2 * tab + bytes.size() + 8;
+    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_cs_blob, total));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cs_blob, off.data(), tab, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cs_blob + tab, len.data(), tab, hipMemcpyHostToDevice, ctx->stream));
+    if (!bytes.empty()) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cs_blob + 2 * tab, bytes.data(), bytes.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (the host vectors go out of scope)
+    return 0;
+}
+static int cs_clear_map(fastp_gpu_ctx* ctx, int w) {
+    if (ctx->d_cs_map[w]) HIP_TRY(ctx, hipMemsetAsync(ctx->d_cs_map[w], 0, cs_map_header_bytes(), ctx->stream));
+    ctx->cs_entries[w] = 0;
+    return 0;
+}
+static int cs_read_words(fastp_gpu_ctx* ctx, const u32* dev, u32* host, int n) {
+    HIP_TRY(ctx, hipMemcpyAsync(host, dev, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+#define CS_LAUNCH(kernel, threads, args)                                                                               \
+    do {                                                                                                               \
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(((size_t)(threads) + CS_BLOCK - 1) / CS_BLOCK)), dim3(CS_BLOCK), 0, ctx->stream, args); \
+        HIP_TRY(ctx, hipGetLastError());                                                                               \
+    } while (0)
+
+// the K-th smallest (K >= 1) first occurrence among the dedupe slots with key >= lo [whose string is not low complexity]:
+// one 8-bit digit per pass from the top.  *total = how many such slots there are; fewer than K: *key is not set.
+static int cs_select(fastp_gpu_ctx* ctx, CsArgs a, u64 K, u64 lo, int nonlc, u64* total, u64* key) {
+    u64 prefix = 0;
+    u32 hist[256];
+    a.sel_lo = lo;
+    a.sel_nonlc = nonlc;
+    const unsigned grid = (unsigned)std::min<size_t>(((size_t)a.n_slots + 255) / 256, 1024);
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        a.sel_shift = shift;
+        a.sel_top = shift == 56;
+        a.sel_prefix = prefix;
+        HIP_TRY(ctx, hipMemsetAsync(a.hist, 0, sizeof(hist), ctx->stream));
+        hipLaunchKernelGGL(fq_census_hist_kernel, dim3(grid), dim3(256), 256 * 4, ctx->stream, a);
+        HIP_TRY(ctx, hipGetLastError());
+        int rc = cs_read_words(ctx, a.hist, hist, 256);
+        if (rc) return rc;
+        if (shift == 56) {
+            u64 t = 0;
+            for (u32 v : hist) t += v;
+            *total = t;
+            if (t < K) return 0;
+        }
+        u64 run = 0;
+        int d = 0;
+        for (; d < 256; d++) {
+            if (run + hist[d] >= K) break;
+            run += hist[d];
+        }
+        if (d == 256) return fail(ctx, FASTP_GPU_E_HIP, "adapter census: the select lost its key");
+        K -= run;
+        prefix = (prefix << 8) | (u64)d;
+    }
+    *key = prefix;
+    return 0;
+}
+
+// phases 2 - 4 for one map: look-up, candidate dedupe, admission
+static int cs_run_map(fastp_gpu_ctx* ctx, CsArgs& a, int w) {
+    a.which = w;
+    a.map = ctx->cs_map[w];
+    a.salt = 0;
+    u32 ctl[CS_CTL_WORDS];
+    HIP_TRY(ctx, hipMemsetAsync(a.ctl + CS_CTL_CAND, 0, 3 * 4, ctx->stream));   // candidates, unresolved, slots
+    CS_LAUNCH(fq_census_lookup_kernel, (size_t)a.n_items * CS_GROUP, a);
+    int rc = cs_read_words(ctx, a.ctl, ctl, CS_CTL_WORDS);
+    if (rc) return rc;
+    const u32 ncand = ctl[CS_CTL_CAND];
+    if (ncand == 0) return 0;
+    // the dedupe table: a power of two of at least twice the candidates
+    size_t ns = 64;
+    while (ns < 2 * (size_t)ncand) ns <<= 1;
+    rc = ensure(ctx, (void**)&ctx->d_cs_slots, &ctx->cs_slots_cap, ns * 28);
+    if (rc) return rc;
+    a.n_slots = (int)ns;
+    a.s_word = (u64*)ctx->d_cs_slots;
+    a.s_first = a.s_word + ns;
+    a.s_item = (u32*)(a.s_first + ns);
+    a.s_count = a.s_item + ns;
+    a.s_verdict = a.s_count + ns;
+    HIP_TRY(ctx, hipMemsetAsync(a.s_word, 0, ns * 8, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(a.s_first, 0xFF, ns * 8, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(a.s_item, 0, ns * 12, ctx->stream));
+    // every round settles at least the string of each claimed slot's first item, so there are at most ncand rounds
+    for (u32 round = 0;; round++) {
+        if (round > ncand) return fail(ctx, FASTP_GPU_E_HIP, "adapter census: the candidate dedupe did not converge");
+        HIP_TRY(ctx, hipMemsetAsync(a.ctl + CS_CTL_UNRESOLVED, 0, 4, ctx->stream));
+        CS_LAUNCH(fq_census_insert_kernel, a.n_items, a);
+        CS_LAUNCH(fq_census_first_kernel, a.n_items, a);
+        CS_LAUNCH(fq_census_verify_kernel, (size_t)a.n_items * CS_GROUP, a);
+        rc = cs_read_words(ctx, a.ctl, ctl, CS_CTL_WORDS);
+        if (rc) return rc;
+        if (ctl[CS_CTL_UNRESOLVED] == 0) break;
+        a.salt = round + 1;   // two strings shared a hash: the ones that lost are hashed again, under another salt
+        a.want_state = CS_CAND;
+        CS_LAUNCH(fq_census_hash_kernel, (size_t)a.n_items * CS_GROUP, a);
+    }
+    // admission: everything while size <= 5000, then what is not low complexity while size <= 20000 - as two bounds on the
+    // order key of the first occurrence (key < x1, or not low complexity and key < x2)
+    const u64 D = ctl[CS_CTL_SLOTS], S0 = ctx->cs_entries[w], ALL = ~(u64)0;
+    const u64 KA = S0 <= CS_LOW_COMPLEXITY_SKIP ? (u64)CS_LOW_COMPLEXITY_SKIP + 1 - S0 : 0;
+    a.x1 = ALL;
+    a.x2 = 0;
+    if (KA < D) {
+        a.x1 = 0;
+        u64 total = 0, key = 0;
+        if (KA > 0) {
+            rc = cs_select(ctx, a, KA, 0, 0, &total, &key);
+            if (rc) return rc;
+            if (total < KA) return fail(ctx, FASTP_GPU_E_HIP, "adapter census: fewer dedupe slots than were claimed");
+            a.x1 = key + 1;
+        }
+        const u64 s = S0 + KA, KB = s <= CS_MAX_ADAPTER_REC ? (u64)CS_MAX_ADAPTER_REC + 1 - s : 0;
+        if (KB > 0) {
+            rc = cs_select(ctx, a, KB, a.x1, 1, &total, &key);
+            if (rc) return rc;
+            a.x2 = total < KB ? ALL : key + 1;
+        }
+    }
+    CS_LAUNCH(fq_census_admit_kernel, ns * CS_GROUP, a);
+    u32 mctl[2];
+    rc = cs_read_words(ctx, a.map.ctl, mctl, 2);
+    if (rc) return rc;
+    if (mctl[0] > CS_MAX_ENTRIES) return fail(ctx, FASTP_GPU_E_HIP, "adapter census: more keys admitted than the caps allow");
+    ctx->cs_entries[w] = mctl[0];
+    return 0;
+}
+
+extern "C" int fastp_gpu_adapter_census(fastp_gpu_ctx* ctx, int32_t n, const fastp_gpu_format_io* m1, const fastp_gpu_format_io* m2,
+                                        const fastp_gpu_correction* corrections, const int32_t* n_corrections, int32_t corrections_capacity,
+                                        const fastp_gpu_adapter_event* events, const int32_t* n_events, int32_t events_capacity) {
+    if (!ctx || !m1 || n < 0 || corrections_capacity < 0 || events_capacity < 0) return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
+    const bool paired = ctx->dp.paired != 0;
+    if (paired != (m2 != nullptr)) return fail(ctx, FASTP_GPU_E_INVALID, "mate 2 must be given exactly for a paired engine");
+    if (n == 0) return FASTP_GPU_OK;
+    const fastp_gpu_format_io* ins[2] = {m1, m2};
+    for (int m = 0; m < (paired ? 2 : 1); m++)
+        if (!ins[m]->text || !ins[m]->line_off || !ins[m]->line_len || !ins[m]->res) return fail(ctx, FASTP_GPU_E_INVALID, "null input");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    int rc = cs_ensure_maps(ctx);
+    if (rc) return rc;
+    // the lists' counters keep counting past the capacity: such a list is incomplete, and nothing is read behind the buffer
+    int32_t ncorr = 0, nev = 0;
+    if (corrections && n_corrections) HIP_TRY(ctx, hipMemcpyAsync(&ncorr, n_corrections, 4, hipMemcpyDeviceToHost, st));
+    if (events && n_events) HIP_TRY(ctx, hipMemcpyAsync(&nev, n_events, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (ncorr < 0 || nev < 0) return fail(ctx, FASTP_GPU_E_INVALID, "negative list counter");
+    if (ncorr > corrections_capacity) return fail(ctx, FASTP_GPU_E_OVERFLOW, "correction list capacity exceeded: the list is incomplete");
+    if (nev > events_capacity) return fail(ctx, FASTP_GPU_E_OVERFLOW, "adapter event list capacity exceeded: the list is incomplete");
+    if (ncorr > 0) {   // the formatter's own patch kernel: the text is the same whether the formatter has run on it or not
+        FmtsArgs f;
+        memset(&f, 0, sizeof(f));
+        f.n = n;
+        f.paired = paired ? 1 : 0;
+        for (int m = 0; m < (paired ? 2 : 1); m++) {
+            f.m[m].text = ins[m]->text;
+            f.m[m].line_off = ins[m]->line_off;
+            f.m[m].line_len = ins[m]->line_len;
+            f.m[m].res = (const u32*)ins[m]->res;
+        }
+        f.corrections = (const u32*)corrections;
+        f.n_corrections = n_corrections;
+        hipLaunchKernelGGL(fq_fmts_corr_kernel, dim3((ncorr + 255) / 256), dim3(256), 0, st, f);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    const int nf = (int)ctx->fasta_strings.size();
+    const size_t cap_items = (size_t)(paired ? 2 : 1) * (size_t)n + (size_t)nev;
+    rc = ensure(ctx, (void**)&ctx->d_cs_items, &ctx->cs_items_cap, cap_items * sizeof(CsItem) + (CS_CTL_WORDS + 256) * 4);
+    if (rc) return rc;
+    CsArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int m = 0; m < (paired ? 2 : 1); m++) {
+        a.m[m].text = ins[m]->text;
+        a.m[m].line_off = ins[m]->line_off;
+        a.m[m].line_len = ins[m]->line_len;
+        a.m[m].res = (const u32*)ins[m]->res;
+    }
+    a.events = (const u32*)events;
+    a.blob_off = (const u32*)ctx->d_cs_blob;
+    a.blob_len = a.blob_off + (2 + nf);
+    a.blob = (const u8*)(a.blob_len + (2 + nf));
+    a.items = (CsItem*)ctx->d_cs_items;
+    a.ctl = (u32*)(ctx->d_cs_items + cap_items * sizeof(CsItem));
+    a.hist = a.ctl + CS_CTL_WORDS;
+    a.hash_mask = cs_hash_mask(ctx);
+    a.n = n;
+    a.paired = paired ? 1 : 0;
+    a.n_events = nev;
+    a.n_fasta = nf;
+    a.max_str = (int)CS_KEY_MAX;
+    a.map = ctx->cs_map[0];
+    HIP_TRY(ctx, hipMemsetAsync(a.ctl, 0, CS_CTL_WORDS * 4, st));
+    CS_LAUNCH(fq_census_gather_kernel, n, a);
+    if (nev > 0) CS_LAUNCH(fq_census_events_kernel, nev, a);
+    u32 ctl[CS_CTL_WORDS];
+    rc = cs_read_words(ctx, a.ctl, ctl, CS_CTL_WORDS);
+    if (rc) return rc;
+    if (ctl[CS_CTL_TOO_LONG]) return fail(ctx, FASTP_GPU_E_TOO_LONG, "adapter census: a string longer than FASTP_GPU_MAX_READ_LEN");
+    if (ctl[CS_CTL_ITEMS] > cap_items) return fail(ctx, FASTP_GPU_E_HIP, "adapter census: the item list overflowed");
+    a.n_items = (int)ctl[CS_CTL_ITEMS];
+    if (a.n_items == 0) return FASTP_GPU_OK;
+    a.which = -1;   // both maps' items
+    a.want_state = CS_NEW;
+    CS_LAUNCH(fq_census_hash_kernel, (size_t)a.n_items * CS_GROUP, a);
+    rc = cs_run_map(ctx, a, 0);
+    if (rc) return rc;
+    if (paired) {
+        CS_LAUNCH(fq_census_pair_kernel, a.n_items, a);   // quirk #8: map 1's verdicts decide which read 2 strings count
+        rc = cs_run_map(ctx, a, 1);
+        if (rc) return rc;
+    }
+    return FASTP_GPU_OK;
+}
+
+// a map's entries on the host, in the reference's map order (classcomp, filterresult.h:14-23: length, then bytes)
+struct CsHostMap {
+    std::vector<u32> off, len;
+    std::vector<u64> count;
+    std::vector<u8> arena;
+    std::vector<u32> order;
+};
+static int cs_download(fastp_gpu_ctx* ctx, int w, CsHostMap& h) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!ctx->d_cs_map[w]) return 0;
+    const CsMap& m = ctx->cs_map[w];
+    u32 mctl[2];
+    int rc = cs_read_words(ctx, m.ctl, mctl, 2);
+    if (rc) return rc;
+    const size_t e = mctl[0];
+    h.off.resize(e); h.len.resize(e); h.count.resize(e); h.arena.resize(mctl[1]);
+    if (e) {
+        HIP_TRY(ctx, hipMemcpyAsync(h.off.data(), m.eoff, e * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h.len.data(), m.elen, e * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h.count.data(), m.ecount, e * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (mctl[1]) HIP_TRY(ctx, hipMemcpyAsync(h.arena.data(), m.arena, mctl[1], hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    h.order.resize(e);
+    for (size_t i = 0; i < e; i++) h.order[i] = (u32)i;
+    std::sort(h.order.begin(), h.order.end(), [&](u32 x, u32 y) {
+        if (h.len[x] != h.len[y]) return h.len[x] < h.len[y];
+        return memcmp(h.arena.data() + h.off[x], h.arena.data() + h.off[y], h.len[x]) < 0;
+    });
+    return 0;
+}
+
+extern "C" int fastp_gpu_adapter_census_size(fastp_gpu_ctx* ctx, int is_r2, int64_t* entries, int64_t* bytes) {
+    if (!ctx) return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    u32 mctl[2] = {0, 0};
+    const int w = is_r2 ? 1 : 0;
+    if (ctx->d_cs_map[w]) {
+        int rc = cs_read_words(ctx, ctx->cs_map[w].ctl, mctl, 2);
+        if (rc) return rc;
+    }
+    if (entries) *entries = mctl[0];
+    if (bytes) *bytes = mctl[1];
+    return FASTP_GPU_OK;
+}
+
+extern "C" int fastp_gpu_adapter_census_read(fastp_gpu_ctx* ctx, int is_r2, char* chars, int64_t chars_capacity, int64_t* off, int64_t* counts) {
+    if (!ctx || !off || chars_capacity < 0) return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
+    CsHostMap h;
+    int rc = cs_download(ctx, is_r2 ? 1 : 0, h);
+    if (rc) return rc;
+    if ((int64_t)h.arena.size() > chars_capacity) return fail(ctx, FASTP_GPU_E_OVERFLOW, "adapter census: chars_capacity too small (fastp_gpu_adapter_census_size)");
+    if (!h.order.empty() && (!chars || !counts)) return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
+    int64_t at = 0;
+    for (size_t i = 0; i < h.order.size(); i++) {
+        const u32 e = h.order[i];
+        off[i] = at;
+        memcpy(chars + at, h.arena.data() + h.off[e], h.len[e]);
+        at += h.len[e];
+        counts[i] = (int64_t)h.count[e];
+    }
+    off[h.order.size()] = at;
+    return FASTP_GPU_OK;
+}
+
+extern "C" int fastp_gpu_adapter_census_load(fastp_gpu_ctx* ctx, int is_r2, const char* chars, const int64_t* off, const int64_t* counts, int64_t entries) {
+    if (!ctx || entries < 0 || entries > CS_MAX_ENTRIES || (entries && (!chars || !off || !counts))) return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = cs_ensure_maps(ctx);
+    if (rc) return rc;
+    const int w = is_r2 ? 1 : 0;
+    const size_t E = CS_MAX_ENTRIES;
+    const u64 mask = cs_hash_mask(ctx);
+    // the header as the device holds it (cs_ensure_maps): ehash | ecount | index | eoff | elen | ctl
+    std::vector<u8> head(cs_map_header_bytes(), 0);
+    u64* ehash = (u64*)head.data();
+    u64* ecount = ehash + E;
+    u32* index = (u32*)(ecount + E);
+    u32* eoff = index + CS_INDEX_SLOTS;
+    u32* elen = eoff + E;
+    u32* mctl = elen + E;
+    std::vector<u8> arena;
+    for (int64_t i = 0; i < entries; i++) {
+        const int64_t len = off[i + 1] - off[i];
+        if (len <= 0 || len > (int64_t)CS_KEY_MAX || counts[i] < 0) return fail(ctx, FASTP_GPU_E_INVALID, "adapter census load: a key must be 1..FASTP_GPU_MAX_READ_LEN bytes");
+        const u8* p = (const u8*)chars + off[i];
+        const u64 h = cs_host_hash(p, (u32)len, mask);
+        for (u32 step = 0;; step++) {
+            u32& at = index[((u32)h + step) & (CS_INDEX_SLOTS - 1)];
+            if (at == 0) { at = (u32)i + 1; break; }
+            const u32 e = at - 1;
+            if (ehash[e] == h && elen[e] == (u32)len && !memcmp(arena.data() + eoff[e], p, (size_t)len))
+                return fail(ctx, FASTP_GPU_E_INVALID, "adapter census load: the same key twice");
+        }
+        ehash[i] = h;
+        ecount[i] = (u64)counts[i];
+        eoff[i] = (u32)arena.size();
+        elen[i] = (u32)len;
+        arena.insert(arena.end(), p, p + len);
+    }
+    mctl[0] = (u32)entries;
+    mctl[1] = (u32)arena.size();
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cs_map[w], head.data(), head.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (!arena.empty()) HIP_TRY(ctx, hipMemcpyAsync(ctx->cs_map[w].arena, arena.data(), arena.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->cs_entries[w] = (u32)entries;
+    return FASTP_GPU_OK;
+}
+
 // ---- Evaluator pre-pass (fq_eval.h) ---------------------------------------------------------------------
 // the reads a reference loading loop `while (records < read_limit && bases < base_limit)` admits
 static int eval_admit(fastp_gpu_ctx* ctx, const uint16_t* len, int32_t n, int64_t read_limit, int64_t base_limit,
@@ -3299,6 +3697,10 @@ extern "C" int fastp_gpu_reset(fastp_gpu_ctx* ctx) {
     if (ctx->d_post_seen) HIP_TRY(ctx, hipMemsetAsync(ctx->d_post_seen, 0, sizeof(u64), ctx->stream));
     ctx->units_seen = 0;
     ctx->has_prefix = false;
+    for (int w = 0; w < 2; w++) {   // fresh FilterResult: both adapter maps empty
+        int rc = cs_clear_map(ctx, w);
+        if (rc) return rc;
+    }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return FASTP_GPU_OK;
 }

@@ -188,6 +188,18 @@ int fastp_gpu_host_add_adapter_pair(fastp_gpu_host* h, const char* a1, int32_t l
     return FASTP_GPU_OK;
 }
 
+int fastp_gpu_host_set_adapter_entries(fastp_gpu_host* h, int is_r2, const char* chars, const int64_t* off, const int64_t* counts,
+                                       int64_t entries) {
+    if (!h || entries < 0 || (entries && (!chars || !off || !counts))) return FASTP_GPU_E_INVALID;
+    for (int64_t i = 0; i < entries; i++)
+        if (off[i + 1] <= off[i]) return FASTP_GPU_E_INVALID;
+    auto& m = h->amap[is_r2 ? 1 : 0].m;
+    h->index_valid[0] = h->index_valid[1] = false;
+    m.clear();
+    for (int64_t i = 0; i < entries; i++) m[std::string(chars + off[i], (size_t)(off[i + 1] - off[i]))] = (long)counts[i];
+    return FASTP_GPU_OK;
+}
+
 int fastp_gpu_host_apply(fastp_gpu_host* h, const fastp_gpu_reads* b1, const fastp_gpu_reads* b2, const fastp_gpu_results* res) {
     if (!h || !b1 || !res || !res->r1) return FASTP_GPU_E_INVALID;
     const bool paired = b2 != nullptr;

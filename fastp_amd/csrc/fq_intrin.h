@@ -234,6 +234,11 @@ FQ_DEV u64 g_atomic_cas_u64(u64* p, u64 expected, u64 desired) {
                                          __HIP_MEMORY_SCOPE_AGENT);
     return expected;
 }
+FQ_DEV u32 g_atomic_cas_u32(u32* p, u32 expected, u32 desired) {
+    __hip_atomic_compare_exchange_strong(p, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_AGENT);
+    return expected;
+}
 FQ_DEV void g_atomic_add_i64(int64_t* p, int64_t v) {
     __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }

@@ -14,7 +14,8 @@
 //                   one reader thread)
 //   caller thread   parse -> worker loop -> format (-> deflate) on the context's stream, D2H of the output text
 //   writer thread   pwrite pieces of a chunk's output (or the emit callback), in chunk order
-//   replay thread   FilterResult::addAdapterTrimmed for the reads the records flag, in input order
+//   replay thread   FilterResult::addAdapterTrimmed for the reads the records flag, in input order (idle when the maps are
+//                   counted on the device: fastp_gpu_stream_set_adapter_census, one fastp_gpu_adapter_census call per trip)
 //
 // The text of a chunk that the records of the trip do not cover (a partial record at the end, the surplus of the
 // mate whose records are shorter) is copied to the front of the other page-locked slot and the next trip's fresh bytes
@@ -236,6 +237,14 @@ struct fastp_gpu_stream {
     int32_t want[FASTP_GPU_N_HOST_OUTPUTS] = {}, compress[FASTP_GPU_N_HOST_OUTPUTS] = {}, out_fd[FASTP_GPU_N_HOST_OUTPUTS] = {};
     int64_t out_offset[FASTP_GPU_N_HOST_OUTPUTS] = {};
     bool ov_device = false;        // --overlapped_out's stream is formatted on the device (fastp_gpu_format_all_streams)
+    // FilterResult's adapter maps are counted on the device (fastp_gpu_adapter_census per trip) instead of replayed on the host
+    // (fastp_gpu_stream_set_adapter_census, FASTP_GPU_STREAM_ADAPTERS=device); after the run: the maps as the census read them
+    bool census = false;
+    struct CensusMap {
+        std::vector<char> chars;
+        std::vector<int64_t> off, counts;
+        int64_t entries = 0;
+    } cmap[2];
     // host copies for the adapter replay
     fastp_gpu_read_result* h_res[2] = {nullptr, nullptr};
     uint32_t* h_loff[2] = {nullptr, nullptr};
@@ -484,6 +493,19 @@ int fetch_ctx_counters(fastp_gpu_stream* s, fastp_gpu_counter_layout* lay, std::
     return FASTP_GPU_OK;
 }
 
+// one of the context's adapter maps (the adapter census) into host arrays
+int census_fetch(fastp_gpu_stream* s, int is_r2, fastp_gpu_stream::CensusMap* m) {
+    int64_t entries = 0, bytes = 0;
+    if (fastp_gpu_adapter_census_size(s->ctx, is_r2, &entries, &bytes) != FASTP_GPU_OK) return s->fail_ctx(FASTP_GPU_E_HIP, "fastp_gpu_adapter_census_size");
+    m->chars.assign((size_t)bytes + 1, 0);
+    m->off.assign((size_t)entries + 1, 0);
+    m->counts.assign((size_t)entries + 1, 0);
+    m->entries = entries;
+    if (fastp_gpu_adapter_census_read(s->ctx, is_r2, m->chars.data(), bytes, m->off.data(), m->counts.data()) != FASTP_GPU_OK)
+        return s->fail_ctx(FASTP_GPU_E_HIP, "fastp_gpu_adapter_census_read");
+    return FASTP_GPU_OK;
+}
+
 // a read of `needed` bases has turned up: the work so far is kept (counters folded on the host, duplicate bitmaps and
 // stream positions carried over) and the run goes on with a context sized for it
 int replan(fastp_gpu_stream* s, int needed) {
@@ -497,6 +519,12 @@ int replan(fastp_gpu_stream* s, int needed) {
     if (rc) return rc;
     const int64_t post_reads = c[(size_t)(lay.stats[FASTP_GPU_STATS_POST1] + lay.st_reads)];
     s->segments.emplace_back(lay, std::move(c));
+    fastp_gpu_stream::CensusMap carried[2];   // the adapter census goes on in the new context where this one stopped
+    if (s->census)
+        for (int m = 0; m < 2; m++) {
+            rc = census_fetch(s, m, &carried[m]);
+            if (rc) return rc;
+        }
     void* image = nullptr;
     const int64_t image_bytes = fastp_gpu_dup_bitmap_bytes(s->ctx);
     if (image_bytes > 0) {
@@ -515,6 +543,11 @@ int replan(fastp_gpu_stream* s, int needed) {
         if (rc != FASTP_GPU_OK) return s->fail_ctx(rc, "fastp_gpu_dup_bitmap_import");
     }
     if (fastp_gpu_stream_set_origin(s->ctx, s->st.units, post_reads) != FASTP_GPU_OK) return s->fail_ctx(FASTP_GPU_E_HIP, "fastp_gpu_stream_set_origin");
+    if (s->census)
+        for (int m = 0; m < 2; m++)
+            if (carried[m].entries && fastp_gpu_adapter_census_load(s->ctx, m, carried[m].chars.data(), carried[m].off.data(), carried[m].counts.data(),
+                                                                    carried[m].entries) != FASTP_GPU_OK)
+                return s->fail_ctx(FASTP_GPU_E_HIP, "fastp_gpu_adapter_census_load");
     s->st.replans++;
     s->st.max_len = target;
     return alloc_rows(s);
@@ -756,6 +789,11 @@ int fastp_gpu_stream_create(const fastp_gpu_params* params, const fastp_gpu_stre
         else if (*v && strcmp(v, "host")) { g_stream_error = "FASTP_GPU_STREAM_OVERLAPPED is neither \"device\" nor \"host\""; return FASTP_GPU_E_INVALID; }
     }
     s->want[FASTP_GPU_OVERLAPPED] = s->ov_device ? 1 : 0;
+    // how a binding that does not call fastp_gpu_stream_set_adapter_census moves the adapter maps to the device
+    if (const char* v = getenv("FASTP_GPU_STREAM_ADAPTERS")) {
+        if (!strcmp(v, "device") || !strcmp(v, "1")) s->census = true;
+        else if (*v && strcmp(v, "host")) { g_stream_error = "FASTP_GPU_STREAM_ADAPTERS is neither \"device\" nor \"host\""; return FASTP_GPU_E_INVALID; }
+    }
     for (int m = 0; m < s->nf; m++) {
         s->src_kind[m] = input_kind(m ? s->in2 : s->in1);
         s->st.input_kind[m] = s->src_kind[m];
@@ -1408,7 +1446,8 @@ int run_loop(Run* R) {
             S_HIP(s, hipMemcpyAsync(&s->h_counts[0], s->d_nc, 4, hipMemcpyDeviceToHost, s->sx));
             S_HIP(s, hipMemcpyAsync(&s->h_counts[1], s->d_nev, 4, hipMemcpyDeviceToHost, s->sx));
             const bool host_ov = s->cfg.want_overlapped && !s->ov_device;
-            const bool host_records = s->cfg.host || host_ov;
+            const bool host_replay = s->cfg.host && !s->census;
+            const bool host_records = host_replay || host_ov;
             if (host_records)
                 for (int m = 0; m < nm; m++) {
                     S_HIP(s, hipMemcpyAsync(s->h_res[m], s->d_res[m], (size_t)n * sizeof(fastp_gpu_read_result), hipMemcpyDeviceToHost, s->sx));
@@ -1425,7 +1464,7 @@ int run_loop(Run* R) {
                 if (ncorr || nev) S_HIP(s, hipStreamSynchronize(s->sx));
                 const uint8_t* text[2] = {s->pin_in[slot][0], nm > 1 ? s->pin_in[slot][file_of(1)] : nullptr};
                 ex.index(ncorr, nev);
-                if (s->cfg.host) {
+                if (host_replay) {
                     ReplayJob job;
                     ex.run(n, text, job.blob);
                     if (!job.blob.empty()) R->q_replay.put(std::move(job));
@@ -1436,6 +1475,15 @@ int run_loop(Run* R) {
                 }
             }
             s->st.d2h_s += now_s() - t0;
+            if (s->census) {   // the adapter maps on the device, from the tensors this trip already holds (replay_s: the maps' cost either way)
+                t0 = now_s();
+                fastp_gpu_format_io cio[2];
+                for (int m = 0; m < nm; m++) { cio[m].text = s->d_text[slot][file_of(m)]; cio[m].line_off = s->d_loff[m]; cio[m].line_len = s->d_llen[m]; cio[m].res = s->d_res[m]; }
+                const int crc = fastp_gpu_adapter_census(s->ctx, n, &cio[0], s->paired ? &cio[1] : nullptr, s->d_corr, s->corr_cap ? s->d_nc : nullptr, s->corr_cap,
+                                                         s->d_ev, s->ev_cap ? s->d_nev : nullptr, s->ev_cap);
+                if (crc != FASTP_GPU_OK) return s->fail_ctx(crc, "fastp_gpu_adapter_census");
+                s->st.replay_s += now_s() - t0;
+            }
             // ---- records -> the text of every output stream (-> gzip members) ----
             if (!s->any_out && wj.has_ov) {
                 wj.oslot = 3;
@@ -1585,6 +1633,30 @@ extern "C" int fastp_gpu_stream_set_overlapped_output(fastp_gpu_stream* s, int o
 
 extern "C" int fastp_gpu_stream_overlapped_on_device(const fastp_gpu_stream* s) { return s && s->ov_device ? 1 : 0; }
 
+extern "C" int fastp_gpu_stream_set_adapter_census(fastp_gpu_stream* s, int on) {
+    if (!s || !s->ctx) return FASTP_GPU_E_INVALID;
+    if (s->started) return s->fail(FASTP_GPU_E_INVALID, "the adapter census is chosen before fastp_gpu_stream_run");
+    s->census = on != 0;
+    return FASTP_GPU_OK;
+}
+
+extern "C" int64_t fastp_gpu_stream_adapter_entries(fastp_gpu_stream* s, int is_r2) {
+    if (!s) return 0;
+    if (!s->census) return s->cfg.host ? fastp_gpu_host_adapter_entries(s->cfg.host, is_r2) : 0;
+    return s->cmap[is_r2 ? 1 : 0].entries;
+}
+
+extern "C" int fastp_gpu_stream_adapter_entry(fastp_gpu_stream* s, int is_r2, int64_t index, const char** seq, int32_t* len, int64_t* count) {
+    if (!s) return FASTP_GPU_E_INVALID;
+    if (!s->census) return s->cfg.host ? fastp_gpu_host_adapter_entry(s->cfg.host, is_r2, index, seq, len, count) : FASTP_GPU_E_INVALID;
+    const fastp_gpu_stream::CensusMap& m = s->cmap[is_r2 ? 1 : 0];
+    if (index < 0 || index >= m.entries) return FASTP_GPU_E_INVALID;
+    if (seq) *seq = m.chars.data() + m.off[(size_t)index];
+    if (len) *len = (int32_t)(m.off[(size_t)index + 1] - m.off[(size_t)index]);
+    if (count) *count = m.counts[(size_t)index];
+    return FASTP_GPU_OK;
+}
+
 extern "C" int fastp_gpu_stream_run(fastp_gpu_stream* s) {
     if (!s || !s->ctx) return FASTP_GPU_E_INVALID;
     s->started = true;
@@ -1632,6 +1704,13 @@ extern "C" int fastp_gpu_stream_run(fastp_gpu_stream* s) {
     writer.join();
     replayer.join();
     for (int m = 0; m < s->nf; m++) close(R.fds[m]);
+    if (rc == FASTP_GPU_OK && s->census)   // the maps as the census holds them: the accessors', and the caller's host object's
+        for (int m = 0; m < 2 && rc == FASTP_GPU_OK; m++) {
+            rc = census_fetch(s, m, &s->cmap[m]);
+            if (rc == FASTP_GPU_OK && s->cfg.host &&
+                fastp_gpu_host_set_adapter_entries(s->cfg.host, m, s->cmap[m].chars.data(), s->cmap[m].off.data(), s->cmap[m].counts.data(), s->cmap[m].entries) != FASTP_GPU_OK)
+                rc = s->fail(FASTP_GPU_E_INVALID, "fastp_gpu_host_set_adapter_entries");
+        }
     if (rc == FASTP_GPU_OK && R.io_err.load()) rc = s->fail(FASTP_GPU_E_INVALID, "file I/O failed");
     if (rc == FASTP_GPU_OK && R.emit_err.load()) rc = s->fail(FASTP_GPU_E_INVALID, "the emit callback stopped the run");
     s->st.wall_s = now_s() - t_start;

@@ -17,7 +17,7 @@ _LIBS: dict[str, C.CDLL] = {}
 EXPORTS = [
     "fastp_gpu_default_params", "fastp_gpu_seq_stride", "fastp_gpu_qual_stride", "fastp_gpu_cycles_for",
     "fastp_gpu_counter_layout_for", "fastp_gpu_counter_layout_for_params", "fastp_gpu_create", "fastp_gpu_destroy", "fastp_gpu_last_error",
-    "fastp_gpu_pack_reads", "fastp_gpu_pack_reads_x", "fastp_gpu_bgzf_index", "fastp_gpu_inflate_bgzf", "fastp_gpu_parse_fastq", "fastp_gpu_parse_exotic", "fastp_gpu_phred64_to_33", "fastp_gpu_host_writes_overlapped", "fastp_gpu_format_fastq", "fastp_gpu_format_streams", "fastp_gpu_format_all_streams", "fastp_gpu_deflate_bgzf", "fastp_gpu_deflate_bgzf_level", "fastp_gpu_device_alloc", "fastp_gpu_device_free", "fastp_gpu_device_upload", "fastp_gpu_device_download", "fastp_gpu_eval_seq_len", "fastp_gpu_eval_adapter_kmers", "fastp_gpu_eval_overrep", "fastp_gpu_eval_known_adapters", "fastp_gpu_eval_adapter_seed", "fastp_gpu_submit_host", "fastp_gpu_submit_device", "fastp_gpu_synchronize",
+    "fastp_gpu_pack_reads", "fastp_gpu_pack_reads_x", "fastp_gpu_bgzf_index", "fastp_gpu_inflate_bgzf", "fastp_gpu_parse_fastq", "fastp_gpu_parse_exotic", "fastp_gpu_phred64_to_33", "fastp_gpu_host_writes_overlapped", "fastp_gpu_format_fastq", "fastp_gpu_format_streams", "fastp_gpu_format_all_streams", "fastp_gpu_deflate_bgzf", "fastp_gpu_deflate_bgzf_level", "fastp_gpu_adapter_census", "fastp_gpu_adapter_census_size", "fastp_gpu_adapter_census_read", "fastp_gpu_adapter_census_load", "fastp_gpu_device_alloc", "fastp_gpu_device_free", "fastp_gpu_device_upload", "fastp_gpu_device_download", "fastp_gpu_eval_seq_len", "fastp_gpu_eval_adapter_kmers", "fastp_gpu_eval_overrep", "fastp_gpu_eval_known_adapters", "fastp_gpu_eval_adapter_seed", "fastp_gpu_submit_host", "fastp_gpu_submit_device", "fastp_gpu_synchronize",
     "fastp_gpu_counters_device", "fastp_gpu_counters", "fastp_gpu_kernel_time",
     "fastp_gpu_counters_export", "fastp_gpu_counters_import",
     "fastp_gpu_dup_scan_bytes", "fastp_gpu_submit_pass1_device", "fastp_gpu_dup_bitmap_bytes", "fastp_gpu_dup_bitmap_export",
@@ -28,10 +28,10 @@ EXPORTS = [
     "fastp_gpu_exchange_dup_prefix", "fastp_gpu_comm_last_error", "fastp_gpu_dup_bitmap_import", "fastp_gpu_warmup",
     # include/fastp_gpu_host.h
     "fastp_gpu_host_create", "fastp_gpu_host_destroy", "fastp_gpu_host_apply", "fastp_gpu_host_output", "fastp_gpu_host_clear_outputs",
-    "fastp_gpu_host_adapter_entries", "fastp_gpu_host_adapter_entry", "fastp_gpu_host_add_adapter", "fastp_gpu_host_add_adapter_pair",
+    "fastp_gpu_host_adapter_entries", "fastp_gpu_host_adapter_entry", "fastp_gpu_host_add_adapter", "fastp_gpu_host_add_adapter_pair", "fastp_gpu_host_set_adapter_entries",
     # include/fastp_gpu_stream.h
     "fastp_gpu_stream_create", "fastp_gpu_stream_run", "fastp_gpu_stream_layout", "fastp_gpu_stream_counters", "fastp_gpu_stream_get_stats",
-    "fastp_gpu_stream_last_error", "fastp_gpu_stream_destroy", "fastp_gpu_stream_set_deflate_level", "fastp_gpu_stream_set_overlapped_output", "fastp_gpu_stream_overlapped_on_device", "fastp_gpu_stream_gunzip_file", "fastp_gpu_stream_gunzip_file_mt",
+    "fastp_gpu_stream_last_error", "fastp_gpu_stream_destroy", "fastp_gpu_stream_set_deflate_level", "fastp_gpu_stream_set_overlapped_output", "fastp_gpu_stream_overlapped_on_device", "fastp_gpu_stream_set_adapter_census", "fastp_gpu_stream_adapter_entries", "fastp_gpu_stream_adapter_entry", "fastp_gpu_stream_gunzip_file", "fastp_gpu_stream_gunzip_file_mt",
 ]
 
 
@@ -379,6 +379,54 @@ class GpuEngine:
         if check:
             self._check(rc)
         return rc, int(n.value)
+
+    # ---- FilterResult's adapter-string maps on the device (csrc/fq_census.h) ----
+    def adapter_census(self, n, m1: abi.FormatIn, m2, corrections_ptr, n_corrections_ptr, corrections_capacity,
+                       events_ptr=None, n_events_ptr=None, events_capacity=0, check=True):
+        """add the n units of one launch to the context's two adapter maps (fastp_gpu_adapter_census): the inputs of
+        format_streams plus the --adapter_fasta event list, all DEVICE pointers; calls in stream order.  Returns rc"""
+        fn = self.lib.fastp_gpu_adapter_census
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int32, C.POINTER(abi.FormatIn), C.POINTER(abi.FormatIn), C.c_void_p, C.c_void_p,
+                       C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
+        rc = fn(self.h, n, C.byref(m1), C.byref(m2) if m2 is not None else None, corrections_ptr, n_corrections_ptr,
+                corrections_capacity, events_ptr, n_events_ptr, events_capacity)
+        if check:
+            self._check(rc)
+        return rc
+
+    def adapter_counts(self, is_r2: bool) -> dict:
+        """FilterResult::mAdapter1 (mAdapter2) as the census holds it: {adapter bytes: count}, in the reference's map
+        order (by length, then bytes)"""
+        size = self.lib.fastp_gpu_adapter_census_size
+        size.restype = C.c_int
+        size.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        ne, nb = C.c_int64(0), C.c_int64(0)
+        self._check(size(self.h, int(is_r2), C.byref(ne), C.byref(nb)))
+        chars = np.zeros(max(1, nb.value), dtype=np.uint8)
+        off = np.zeros(ne.value + 1, dtype=np.int64)
+        cnt = np.zeros(max(1, ne.value), dtype=np.int64)
+        read = self.lib.fastp_gpu_adapter_census_read
+        read.restype = C.c_int
+        read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        self._check(read(self.h, int(is_r2), chars.ctypes.data, chars.size, off.ctypes.data, cnt.ctypes.data))
+        raw = chars.tobytes()
+        return {raw[off[i]:off[i + 1]]: int(cnt[i]) for i in range(ne.value)}
+
+    def load_adapter_counts(self, is_r2: bool, counts, check=True):
+        """replace a map's contents with {adapter bytes: count} (or a list of such pairs): fastp_gpu_adapter_census_load"""
+        items = list(counts.items()) if isinstance(counts, dict) else list(counts)
+        chars = np.frombuffer(b"".join(k for k, _ in items) or b"\0", dtype=np.uint8)
+        off = np.zeros(len(items) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(k) for k, _ in items], dtype=np.int64) if items else 0
+        cnt = np.array([v for _, v in items] or [0], dtype=np.int64)
+        fn = self.lib.fastp_gpu_adapter_census_load
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        rc = fn(self.h, int(is_r2), chars.ctypes.data, off.ctypes.data, cnt.ctypes.data, len(items))
+        if check:
+            self._check(rc)
+        return rc
 
     # ---- the Evaluator pre-pass on the device (csrc/fq_eval.h); device pointers of one mate's packed rows ----
     def eval_seq_len(self, len_ptr, n):

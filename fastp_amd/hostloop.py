@@ -90,7 +90,8 @@ def parse_fastq(data: bytes, stride: int | None = None) -> FastqBatch:
 
 class AdapterMaps:
     """FilterResult::mAdapter1/mAdapter2 with the reference's insertion caps
-    (filterresult.cpp:124-180).  Host-side by design: string keyed."""
+    (filterresult.cpp:124-180): the literal, per-record port.  The engine counts the same maps on the device
+    (GpuEngine.adapter_census / adapter_counts, csrc/fq_census.h); the tests take their expected values from here."""
 
     def __init__(self):
         self.a1: dict[bytes, int] = {}

@@ -268,13 +268,17 @@ class FastqPipeline:
     def run(self, in1: str, in2: str | None, out1: str, out2: str | None, failed_out: str | None = None,
             merged_out: str | None = None, unpaired1: str | None = None, unpaired2: str | None = None,
             umi: tuple | None = None, compression_level: int | None = None, overlapped_out: str | None = None,
-            fix_mgi_id: bool = False) -> dict:
+            fix_mgi_id: bool = False, adapter_counts: bool = False) -> dict:
         """umi = (location "read1" | "read2" | "per_read", length[, prefix bytes[, delimiter bytes]]): the name edit that goes
         with params.umi_len1/2 (UmiProcessor::addUmiToName); or (location "index1" | "index2" | "per_index", 0[, prefix[,
         delimiter]]): the UMI is the index part of the name, nothing is trimmed.  fix_mgi_id: --fix_mgi_id, a space in front
         of a name's final /1 or /2, before the UMI edit.  compression_level: the reference's -z (1..9, 0 = the default)
         for every ".gz" output; None is the default encoder through fastp_gpu_deflate_bgzf.  overlapped_out: the file of
-        --overlapped_out's stream, needed when params.overlapped_out is set (a ".gz" path is compressed like the others)"""
+        --overlapped_out's stream, needed when params.overlapped_out is set (a ".gz" path is compressed like the others).
+        adapter_counts: FilterResult's adapter-string maps (the report's adapter_cutting.read1_adapter_counts /
+        read2_adapter_counts) are counted on the device, per chunk, on the tensors the chunk already holds
+        (fastp_gpu_adapter_census); adapter_counts() returns them"""
+        self.census = bool(adapter_counts)
         torch = self.torch
         if compression_level is not None and not 0 <= int(compression_level) <= 9:
             raise PipelineError("compression_level is 0 (the default) to 9")
@@ -485,6 +489,12 @@ class FastqPipeline:
             raise PipelineError("correction list overflow: raise corr_capacity")
         st["t_format"] += time.perf_counter() - t0
         st["bytes_text"] = st.get("bytes_text", 0) + sum(lens)
+        if self.census:
+            t0 = time.perf_counter()
+            self.eng.adapter_census(n, fi[0], fi[1] if self.paired else None, self.corr.data_ptr() if self.corr_cap else None,
+                                    self.nc.data_ptr() if self.corr_cap else None, self.corr_cap,
+                                    self.ev.data_ptr() if self.ev_cap else None, self.nev.data_ptr() if self.ev_cap else None, self.ev_cap)
+            st["t_census"] = st.get("t_census", 0.0) + time.perf_counter() - t0
         t0 = time.perf_counter()
         for q in range(abi.N_ALL_OUTPUTS):
             if self.out_cap[q] and self.gz_out[q]:
@@ -505,3 +515,11 @@ class FastqPipeline:
 
     def counters(self):
         return self.eng.counters()
+
+    def adapter_counts(self):
+        """FilterResult::mAdapter1 / mAdapter2 of the runs made with adapter_counts=True: an object with the two dicts
+        {adapter bytes: count} as .a1 / .a2 (hostloop.AdapterMaps), in the reference's map order"""
+        from . import hostloop
+        m = hostloop.AdapterMaps()
+        m.a1, m.a2 = self.eng.adapter_counts(False), self.eng.adapter_counts(True)
+        return m

@@ -17,7 +17,7 @@
  *   (peprocessor.cpp:710-723) and the integer side of FilterResult
  *   (filterresult.cpp:28-36,99-107,182-189).
  * The host keeps FASTQ decode/encode, read names, output routing, the
- * adapter-string map and the JSON/HTML reporters.
+ * adapter-string map (or leaves it to fastp_gpu_adapter_census) and the JSON/HTML reporters.
  *
  * Plain C: pointers and sizes only.  No function here ever calls exit();
  * every failure is a negative return code (reference: error_exit, util.h:270).
@@ -546,6 +546,41 @@ int fastp_gpu_format_all_streams(fastp_gpu_ctx* ctx, int32_t n, const fastp_gpu_
                                  uint8_t* const out[FASTP_GPU_N_HOST_OUTPUTS], const int64_t out_capacity[FASTP_GPU_N_HOST_OUTPUTS],
                                  int64_t out_len[FASTP_GPU_N_HOST_OUTPUTS] /* host: bytes written (needed) per stream */);
 
+/* ---- FilterResult's adapter-string maps ON THE DEVICE (the adapter census) ---------------------
+ * FilterResult::mAdapter1 / mAdapter2 (src/filterresult.cpp:115-180; the report's adapter_cutting.read1_adapter_counts /
+ * read2_adapter_counts) kept by the context: every string the worker loop hands to addAdapterTrimmed, with the reference's
+ * insertion caps (a new key is refused once the map holds more than 20000 keys, a low-complexity one once it holds more than
+ * 5000) and the early return of the pair form (read 2's string is not looked at when a cap refused read 1's).
+ *
+ * fastp_gpu_adapter_census adds the n units of one launch to the two maps, in the order the reference's single worker
+ * (-w 1) sees them: per unit the pair form when read 1 has FASTP_GPU_RF_ADAPTER_OV, otherwise the single form of each mate
+ * with FASTP_GPU_RF_ADAPTER and adapter_len, then each mate's --adapter_fasta events in ascending `adapter` index.  The
+ * inputs are what fastp_gpu_format_streams takes (DEVICE pointers; mate2 NULL for single-end) plus the event list; the
+ * corrections are patched into `text` exactly as the formatter does it, so the strings hold the corrected bases whether
+ * the formatter has run on this text or not.  A string is bytes [front + adapter_pos, + adapter_len) of the mate's
+ * sequence line clamped to the line, or for adapter_pos < 0 the first adapter_len bytes of the adapter sequence (-a,
+ * --adapter_sequence_r2, the event's --adapter_fasta entry); an empty string is ignored.  Calls must come in stream
+ * order.  FASTP_GPU_E_OVERFLOW when a list's counter ran past its capacity: nothing is read behind the buffer and nothing
+ * is counted.  Synchronous.
+ *
+ * _size / _read: a map's entries in HOST memory, in the reference's map order (classcomp, filterresult.h:14-23: by
+ * length, then bytes): key i is chars[off[i], off[i + 1]), counts[i] its count; off holds entries + 1 values.
+ * FASTP_GPU_E_OVERFLOW when chars_capacity is below *bytes of _size.
+ * _load replaces a map's contents (HOST arrays as _read fills them, in any order; at most 20001 keys of 1 ..
+ * FASTP_GPU_MAX_READ_LEN bytes, no key twice): how a host carries the maps into a new context.
+ * fastp_gpu_reset empties both maps. */
+int fastp_gpu_adapter_census(fastp_gpu_ctx* ctx, int32_t n, const fastp_gpu_format_io* mate1,
+                             const fastp_gpu_format_io* mate2 /* NULL for single-end */,
+                             const fastp_gpu_correction* corrections, const int32_t* n_corrections /* may be NULL */,
+                             int32_t corrections_capacity,
+                             const fastp_gpu_adapter_event* events, const int32_t* n_events /* may be NULL */,
+                             int32_t events_capacity);
+int fastp_gpu_adapter_census_size(fastp_gpu_ctx* ctx, int is_r2, int64_t* entries, int64_t* bytes);
+int fastp_gpu_adapter_census_read(fastp_gpu_ctx* ctx, int is_r2, char* chars, int64_t chars_capacity,
+                                  int64_t* off /* [entries + 1] */, int64_t* counts /* [entries] */);
+int fastp_gpu_adapter_census_load(fastp_gpu_ctx* ctx, int is_r2, const char* chars, const int64_t* off,
+                                  const int64_t* counts, int64_t entries);
+
 /* ---- device memory for callers that do not link the HIP runtime themselves ----------------
  * The entry points that take DEVICE pointers (submit_device, parse / format / deflate / inflate, eval_*)
  * are meant for hosts that manage HBM with HIP; a host that does not (the reference is plain C++ built
@@ -781,7 +816,7 @@ int fastp_gpu_device(const fastp_gpu_ctx* ctx);
 
 /* Start a new run on the same context: counter block, duplicate bitmaps and stream positions as right after
  * fastp_gpu_create - what constructing fresh Stats / FilterResult / Duplicate objects is for the reference
- * (src/peprocessor.cpp:26-60).  Synchronous. */
+ * (src/peprocessor.cpp:26-60); the adapter census's two maps are emptied as well.  Synchronous. */
 int fastp_gpu_reset(fastp_gpu_ctx* ctx);
 
 /* time spent inside the kernels of the per-read path (the fused kernel, or - split / lane plan - the per-read kernel

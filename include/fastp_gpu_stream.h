@@ -12,7 +12,8 @@
  *   the output strings the loop body hands to WriterThread::input  src/peprocessor.cpp:652-686,
  *   src/seprocessor.cpp:299-304  (Read::appendToString src/read.cpp:119-154)
  *   WriterThread::inputPwrite's per-pack gzip members  src/writerthread.cpp:118-168
- *   FilterResult::addAdapterTrimmed  src/filterresult.cpp:124-180 (replayed on the host from the parsed text)
+ *   FilterResult::addAdapterTrimmed  src/filterresult.cpp:124-180 (replayed on the host from the parsed text, or counted on
+ *   the device: fastp_gpu_stream_set_adapter_census)
  *
  *   BgzfMtReader (bgzip-written ".gz" inputs)  src/bgzf.h:36-239  } fastp_gpu_inflate_bgzf on the compressed bytes
  *
@@ -118,6 +119,24 @@ int fastp_gpu_stream_set_deflate_level(fastp_gpu_stream* s, int level);
  * FASTP_GPU_E_INVALID. */
 int fastp_gpu_stream_set_overlapped_output(fastp_gpu_stream* s, int out_fd, int64_t out_offset, int compress);
 int fastp_gpu_stream_overlapped_on_device(const fastp_gpu_stream* s);   /* 1 once the device writes it */
+/* Between create and run: on != 0 counts FilterResult's adapter maps on the device - fastp_gpu_adapter_census per trip, on
+ * the tensors the trip already holds - instead of replaying them on the host: the records, line tables and sparse lists then
+ * stay on the device (unless the host writes --overlapped_out's stream), a re-plan carries the maps into the new context, and
+ * at the end of the run config.host, when given, is filled with fastp_gpu_host_set_adapter_entries - the same maps either way.
+ * stats.replay_s is the time of the census calls then.  FASTP_GPU_E_INVALID once fastp_gpu_stream_run has been called.
+ * A stream this was never called for takes the environment variable FASTP_GPU_STREAM_ADAPTERS (read at create): "device"
+ * (or "1") = on, "host" or unset = the host replay, anything else FASTP_GPU_E_INVALID. */
+int fastp_gpu_stream_set_adapter_census(fastp_gpu_stream* s, int on);
+/* Replace a map of a host glue object (fastp_gpu_host.h) with the entries of an adapter census - fastp_gpu_adapter_census_read's
+ * arrays: key i is chars[off[i], off[i + 1]), counts[i] its count - so that a host that counted on the device reads the maps
+ * through fastp_gpu_host_adapter_entry as before.  What the stream does with config.host at the end of a census run; declared
+ * here, with the census's other host-side calls (fastp_gpu_host.h keeps the symbols of the per-pack glue). */
+int fastp_gpu_host_set_adapter_entries(fastp_gpu_host* h, int is_r2, const char* chars, const int64_t* off,
+                                       const int64_t* counts, int64_t entries);
+/* after the run: the adapter maps (with the census on: in the reference's map order - by length, then bytes; off: what
+ * config.host holds, 0 entries without one).  *seq is not terminated and stays valid until the stream is destroyed. */
+int64_t fastp_gpu_stream_adapter_entries(fastp_gpu_stream* s, int is_r2);
+int fastp_gpu_stream_adapter_entry(fastp_gpu_stream* s, int is_r2, int64_t index, const char** seq, int32_t* len, int64_t* count);
 /* the run's counter block in the layout of the LAST context (cycles = its max_len; the blocks of the contexts a
  * re-plan replaced are folded in).  fastp_gpu_stream_layout first, then counters with n = layout.total. */
 int fastp_gpu_stream_layout(const fastp_gpu_stream* s, fastp_gpu_counter_layout* out);
