@@ -302,6 +302,12 @@ struct Switches {
                               // different strings share one (the collision path): tests/test_adapter_census.py
 };
 
+// A kernel's dynamic LDS as the context launches it (kernel_lds_table): create refuses a context whose `need` is over the device's
+// LDS per workgroup (check_kernel_lds) and sets `set` as the kernel's MaxDynamicSharedMemorySize (set_kernel_attributes).  The two
+// differ for the kernels that size their tables to aux_lds_cap at each launch; need = LDS_NO_CHECK: the attribute only.
+struct KernelLds { const char* name; const void* fn; long long need; int set; };
+constexpr long long LDS_NO_CHECK = 0;
+
 struct fastp_gpu_ctx {
     fastp_gpu_params params;
     Switches sw;
@@ -315,7 +321,9 @@ struct fastp_gpu_ctx {
     int cus = 0;
     int lds_bytes = 0;       // the device's LDS per workgroup (hipDeviceProp_t::sharedMemPerBlock): every LDS decision uses it
     int blocks = 0;           // persistent workgroups per launch
+    int tiles_per_block = 0;  // tiles a workgroup of the tile kernel takes per launch (its packed per-cycle counters bound it)
     int max_pairs_per_launch = 0;
+    std::vector<KernelLds> kernel_lds;   // every kernel with dynamic LDS this context may launch, in the order create checks them
     // split plan (fq_stats.h): the per-read kernel as small workgroups, Stats::statRead as its own streaming kernel
     bool split = false;
     int st_threads = 0, st_blocks = 0;     // the Stats kernel's workgroup size and the most workgroups it is launched with
@@ -324,7 +332,7 @@ struct fastp_gpu_ctx {
     u32* d_corr_chain = nullptr; size_t corr_chain_cap = 0;  // their per-read chains: head[reads] | next[capacity]
     int st_form = 4, st_max_reads = CYC_MAX_READS, st_max_grid = 0;   // the Stats kernel's form: 5 (fq_stats5.h) where it fits, else 4 (fq_stats.h)
     stats5_kernel_fn st5_fn = nullptr; int st5_inst = -1;   // form 5: the instantiation this context launches (stats5_inst_for), chosen at create
-    int finish_threads = 1024;   // fq_dup_finish_kernel's workgroup: the largest whose waves fit beside the Stats kernel's (finish_threads_beside, at create)
+    int finish_threads = 1024;   // fq_dup_finish_kernel's workgroup: the largest whose waves fit beside the Stats kernel's (choose_finish_threads, at create)
     int last_stats_fold = -1;    // which fold the most recent launch's Stats fold took (FOLD_GROUPS / FOLD_WIDE; -1: none yet)
     // Argument blocks with their constant part filled once (fill_arg_templates, at the end of fastp_gpu_create): a launch copies the
     // block and sets what differs per launch - pointers, n, first, units per block, debug_skip.  The Stats kernel's geometry (H, Hs,
@@ -518,26 +526,57 @@ extern "C" void fastp_gpu_destroy(fastp_gpu_ctx* ctx) {
     delete ctx;
 }
 
-// the option family the lane kernel covers: nothing moves or edits a kept base (split plan), no step that needs an
-// unbounded indexed walk along a read (adapter sequences, one-gap overlap, polyX, complexity), windows of up to 8
-// bases, reads of up to 256 bases, a duplicate hash with the byte-plane table and 3-byte primes
-// form 5 of the Stats kernel (fq_stats5.h): the copies of the 5-mer table its LDS layout has room for (0: it does not fit)
-// (and, through hb, the columns its table holds: reads with more 16-base columns than fit are taken in blocks of hb columns)
+// The LDS layout of form 5 of the Stats kernel (fq_stats5.h) with hb table columns and kc copies of the 5-mer counters: the joint
+// table [2][8][4][ST5_QN][hb] of 16-bit cell pairs, kc copies of the mate's 5-mer counters, the packed cells of what the table has
+// no cell for, the histogram of those, a list per wavefront.  Writes the dword offsets into sa and returns the total: the one
+// statement of the layout, for the fit test (stats5_copies) and for the context's kernel (plan_stats_kernel) alike.
+static int stats5_lds_layout(StatsArgs& sa, int Cp, int hb, int kc) {
+    int o = 0;
+    sa.l_cyc = o; o += 2 * 8 * 4 * ST5_QN * hb;
+    sa.l_kmer = o; o += 2 * KMER_BINS * kc;
+    o = (o + 1) & ~1;
+    sa.l_ovf = o; o += 2 * Cp * N_CLS * 2;
+    sa.l_qh = o; o += 2 * 128;
+    sa.l_wl = o; o += (1024 / 64) * 2 * ST5_WL / 2;   // (u16 entries)
+    return o;
+}
+// The LDS layout of form 4 (fq_stats.h): [2][8][ST4_ROWS][Hs] u32 per-cycle cells of ONE mate, four copies of its 5-mer counters,
+// its histogram; the class stride padded to 32 items (= all 64 banks).  Shrinks sa.Hs, then sa.kc, until two workgroups fit a CU
+// (or nothing is left to shrink); writes the dword offsets into sa and returns the total.
+static int stats4_lds_layout(StatsArgs& sa, int lds_bytes) {
+    sa.kc = 4;
+    sa.Hs = sa.H < 32 ? 32 : sa.H;
+    for (;;) {
+        sa.wl_cap = 511;
+        int o = 0;
+        sa.l_cyc = o; o += 2 * 8 * ST4_ROWS * sa.Hs;
+        sa.l_kmer = o; o += 2 * KMER_BINS * sa.kc;
+        sa.l_qh = o; o += ST_QH_COPIES * 2 * 128;
+        o = (o + 3) & ~3;
+        sa.l_lut = o; o += 4 * 256;
+        sa.l_mt = o; o += 18 + 2;
+        sa.l_wl = o; o += 1 + sa.wl_cap;
+        if (2 * o * 4 <= lds_bytes) return o;   // two workgroups per CU
+        if (sa.Hs > sa.H) sa.Hs = sa.H;         // first the padding,
+        else if (sa.kc > 1) sa.kc /= 2;         // then the copies
+        else return o;
+    }
+}
+// form 5 of the Stats kernel: the copies of the 5-mer table its LDS layout has room for (0: it does not fit)
+// (and, through hb, the columns its table holds: reads with more 16-base columns than fit are taken in blocks of hb columns;
+// reads of up to 176 bases fit one workgroup's LDS whole; merge mode's third pass exists in form 4 only)
 static int stats5_copies(const DevParams& p, int lds_bytes, int* hb_out = nullptr) {
     if (p.merge_lane) return 0;
     const int H16 = (p.qw_g + 3) / 4, Cp = (p.cycles + 3) & ~3;
     if (H16 > p.sw_g || H16 > 64) return 0;
+    StatsArgs probe = {};
     for (int nblk = 1; nblk <= 4; nblk++) {
         const int hb = (H16 + nblk - 1) / nblk;
-        for (int kc = 2; kc >= 1; kc--) {
-            int o = 2 * 8 * 4 * ST5_QN * hb + 2 * KMER_BINS * kc;
-            o = (o + 1) & ~1;
-            o += 2 * Cp * N_CLS * 2 + 2 * 128 + (1024 / 64) * 2 * ST5_WL / 2;
-            if (o * 4 <= lds_bytes) {
+        for (int kc = 2; kc >= 1; kc--)
+            if (stats5_lds_layout(probe, Cp, hb, kc) * 4 <= lds_bytes) {
                 if (hb_out) *hb_out = hb;
                 return kc;
             }
-        }
     }
     return 0;
 }
@@ -567,6 +606,9 @@ static stats5_kernel_fn stats5_kernel_for(int inst) {
 static bool stats5_no_front(const DevParams& p) {
     return !p.front_per_read && !(p.front_lane && (p.lane_front1 != 0 || p.lane_front2 != 0));
 }
+// the option family the lane kernel covers: nothing moves or edits a kept base (split plan), no step that needs an
+// unbounded indexed walk along a read (adapter sequences, one-gap overlap, polyX, complexity), windows of up to 8
+// bases, reads of up to 256 bases, a duplicate hash with the byte-plane table and 3-byte primes
 static bool lane_plan_supported(const DevParams& p, const HostLuts& luts, int lds_bytes) {
     if (p.front_per_read && !stats5_copies(p, lds_bytes)) return false;   // a front per read: form 5 of the Stats kernel only
     if (!(p.stats_one_pass || p.front_lane || p.corr_lane || p.merge_lane) || p.allow_gap || p.overlapped_out) return false;
@@ -582,6 +624,19 @@ static bool lane_plan_supported(const DevParams& p, const HostLuts& luts, int ld
 
 // the dynamic LDS the overrepresentation count and text kernels may take (they size their tables to it at each launch)
 static int aux_lds_cap(const fastp_gpu_ctx* ctx) { return std::min(150 * 1024, ctx->lds_bytes); }
+// the dynamic LDS of the kernels whose size is a formula: create's check, the attribute and the launch all ask here
+// (DevParams::cycles and the counter layout's cycles are both fastp_gpu_cycles_for of the context's parameters)
+static size_t front_stats_lds_bytes(const fastp_gpu_ctx* ctx) { return (size_t)(ctx->dp.paired ? 2 : 1) * 34 * (size_t)ctx->dp.cycles * 4; }
+static size_t corr_stats_lds_bytes(const fastp_gpu_ctx* ctx) {
+    return (size_t)(ctx->dp.paired ? 2 : 1) * (33 * (size_t)ctx->dp.cycles + 128 + KMER_BINS) * 4;
+}
+static int inflate_lane_lds_bytes() { return INF_ENTRIES * INF_LANES * 2 + INF_SBUF * INF_LANES * 4; }
+// the tile kernel of the context's plan, and what create's messages call it
+static const void* tile_kernel_for(const fastp_gpu_ctx* ctx, const char** name = nullptr) {
+    const bool wide = ctx->cfg.threads > 256;
+    if (name) *name = ctx->split ? (wide ? "scan_wide kernel" : "scan kernel") : "fused kernel";
+    return ctx->split ? (wide ? (const void*)fq_scan_wide_kernel : (const void*)fq_scan_kernel) : (const void*)fq_fused_kernel;
+}
 
 typedef void (*lane_kernel_fn)(LaneArgs);
 template <int EXT>
@@ -668,431 +723,12 @@ static void fill_arg_templates(fastp_gpu_ctx* ctx) {
     cs.st_qual_hist = cl.st_qual_hist; cs.st_kmer = cl.st_kmer; cs.st_cycle = cl.st_cycle; cs.cycles = cl.cycles;
 }
 
-enum { KERNEL_REGS_N = 16 };
-extern "C" int fastp_gpu_debug_kernel_regs(fastp_gpu_ctx* ctx, int32_t* out, int32_t n);   // (below, next to the other debugging aid)
-
-extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fastp_gpu_ctx** out) {
-    if (!params || !out) return fail(nullptr, FASTP_GPU_E_INVALID, "null argument");
-    *out = nullptr;
-    int ndev = 0;
-    fq::timeline("create: begin");
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, FASTP_GPU_E_NO_DEVICE, "no HIP device visible - the engine has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(nullptr, FASTP_GPU_E_NO_DEVICE, "device ordinal out of range");
-    std::unique_ptr<fastp_gpu_ctx> owner(new fastp_gpu_ctx());   // released at `*out = ctx`: every return before that frees it
-    fastp_gpu_ctx* ctx = owner.get();
-    ctx->sw = read_switches();
-    const Switches& sw = ctx->sw;
-    ctx->params = *params;
-    if (params->adapter_seq_r1) ctx->adapter1 = params->adapter_seq_r1;
-    if (params->adapter_seq_r2) ctx->adapter2 = params->adapter_seq_r2;
-    ctx->params.adapter_seq_r1 = ctx->adapter1.c_str();
-    ctx->params.adapter_seq_r2 = ctx->adapter2.c_str();
-    if (params->n_adapter_fasta > 0 && params->adapter_fasta) {  // own copies: the caller's strings may go away
-        for (int i = 0; i < params->n_adapter_fasta; i++) ctx->fasta_strings.push_back(params->adapter_fasta[i] ? params->adapter_fasta[i] : "");
-        for (auto& f : ctx->fasta_strings) ctx->fasta_ptrs.push_back(f.c_str());
-        ctx->params.adapter_fasta = ctx->fasta_ptrs.data();
-    }
-    if (params->overrep_enabled) {  // own copies of the seed strings
-        const char* const* lists[2] = {params->overrep_seqs1, params->overrep_seqs2};
-        const int ns[2] = {params->n_overrep_seqs1, params->n_overrep_seqs2};
-        for (int m = 0; m < 2; m++) {
-            for (int i = 0; i < ns[m] && lists[m]; i++) ctx->ovr_strings[m].push_back(lists[m][i] ? lists[m][i] : "");
-            for (auto& q : ctx->ovr_strings[m]) ctx->ovr_ptrs[m].push_back(q.c_str());
-        }
-        ctx->params.overrep_seqs1 = ctx->ovr_ptrs[0].data();
-        ctx->params.overrep_seqs2 = ctx->ovr_ptrs[1].data();
-    }
-    ctx->device = device;
-    std::string err;
-    int rc = build_dev_params(ctx->params, ctx->dp, ctx->luts, err);
-    if (rc) return fail(nullptr, rc, err);
-    hipError_t he = hipSetDevice(device);
-    if (he != hipSuccess) return fail(nullptr, FASTP_GPU_E_HIP, "hipSetDevice failed");
-    hipDeviceProp_t prop;
-    he = hipGetDeviceProperties(&prop, device);
-    if (he != hipSuccess) return fail(nullptr, FASTP_GPU_E_HIP, "hipGetDeviceProperties failed");
-    ctx->cus = prop.multiProcessorCount;
-    ctx->lds_bytes = (int)std::min<size_t>(prop.sharedMemPerBlock, (size_t)1 << 30);
-    const int lds_max = ctx->lds_bytes;
-    // tile / launch geometry (tunable without a rebuild)
-    const int lds_kb_default = lds_max / 1024 >= 160 ? 160 : lds_max / 1024;
-    // The split plan (per-read kernel as 256-lane workgroups, several per CU, + the streaming Stats kernel) whenever no
-    // option moves or edits a kept base; FASTP_GPU_SPLIT=0 keeps Stats inside the one-workgroup-per-CU fused kernel.
-    // the Stats kernel as its own launch: options that leave every kept base where it was, or (lane plan only) move it by the
-    // same front for every read that is written out (DevParams::front_lane)
-    if (sw.hash_generic) {  // tests: the multiply form of the duplicate hash (what B = 8 uses; the lane plan has none)
-        ctx->luts.dup_planes.clear();
-        ctx->luts.dup_nq = 0;
-    }
-    const bool lane_wanted = sw.lane != 0 && lane_plan_supported(ctx->dp, ctx->luts, lds_max);
-    ctx->split = (ctx->dp.stats_one_pass || ((ctx->dp.front_lane || ctx->dp.corr_lane || ctx->dp.merge_lane) && lane_wanted)) && sw.split != 0;
-    ctx->lane = ctx->split && lane_wanted;
-    ctx->cfg.split = ctx->split ? 1 : 0;
-    ctx->cfg.threads = sw.threads ? sw.threads : (ctx->split ? 256 : 1024);
-    ctx->cfg.P = sw.tile;
-    // (FASTP_GPU_LDS_KB above what the device has is clamped to it: a budget the card cannot give would only fail the launch)
-    ctx->cfg.lds_budget = std::min(sw.lds_kb ? sw.lds_kb : (ctx->split ? std::min(40, lds_kb_default) : lds_kb_default), lds_max / 1024) * 1024;
-    if (ctx->cfg.threads < 64 || ctx->cfg.threads > 1024 || (ctx->cfg.threads & 63))
-        return fail(nullptr, FASTP_GPU_E_INVALID, "FASTP_GPU_THREADS must be a multiple of 64 in 64..1024");
-    rc = compute_lds_layout(ctx->dp, ctx->cfg, ctx->L, err, ctx->luts.dup_nq);
-    if (rc && ctx->split && !sw.lds_kb) {  // long reads (or a tile size asked for): the small budget holds no such tile
-        ctx->cfg.lds_budget = lds_kb_default * 1024;
-        rc = compute_lds_layout(ctx->dp, ctx->cfg, ctx->L, err, ctx->luts.dup_nq);
-    }
-    if (rc) return fail(nullptr, rc, err);
-    int blocks_per_cu = std::max(1, (int)(lds_max / (ctx->L.total * 4)));
-    blocks_per_cu = std::max(1, std::min(blocks_per_cu, 2048 / ctx->cfg.threads));   // 32 wavefronts per CU
-#ifndef FQ_HOSTSIM
-    {
-        // persistent workgroups: the grid must not exceed what is resident at once (registers bound it, not only LDS)
-        int nb = 0;
-        const void* kfn = ctx->split ? (ctx->cfg.threads > 256 ? (const void*)fq_scan_wide_kernel : (const void*)fq_scan_kernel) : (const void*)fq_fused_kernel;
-        (void)hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->L.total * 4);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kfn, ctx->cfg.threads, (size_t)ctx->L.total * 4) == hipSuccess && nb > 0)
-            blocks_per_cu = std::min(blocks_per_cu, nb);
-        (void)hipGetLastError();
-    }
-#endif
-    ctx->blocks = ctx->cus * blocks_per_cu;
-    // a workgroup's packed per-cycle counters hold CYC_MAX_READS reads per Stats slot
-    int tiles_per_block = CYC_MAX_READS / ctx->L.P;
-    const int cap_tiles = sw.max_tiles_per_block;  // tests: force several launches
-    if (cap_tiles > 0 && cap_tiles < tiles_per_block) tiles_per_block = cap_tiles;
-    if (tiles_per_block < 1) return fail(nullptr, FASTP_GPU_E_INVALID, "tile too large for the packed counters");
-    if (ctx->split) {
-        // the Stats kernel: form 5 where its joint table fits the device's LDS and the options allow it (stats5_copies), else form 4
-        StatsArgs& sa = ctx->t_stats;
-        sa.H = ctx->dp.qw_g / 2;
-        int hb = 0;
-        const int kc5 = stats5_copies(ctx->dp, lds_max, &hb);
-        if (kc5) {
-            sa.H16 = (ctx->dp.qw_g + 3) / 4;
-            // form 5 (fq_stats5.h): the joint table [2][8][4][ST5_QN][H16] of 16-bit cell pairs, KC copies of the mate's 5-mer
-            // counters, the packed cells of what the table has no cell for, the histogram of those, a list per wavefront - where it
-            // fits one workgroup's LDS (reads of up to 176 bases; merge mode's third pass exists in form 4 only)
-            int o = 0;
-            sa.l_cyc = o; o += 2 * 8 * 4 * ST5_QN * hb;
-            sa.l_kmer = o; o += 2 * KMER_BINS * kc5;
-            o = (o + 1) & ~1;
-            sa.l_ovf = o; o += 2 * ctx->L.Cp * N_CLS * 2;
-            sa.l_qh = o; o += 2 * 128;
-            sa.l_wl = o; o += (1024 / 64) * 2 * ST5_WL / 2;   // (u16 entries)
-            ctx->st_form = 5;
-            sa.kc = kc5;
-            sa.Hs = hb;                     // the table's columns: all of a read's (H16), or a block of them
-            ctx->st5_inst = stats5_inst_for(sa.Hs, sa.kc, sa.H16, stats5_no_front(ctx->dp));
-            ctx->st5_fn = stats5_kernel_for(ctx->st5_inst);
-            ctx->st_lds_dwords = o;
-            ctx->st_max_reads = CYC_MAX_READS;   // (a list entry holds the trip in 10 bits: 16 wavefronts x (64 / hb >= 4) units per trip, <= 256 trips)
-        } else {
-            // form 4 (fq_stats.h): [2][8][ST4_ROWS][Hs] u32 per-cycle cells of ONE mate, four copies of its 5-mer counters, its histogram;
-            // the class stride padded to 32 items (= all 64 banks)
-            ctx->st_form = 4;
-            sa.kc = 4;
-            sa.Hs = sa.H < 32 ? 32 : sa.H;
-            ctx->st_max_reads = ST4_MAX_READS;
-            for (;;) {
-                sa.wl_cap = 511;
-                int o = 0;
-                sa.l_cyc = o; o += 2 * 8 * ST4_ROWS * sa.Hs;
-                sa.l_kmer = o; o += 2 * KMER_BINS * sa.kc;
-                sa.l_qh = o; o += ST_QH_COPIES * 2 * 128;
-                o = (o + 3) & ~3;
-                sa.l_lut = o; o += 4 * 256;
-                sa.l_mt = o; o += 18 + 2;
-                sa.l_wl = o; o += 1 + sa.wl_cap;
-                ctx->st_lds_dwords = o;
-                if (2 * o * 4 <= lds_max) break;                          // two workgroups per CU
-                if (sa.Hs > sa.H) sa.Hs = sa.H;       // first the padding,
-                else if (sa.kc > 1) sa.kc /= 2;                 // then the copies
-                else break;
-            }
-        }
-        ctx->st_slab_dwords = 4 * ctx->L.Cp * N_CLS * 2 + 4 * KMER_BINS + 4 * 128;
-        ctx->st_threads = 1024;
-        if (ctx->st_lds_dwords * 4 > lds_max) return fail(nullptr, FASTP_GPU_E_INVALID, "reads too long for the Stats kernel's LDS");
-        const int st_per_cu = sw.stats_blocks_per_cu ? sw.stats_blocks_per_cu : std::min(2048 / ctx->st_threads, lds_max / (ctx->st_lds_dwords * 4));
-        ctx->st_blocks = ctx->cus * std::max(1, st_per_cu);
-        if (ctx->lane) {
-            ctx->ln_swm = ctx->dp.sw_g <= 10 ? 10 : 16;
-            LaneLds& l = ctx->ln_lds;
-            int o = 0;
-            l.n_misc = MISC_ISIZE + ctx->dp.isize_max + 1;
-            l.jkmer = 0;
-            if (ctx->dp.merge_lane) {   // the merged reads' junction 5-mers: counters behind the MISC_* ones (ReduceArgs::merge_tail)
-                l.jkmer = o + l.n_misc;
-                l.n_misc += KMER_BINS;
-            }
-            l.misc = o; o += l.n_misc;
-            const int lw = (ctx->dp.cycles + 2) / 2;
-            l.lut_ov = o; o += lw;
-            l.lut_lowq = o; o += lw;
-            l.lut_cplx = o; o += lw;
-            l.val4 = o; o += 256;
-            o = (o + 1) & ~1;
-            l.planes = o;
-            l.n_planes = ctx->dp.dup_enabled ? (int)ctx->luts.dup_planes.size() : 0;
-            o += l.n_planes;
-            o = (o + 3) & ~3;
-            l.stage = o;
-            l.stage_dwords = (64 * std::max(ctx->dp.qw_g, ctx->dp.sw_g) + 4 * ctx->ln_swm + 3) & ~3;   // + the over-read of the last row
-            l.part_dwords = ctx->dp.paired ? (ctx->ln_swm / 2) * 64 : 0;   // read 1 of a pair: [ln_swm / 2 words][64 lanes]
-            // as many wavefronts per workgroup as the LDS holds (up to three per SIMD for reads <= 160 bases, two above)
-            const int max_waves = (ctx->ln_swm > 10 ? 512 : 256 * FQ_LANE_WAVES) / 64;
-            l.clist_dwords = (ctx->dp.corr_lane && ctx->dp.paired) ? (ctx->ln_swm / 2) * 64 : 0;   // -c: read 1's edited positions, a bit mask per lane
-            // the workgroup's chunk counter (l.ctr below) and the reserve come out of the LDS before it is divided into
-            // wavefronts (o and every per-wavefront size are multiples of 4 dwords: no padding in front of l.ctr)
-            const int tail_dwords = LANE_CTR_DWORDS + LANE_RESERVED_DWORDS;
-            int waves = (int)(((long long)lds_max / 4 - o - tail_dwords) / (l.stage_dwords + l.part_dwords + l.clist_dwords));
-            waves = std::max(1, std::min(waves, max_waves));
-            ctx->ln_threads = waves * 64;
-            o += waves * l.stage_dwords;
-            l.part = o;
-            o += waves * l.part_dwords;
-            l.clist = o;
-            o += waves * l.clist_dwords;
-            o = (o + 3) & ~3;
-            l.ctr = o;
-            o += tail_dwords;
-            l.total = o;
-            int per_cu = 0;
-#ifndef FQ_HOSTSIM
-            {
-                int nb = 0;
-                lane_kernel_fn fn = lane_kernel_for(ctx->ln_swm, ctx->dp.dup_enabled ? ctx->dp.dup_bufnum : 0, ctx->dp.paired != 0, lane_ext(ctx->dp));
-                (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, l.total * 4);
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, ctx->ln_threads, (size_t)l.total * 4) == hipSuccess && nb > 0) per_cu = nb;
-                (void)hipGetLastError();
-            }
-#endif
-            if (per_cu <= 0) per_cu = 4;
-            ctx->ln_blocks = ctx->cus * per_cu;
-        }
-    }
-    // --cut_front on the lane plan (a front per read) has its POST Stats only in form 5 of the Stats kernel
-    if (ctx->lane && ctx->dp.front_per_read && ctx->st_form != 5)
-        return fail(nullptr, FASTP_GPU_E_INVALID, "a front per read on the lane plan needs form 5 of the Stats kernel, which was not chosen");
-    {   // every kernel's dynamic LDS against what the device gives a workgroup: a layout that does not fit fails here, never at a launch
-        const char* name = ctx->split ? (ctx->cfg.threads > 256 ? "scan_wide kernel" : "scan kernel") : "fused kernel";
-        std::vector<std::pair<const char*, long long>> need = {{name, (long long)ctx->L.total * 4}, {"hash kernel", (long long)ctx->L.total * 4},
-                                                               {"text kernel", (long long)TEXT_WAVES * text_wave_bytes((ctx->dp.max_len + 8 + 7) & ~7)},
-                                                               {"deflate kernel", (long long)sizeof(DefLds)},
-                                                               {"deflate kernel (levels 5 to 9)", (long long)sizeof(DefChainLds)},
-                                                               {"inflate kernel", (long long)(INF_ENTRIES * INF_LANES * 2 + INF_SBUF * INF_LANES * 4)}};
-        if (ctx->split) need.push_back({ctx->st_form == 5 ? "Stats kernel (form 5)" : "Stats kernel", (long long)ctx->st_lds_dwords * 4});
-        if (ctx->lane) need.push_back({"lane kernel", (long long)ctx->ln_lds.total * 4});
-        if (ctx->split && ctx->dp.front_per_read) need.push_back({"front Stats kernel", (long long)(ctx->dp.paired ? 2 : 1) * 34 * ctx->dp.cycles * 4});
-        if (ctx->split && ctx->dp.corr_lane)
-            need.push_back({"correction Stats kernel", (long long)(ctx->dp.paired ? 2 : 1) * (33 * ctx->dp.cycles + 128 + KMER_BINS) * 4});
-        for (const auto& k : need)
-            if (k.second > lds_max) {
-                const std::string m = std::string(k.first) + ": " + std::to_string(k.second) + " bytes of LDS per workgroup, the device has " +
-                                      std::to_string(lds_max);
-                return fail(nullptr, FASTP_GPU_E_INVALID, m);
-            }
-    }
-    {
-        long long mp = (long long)ctx->blocks * tiles_per_block * ctx->L.P;
-        if (ctx->split) {   // the per-read kernel has no packed counters; a Stats workgroup takes <= CYC_MAX_READS units
-            mp = (long long)ctx->st_blocks * CYC_MAX_READS;   // (form 4 takes such a launch as several rounds of workgroups)
-            if (ctx->st_form == 5) mp *= 2;                   // (one workgroup per CU: two rounds, as many units per launch as before)
-            if (cap_tiles > 0) mp = std::min(mp, (long long)ctx->blocks * cap_tiles * ctx->L.P);
-        }
-        if (mp > (1ll << DUP_IDX_BITS) - 1) mp = (1ll << DUP_IDX_BITS) - 1;
-        if (ctx->split && ctx->dp.corr_lane) {   // the launch's correction list (fill_launch_buffers): an entry for every base of every pair
-            // 2^29 entries (6 GiB with the chains) - or, on a card with 64 GiB to spare, just under 2^30: a -c / --merge step of 4 Mi
-            // pairs of 2x150 is then ONE launch instead of two (2 * index + 1 still fits an int)
-            long long entries = 1ll << 29;
-            size_t mfree = 0, mtotal = 0;
-            if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess && mfree >= ((size_t)64 << 30)) entries = (1ll << 30) - 64;
-            (void)hipGetLastError();
-            mp = std::min(mp, entries / std::max(1, ctx->dp.max_len));
-        }
-        mp = mp / ctx->L.P * ctx->L.P;
-        ctx->max_pairs_per_launch = (int)mp;
-    }
-    fastp_gpu_counter_layout_for_params(&ctx->params, &ctx->cl);
-    ctx->exact_all = sw.exact != 0;   // tests: every unit through the text kernel (fq_text.h)
-    if (ctx->exact_all && sw.verbose) fprintf(stderr, "fastp_gpu: FASTP_GPU_EXACT=1, every unit takes the text kernel\n");
-    if (sw.verbose)
-        fprintf(stderr, "fastp_gpu: %s, tile P=%d (%d rows), %d threads, LDS %d bytes, %d workgroups, %d units/launch; stats kernel form %d, %d x %d threads, LDS %d bytes\n",
-                ctx->lane ? "lane plan" : (ctx->split ? "split plan" : "fused plan"), ctx->L.P, ctx->L.NR, ctx->cfg.threads, ctx->L.total * 4, ctx->blocks,
-                ctx->max_pairs_per_launch, ctx->st_form, ctx->st_blocks, ctx->st_threads, ctx->st_lds_dwords * 4);
-    if (sw.verbose && ctx->lane)
-        fprintf(stderr, "fastp_gpu: lane kernel %d x %d threads (%d per CU), LDS %d bytes per workgroup (stage %d + read-1 sums %d per wavefront), SWM %d, ext %d\n",
-                ctx->ln_blocks, ctx->ln_threads, ctx->ln_blocks / std::max(1, ctx->cus), ctx->ln_lds.total * 4, ctx->ln_lds.stage_dwords * 4,
-                ctx->ln_lds.part_dwords * 4, ctx->ln_swm, (int)lane_ext(ctx->dp));
-    ctx->slab_dwords = ctx->L.acc_end - ctx->L.acc_cyc;
-
-    *out = owner.release();  // from here on errors go through destroy
-    fq::timeline("create: plan chosen (device properties, occupancy queries)");
-#define CREATE_TRY(call)                                               \
-    do {                                                               \
-        int r_ = [&]() -> int { HIP_TRY(ctx, call); return 0; }();     \
-        if (r_) { std::string m = ctx->err; fastp_gpu_destroy(ctx); *out = nullptr; return fail(nullptr, r_, m); } \
-    } while (0)
-    CREATE_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-    fq::timeline("create: launch stream created");
-    CREATE_TRY(hipFuncSetAttribute(ctx->split ? (ctx->cfg.threads > 256 ? (const void*)fq_scan_wide_kernel : (const void*)fq_scan_kernel) : (const void*)fq_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->L.total * 4));
-    CREATE_TRY(hipFuncSetAttribute((const void*)fq_hash_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->L.total * 4));
-    if (ctx->split) {
-        CREATE_TRY(hipFuncSetAttribute((const void*)fq_stats_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->st_lds_dwords * 4));
-        if (ctx->dp.front_per_read)
-            CREATE_TRY(hipFuncSetAttribute((const void*)fq_front_stats_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)((ctx->dp.paired ? 2 : 1) * 34 * (size_t)ctx->cl.cycles * 4)));
-        if (ctx->dp.corr_lane)
-            CREATE_TRY(hipFuncSetAttribute((const void*)fq_corr_stats_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)((ctx->dp.paired ? 2 : 1) * (33 * (size_t)ctx->cl.cycles + 128 + KMER_BINS) * 4)));
-        // a slab per workgroup of the largest launch: rounds of st_blocks for form 4, two rounds for form 5
-        ctx->st_max_grid = ctx->st_form == 4 ? (ctx->max_pairs_per_launch + ST4_MAX_READS - 1) / ST4_MAX_READS + ctx->st_blocks : 2 * ctx->st_blocks + 2;
-        if (ctx->st_form == 5) {
-            CREATE_TRY(hipFuncSetAttribute((const void*)ctx->st5_fn, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->st_lds_dwords * 4));
-#ifdef FQ_PROFILE_ABLATION
-            CREATE_TRY(hipFuncSetAttribute((const void*)stats5_kernel_for(ST5_ABLATION), hipFuncAttributeMaxDynamicSharedMemorySize, ctx->st_lds_dwords * 4));
-#endif
-        }
-        CREATE_TRY(hipMalloc((void**)&ctx->d_st_slabs, (size_t)ctx->st_max_grid * ctx->st_slab_dwords * 4));
-#ifdef FQ_HOSTSIM
-        CREATE_TRY(hipStreamCreateWithFlags(&ctx->tail, hipStreamNonBlocking));
-#else
-        // a second stream that really runs beside the first (fq_probe_wait_kernel): up to six candidates, the ones that share the
-        // first stream's queue are held until the search ends (the next one is then given another queue) and closed afterwards
-        int* d_flag = nullptr;
-        CREATE_TRY(hipMalloc((void**)&d_flag, 2 * sizeof(int)));
-        std::vector<hipStream_t> rejected;
-        const int tries = 6;
-        for (int t = 0; t < tries && !ctx->tail; t++) {
-            hipStream_t cand = nullptr;
-            CREATE_TRY(hipStreamCreateWithFlags(&cand, hipStreamNonBlocking));
-            CREATE_TRY(hipMemsetAsync(d_flag, 0, 2 * sizeof(int), ctx->stream));
-            CREATE_TRY(hipStreamSynchronize(ctx->stream));
-            hipLaunchKernelGGL(fq_probe_wait_kernel, dim3(1), dim3(64), 0, ctx->stream, d_flag, 2000000ll);
-            hipLaunchKernelGGL(fq_probe_set_kernel, dim3(1), dim3(64), 0, cand, d_flag);
-            CREATE_TRY(hipStreamSynchronize(cand));
-            CREATE_TRY(hipStreamSynchronize(ctx->stream));
-            int h[2] = {0, 0};
-            CREATE_TRY(hipMemcpy(h, d_flag, sizeof(h), hipMemcpyDeviceToHost));
-            if (h[1] != 0) ctx->tail = cand;
-            else rejected.push_back(cand);
-        }
-        if (!ctx->tail) { ctx->tail = rejected.back(); rejected.pop_back(); }   // (none runs beside it: correct, one behind the other)
-        if (sw.verbose) fprintf(stderr, "fastp_gpu: second stream: candidate %d of %d runs beside the first\n", (int)rejected.size() + 1, tries);
-        for (hipStream_t r : rejected) (void)hipStreamDestroy(r);
-        (void)hipFree(d_flag);
-#endif
-        fq::timeline("create: second stream probed");
-        CREATE_TRY(hipEventCreateWithFlags(&ctx->ev_k1, hipEventDisableTiming));
-        CREATE_TRY(hipEventCreateWithFlags(&ctx->ev_tail, hipEventDisableTiming));
-        if (ctx->lane) {
-            CREATE_TRY(hipMalloc((void**)&ctx->d_ln_slabs, (size_t)ctx->ln_blocks * ctx->ln_lds.n_misc * 4));
-            for (int Bh : {0, ctx->dp.dup_enabled ? ctx->dp.dup_bufnum : 0})
-                CREATE_TRY(hipFuncSetAttribute((const void*)lane_kernel_for(ctx->ln_swm, Bh, ctx->dp.paired != 0, lane_ext(ctx->dp)),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, ctx->ln_lds.total * 4));
-        }
-    }
-    CREATE_TRY(hipFuncSetAttribute((const void*)fq_ovr_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, aux_lds_cap(ctx)));
-    CREATE_TRY(hipFuncSetAttribute((const void*)fq_text_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, aux_lds_cap(ctx)));
-    CREATE_TRY(hipFuncSetAttribute((const void*)fq_deflate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(DefLds)));
-    CREATE_TRY(hipFuncSetAttribute((const void*)fq_deflate_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(DefChainLds)));
-    if ((int)sizeof(IwLds) <= ctx->lds_bytes)   // (a card with less LDS inflates with the lane kernel only)
-        CREATE_TRY(hipFuncSetAttribute((const void*)fq_inflate_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(IwLds)));
-    CREATE_TRY(hipFuncSetAttribute((const void*)fq_inflate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   INF_ENTRIES * INF_LANES * 2 + INF_SBUF * INF_LANES * 4));
-    fq::timeline("create: kernel attributes set");
-    auto upload = [&](void** dptr, const void* src, size_t bytes) -> int {
-        if (bytes == 0) { *dptr = nullptr; return 0; }
-        HIP_TRY(ctx, hipMalloc(dptr, bytes));
-        HIP_TRY(ctx, hipMemcpy(*dptr, src, bytes, hipMemcpyHostToDevice));
-        return 0;
-    };
-#define CREATE_RC(expr)                                                                                    \
-    do {                                                                                                   \
-        int r_ = (expr);                                                                                   \
-        if (r_) { std::string m = ctx->err; fastp_gpu_destroy(ctx); *out = nullptr; return fail(nullptr, r_, m); } \
-    } while (0)
-    CREATE_RC(upload((void**)&ctx->d_ov_limit, ctx->luts.ov_limit.data(), ctx->luts.ov_limit.size() * 2));
-    CREATE_RC(upload((void**)&ctx->d_lowq, ctx->luts.lowq_limit.data(), ctx->luts.lowq_limit.size() * 2));
-    CREATE_RC(upload((void**)&ctx->d_cplx, ctx->luts.cplx_min.data(), ctx->luts.cplx_min.size() * 2));
-    CREATE_RC(upload((void**)&ctx->d_primes, ctx->luts.dup_primes.data(), ctx->luts.dup_primes.size() * 4));
-    CREATE_RC(upload((void**)&ctx->d_planes, ctx->luts.dup_planes.data(), ctx->luts.dup_planes.size() * 4));
-    CREATE_RC(upload((void**)&ctx->d_posum, ctx->luts.dup_posum.data(), ctx->luts.dup_posum.size() * 8));
-    CREATE_RC(upload((void**)&ctx->d_fasta_words, ctx->luts.fasta_words.data(), ctx->luts.fasta_words.size() * 4));
-    CREATE_RC(upload((void**)&ctx->d_fasta_len, ctx->luts.fasta_len.data(), ctx->luts.fasta_len.size() * 4));
-    if (ctx->dp.overrep) {
-        for (int m = 0; m < 2; m++) {
-            CREATE_RC(upload((void**)&ctx->d_ovr_table[m], ctx->luts.ovr_table[m].data(), ctx->luts.ovr_table[m].size() * 4));
-            CREATE_RC(upload((void**)&ctx->d_ovr_sym[m], ctx->luts.ovr_sym[m].data(), ctx->luts.ovr_sym[m].size()));
-            CREATE_RC(upload((void**)&ctx->d_ovr_len[m], ctx->luts.ovr_len[m].data(), ctx->luts.ovr_len[m].size() * 4));
-        }
-        const uint64_t zero = 0;
-        CREATE_RC(upload((void**)&ctx->d_post_seen, &zero, sizeof(zero)));
-    }
-    {
-        std::vector<int64_t> zero((size_t)ctx->cl.total, 0);
-        zero[0] = FASTP_GPU_ABI_VERSION;
-        zero[1] = ctx->cl.cycles;
-        zero[2] = ctx->dp.isize_max;
-        CREATE_RC(upload((void**)&ctx->d_ctr, zero.data(), zero.size() * 8));
-    }
-    CREATE_TRY(hipMalloc((void**)&ctx->d_slabs, (size_t)ctx->blocks * ctx->slab_dwords * 4));
-    if (ctx->dp.dup_enabled) {
-        const size_t bytes = (size_t)(ctx->dp.dup_bits >> 3) * ctx->dp.dup_bufnum;
-        CREATE_TRY(hipMalloc((void**)&ctx->d_bitmap, bytes));
-        CREATE_TRY(hipMemsetAsync(ctx->d_bitmap, 0, bytes, ctx->stream));
-    }
-    if (sw.phase_timing) {
-        CREATE_TRY(hipMalloc((void**)&ctx->d_phase, 16 * sizeof(u64)));
-        CREATE_TRY(hipMemsetAsync(ctx->d_phase, 0, 16 * sizeof(u64), ctx->stream));
-    }
-    CREATE_TRY(hipStreamSynchronize(ctx->stream));
-    fill_arg_templates(ctx);
-#ifndef FQ_HOSTSIM
-    if (ctx->split && ctx->st_form == 5) {   // what stays free beside the Stats kernel's waves, and for whom
-        int32_t kr[KERNEL_REGS_N];
-        CREATE_RC(fastp_gpu_debug_kernel_regs(ctx, kr, KERNEL_REGS_N));
-        const int waves = ctx->st_threads / 64 / 4, alloc = (kr[1] + 7) & ~7, left = 512 - waves * alloc;
-        // Duplicate's finish is a grid-stride loop over the units: any workgroup size does.  As 1024 lanes (four waves per SIMD) it
-        // never fitted what the Stats kernel leaves, waited for that kernel's workgroups to go and ended the step behind it; the
-        // largest size that fits runs beside it like losers and winners do.  Nothing fits beside a 128-VGPR instantiation: 1024 stays.
-        // Paired contexts only: a single-end unit has half the bases, the Stats kernel ends BEFORE Duplicate's chain does (10 M reads:
-        // 540 us against 40 + 230 + 320), and alone on the chip finish is slower in small workgroups - 234 us against 67, four times
-        // the workgroups and as many adds to one counter (profiles/r08_a_step_tail.txt: the single-end step was 8 - 10 % slower).
-        const int finish_a8 = (kr[13] + 7) & ~7;
-        for (int t = 1024; t >= 256 && ctx->dp.paired; t >>= 1)
-            if (kr[13] > 0 && t <= kr[14] && (t / 256) * finish_a8 <= left) { ctx->finish_threads = t; break; }
-        if (sw.verbose) {
-            const char* names[4] = {"fq_reduce_kernel", "fq_dup_losers_kernel", "fq_dup_winners_kernel", "fq_dup_finish_kernel"};
-            std::string fits;
-            for (int k = 0; k < 4; k++) {   // a workgroup of the kernel as launched (256 lanes = a wave per SIMD, 1024 = four) in what is left
-                const int a8 = (kr[4 + 3 * k] + 7) & ~7, wg_waves = std::max(1, (k == 3 ? ctx->finish_threads : kr[5 + 3 * k]) / 64 / 4);
-                if (a8 * wg_waves <= left)
-                    fits += std::string(fits.empty() ? "" : ", ") + names[k] + " (" + std::to_string(wg_waves) + " x " + std::to_string(a8) + ")";
-            }
-            fprintf(stderr, "fastp_gpu: stats kernel instantiation %d: %d VGPRs (allocated %d), %d waves per SIMD, %d registers per SIMD left; a workgroup fits beside it of: %s; fq_dup_finish_kernel runs as %d lanes\n",
-                    ctx->st5_inst, kr[1], alloc, waves, left, fits.empty() ? "none" : fits.c_str(), ctx->finish_threads);
-        }
-    }
-#endif
-    fq::timeline("create: end (tables uploaded, bloom filter cleared)");
-    return FASTP_GPU_OK;
-}
-
-// debugging aid (not part of the drop-in surface): cycles spent per phase of the fused kernel,
-// summed over workgroups, when the context was created with FASTP_GPU_PHASE_TIMING=1
-extern "C" int fastp_gpu_debug_phase_cycles(fastp_gpu_ctx* ctx, uint64_t* out16) {
-    if (!ctx || !out16 || !ctx->d_phase) return FASTP_GPU_E_INVALID;
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    HIP_TRY(ctx, hipMemcpy(out16, ctx->d_phase, 16 * sizeof(u64), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemset(ctx->d_phase, 0, 16 * sizeof(u64)));
-    return FASTP_GPU_OK;
-}
-
 // debugging aid: what the runtime allocates the Stats kernel this context launches and the tail stream's small kernels -
 // out[0] the instantiation of form 5 (ST5_*; -1: form 4), then {VGPRs, max threads per workgroup, static LDS bytes} of the
 // Stats kernel, fq_reduce_kernel, fq_dup_losers_kernel, fq_dup_winners_kernel, fq_dup_finish_kernel.  Whether a wave of a tail
 // kernel fits beside the Stats kernel's four per SIMD is arithmetic on these (granules of 8 of a 512-entry file per SIMD).
 // The emulator has no such attributes: zeros behind out[0].
+enum { KERNEL_REGS_N = 16 };
 extern "C" int fastp_gpu_debug_kernel_regs(fastp_gpu_ctx* ctx, int32_t* out, int32_t n) {
     if (!ctx || !out || n < KERNEL_REGS_N) return FASTP_GPU_E_INVALID;
     for (int i = 0; i < n; i++) out[i] = 0;
@@ -1108,6 +744,463 @@ extern "C" int fastp_gpu_debug_kernel_regs(fastp_gpu_ctx* ctx, int32_t* out, int
         out[3 + 3 * k] = (int32_t)fa.sharedSizeBytes;
     }
 #endif
+    return FASTP_GPU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// fastp_gpu_create, step by step.  Every step is `static int step(fastp_gpu_ctx*)`: it returns a FASTP_GPU_* code and leaves its
+// message through fail() / HIP_TRY.  fastp_gpu_create owns the context from `new` to its last line, so a step that fails just
+// returns: whatever the steps before it made goes with the context (fastp_gpu_destroy).
+// ---------------------------------------------------------------------------
+
+// own copies of the strings ctx->params points to: the caller's may go away
+static int own_param_strings(fastp_gpu_ctx* ctx) {
+    fastp_gpu_params& p = ctx->params;
+    if (p.adapter_seq_r1) ctx->adapter1 = p.adapter_seq_r1;
+    if (p.adapter_seq_r2) ctx->adapter2 = p.adapter_seq_r2;
+    p.adapter_seq_r1 = ctx->adapter1.c_str();
+    p.adapter_seq_r2 = ctx->adapter2.c_str();
+    if (p.n_adapter_fasta > 0 && p.adapter_fasta) {
+        for (int i = 0; i < p.n_adapter_fasta; i++) ctx->fasta_strings.push_back(p.adapter_fasta[i] ? p.adapter_fasta[i] : "");
+        for (auto& f : ctx->fasta_strings) ctx->fasta_ptrs.push_back(f.c_str());
+        p.adapter_fasta = ctx->fasta_ptrs.data();
+    }
+    if (p.overrep_enabled) {  // the seed strings
+        const char* const* lists[2] = {p.overrep_seqs1, p.overrep_seqs2};
+        const int ns[2] = {p.n_overrep_seqs1, p.n_overrep_seqs2};
+        for (int m = 0; m < 2; m++) {
+            for (int i = 0; i < ns[m] && lists[m]; i++) ctx->ovr_strings[m].push_back(lists[m][i] ? lists[m][i] : "");
+            for (auto& q : ctx->ovr_strings[m]) ctx->ovr_ptrs[m].push_back(q.c_str());
+        }
+        p.overrep_seqs1 = ctx->ovr_ptrs[0].data();
+        p.overrep_seqs2 = ctx->ovr_ptrs[1].data();
+    }
+    return 0;
+}
+
+// the options as the device code takes them (fq_host.cpp) and the device's properties
+static int read_params_and_device(fastp_gpu_ctx* ctx) {
+    std::string err;
+    const int rc = build_dev_params(ctx->params, ctx->dp, ctx->luts, err);
+    if (rc) return fail(ctx, rc, err);
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, FASTP_GPU_E_HIP, "hipSetDevice failed");
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) return fail(ctx, FASTP_GPU_E_HIP, "hipGetDeviceProperties failed");
+    ctx->cus = prop.multiProcessorCount;
+    ctx->lds_bytes = (int)std::min<size_t>(prop.sharedMemPerBlock, (size_t)1 << 30);
+    return 0;
+}
+
+// The plan and the tile kernel's geometry (tunable without a rebuild).
+// The split plan (per-read kernel as 256-lane workgroups, several per CU, + the streaming Stats kernel) whenever no
+// option moves or edits a kept base; FASTP_GPU_SPLIT=0 keeps Stats inside the one-workgroup-per-CU fused kernel.
+// the Stats kernel as its own launch: options that leave every kept base where it was, or (lane plan only) move it by the
+// same front for every read that is written out (DevParams::front_lane)
+static int choose_plan(fastp_gpu_ctx* ctx) {
+    const Switches& sw = ctx->sw;
+    const int lds_max = ctx->lds_bytes;
+    const int lds_kb_default = lds_max / 1024 >= 160 ? 160 : lds_max / 1024;
+    if (sw.hash_generic) {  // tests: the multiply form of the duplicate hash (what B = 8 uses; the lane plan has none)
+        ctx->luts.dup_planes.clear();
+        ctx->luts.dup_nq = 0;
+    }
+    const bool lane_wanted = sw.lane != 0 && lane_plan_supported(ctx->dp, ctx->luts, lds_max);
+    ctx->split = (ctx->dp.stats_one_pass || ((ctx->dp.front_lane || ctx->dp.corr_lane || ctx->dp.merge_lane) && lane_wanted)) && sw.split != 0;
+    ctx->lane = ctx->split && lane_wanted;
+    ctx->cfg.split = ctx->split ? 1 : 0;
+    ctx->cfg.threads = sw.threads ? sw.threads : (ctx->split ? 256 : 1024);
+    ctx->cfg.P = sw.tile;
+    // (FASTP_GPU_LDS_KB above what the device has is clamped to it: a budget the card cannot give would only fail the launch)
+    ctx->cfg.lds_budget = std::min(sw.lds_kb ? sw.lds_kb : (ctx->split ? std::min(40, lds_kb_default) : lds_kb_default), lds_max / 1024) * 1024;
+    if (ctx->cfg.threads < 64 || ctx->cfg.threads > 1024 || (ctx->cfg.threads & 63))
+        return fail(ctx, FASTP_GPU_E_INVALID, "FASTP_GPU_THREADS must be a multiple of 64 in 64..1024");
+    std::string err;
+    int rc = compute_lds_layout(ctx->dp, ctx->cfg, ctx->L, err, ctx->luts.dup_nq);
+    if (rc && ctx->split && !sw.lds_kb) {  // long reads (or a tile size asked for): the small budget holds no such tile
+        ctx->cfg.lds_budget = lds_kb_default * 1024;
+        rc = compute_lds_layout(ctx->dp, ctx->cfg, ctx->L, err, ctx->luts.dup_nq);
+    }
+    if (rc) return fail(ctx, rc, err);
+    int blocks_per_cu = std::max(1, (int)(lds_max / (ctx->L.total * 4)));
+    blocks_per_cu = std::max(1, std::min(blocks_per_cu, 2048 / ctx->cfg.threads));   // 32 wavefronts per CU
+#ifndef FQ_HOSTSIM
+    {
+        // persistent workgroups: the grid must not exceed what is resident at once (registers bound it, not only LDS)
+        int nb = 0;
+        const void* kfn = tile_kernel_for(ctx);
+        (void)hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->L.total * 4);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kfn, ctx->cfg.threads, (size_t)ctx->L.total * 4) == hipSuccess && nb > 0)
+            blocks_per_cu = std::min(blocks_per_cu, nb);
+        (void)hipGetLastError();
+    }
+#endif
+    ctx->blocks = ctx->cus * blocks_per_cu;
+    // a workgroup's packed per-cycle counters hold CYC_MAX_READS reads per Stats slot
+    ctx->tiles_per_block = CYC_MAX_READS / ctx->L.P;
+    if (sw.max_tiles_per_block > 0 && sw.max_tiles_per_block < ctx->tiles_per_block) ctx->tiles_per_block = sw.max_tiles_per_block;  // tests: force several launches
+    if (ctx->tiles_per_block < 1) return fail(ctx, FASTP_GPU_E_INVALID, "tile too large for the packed counters");
+    return 0;
+}
+
+// the Stats kernel of a split plan: form 5 where its joint table fits the device's LDS and the options allow it (stats5_copies), else form 4
+static int plan_stats_kernel(fastp_gpu_ctx* ctx) {
+    if (!ctx->split) return 0;
+    const int lds_max = ctx->lds_bytes;
+    StatsArgs& sa = ctx->t_stats;
+    sa.H = ctx->dp.qw_g / 2;
+    int hb = 0;
+    const int kc5 = stats5_copies(ctx->dp, lds_max, &hb);
+    if (kc5) {
+        ctx->st_form = 5;
+        sa.H16 = (ctx->dp.qw_g + 3) / 4;
+        sa.kc = kc5;
+        sa.Hs = hb;                     // the table's columns: all of a read's (H16), or a block of them
+        ctx->st_lds_dwords = stats5_lds_layout(sa, ctx->L.Cp, hb, kc5);
+        ctx->st5_inst = stats5_inst_for(sa.Hs, sa.kc, sa.H16, stats5_no_front(ctx->dp));
+        ctx->st5_fn = stats5_kernel_for(ctx->st5_inst);
+        ctx->st_max_reads = CYC_MAX_READS;   // (a list entry holds the trip in 10 bits: 16 wavefronts x (64 / hb >= 4) units per trip, <= 256 trips)
+    } else {
+        ctx->st_form = 4;
+        ctx->st_lds_dwords = stats4_lds_layout(sa, lds_max);
+        ctx->st_max_reads = ST4_MAX_READS;
+    }
+    ctx->st_slab_dwords = 4 * ctx->L.Cp * N_CLS * 2 + 4 * KMER_BINS + 4 * 128;
+    ctx->st_threads = 1024;
+    if (ctx->st_lds_dwords * 4 > lds_max) return fail(ctx, FASTP_GPU_E_INVALID, "reads too long for the Stats kernel's LDS");
+    const int st_per_cu = ctx->sw.stats_blocks_per_cu ? ctx->sw.stats_blocks_per_cu : std::min(2048 / ctx->st_threads, lds_max / (ctx->st_lds_dwords * 4));
+    ctx->st_blocks = ctx->cus * std::max(1, st_per_cu);
+    return 0;
+}
+
+// the lane kernel of a lane plan: its LDS layout, as many wavefronts per workgroup as that leaves room for, its grid
+static int plan_lane_kernel(fastp_gpu_ctx* ctx) {
+    if (!ctx->lane) return 0;
+    // --cut_front on the lane plan (a front per read) has its POST Stats only in form 5 of the Stats kernel
+    if (ctx->dp.front_per_read && ctx->st_form != 5)
+        return fail(ctx, FASTP_GPU_E_INVALID, "a front per read on the lane plan needs form 5 of the Stats kernel, which was not chosen");
+    ctx->ln_swm = ctx->dp.sw_g <= 10 ? 10 : 16;
+    LaneLds& l = ctx->ln_lds;
+    int o = 0;
+    l.n_misc = MISC_ISIZE + ctx->dp.isize_max + 1;
+    l.jkmer = 0;
+    if (ctx->dp.merge_lane) {   // the merged reads' junction 5-mers: counters behind the MISC_* ones (ReduceArgs::merge_tail)
+        l.jkmer = o + l.n_misc;
+        l.n_misc += KMER_BINS;
+    }
+    l.misc = o; o += l.n_misc;
+    const int lw = (ctx->dp.cycles + 2) / 2;
+    l.lut_ov = o; o += lw;
+    l.lut_lowq = o; o += lw;
+    l.lut_cplx = o; o += lw;
+    l.val4 = o; o += 256;
+    o = (o + 1) & ~1;
+    l.planes = o;
+    l.n_planes = ctx->dp.dup_enabled ? (int)ctx->luts.dup_planes.size() : 0;
+    o += l.n_planes;
+    o = (o + 3) & ~3;
+    l.stage = o;
+    l.stage_dwords = (64 * std::max(ctx->dp.qw_g, ctx->dp.sw_g) + 4 * ctx->ln_swm + 3) & ~3;   // + the over-read of the last row
+    l.part_dwords = ctx->dp.paired ? (ctx->ln_swm / 2) * 64 : 0;   // read 1 of a pair: [ln_swm / 2 words][64 lanes]
+    // as many wavefronts per workgroup as the LDS holds (up to three per SIMD for reads <= 160 bases, two above)
+    const int max_waves = (ctx->ln_swm > 10 ? 512 : 256 * FQ_LANE_WAVES) / 64;
+    l.clist_dwords = (ctx->dp.corr_lane && ctx->dp.paired) ? (ctx->ln_swm / 2) * 64 : 0;   // -c: read 1's edited positions, a bit mask per lane
+    // the workgroup's chunk counter (l.ctr below) and the reserve come out of the LDS before it is divided into
+    // wavefronts (o and every per-wavefront size are multiples of 4 dwords: no padding in front of l.ctr)
+    const int tail_dwords = LANE_CTR_DWORDS + LANE_RESERVED_DWORDS;
+    int waves = (int)(((long long)ctx->lds_bytes / 4 - o - tail_dwords) / (l.stage_dwords + l.part_dwords + l.clist_dwords));
+    waves = std::max(1, std::min(waves, max_waves));
+    ctx->ln_threads = waves * 64;
+    o += waves * l.stage_dwords;
+    l.part = o;
+    o += waves * l.part_dwords;
+    l.clist = o;
+    o += waves * l.clist_dwords;
+    o = (o + 3) & ~3;
+    l.ctr = o;
+    o += tail_dwords;
+    l.total = o;
+    int per_cu = 0;
+#ifndef FQ_HOSTSIM
+    {
+        int nb = 0;
+        lane_kernel_fn fn = lane_kernel_for(ctx->ln_swm, ctx->dp.dup_enabled ? ctx->dp.dup_bufnum : 0, ctx->dp.paired != 0, lane_ext(ctx->dp));
+        (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, l.total * 4);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, ctx->ln_threads, (size_t)l.total * 4) == hipSuccess && nb > 0) per_cu = nb;
+        (void)hipGetLastError();
+    }
+#endif
+    if (per_cu <= 0) per_cu = 4;
+    ctx->ln_blocks = ctx->cus * per_cu;
+    return 0;
+}
+
+// Every kernel with dynamic LDS the context may launch: what its layout needs and what its attribute is set to.  The rows with a
+// check stay in this order: check_kernel_lds names the first that does not fit.
+static std::vector<KernelLds> kernel_lds_table(const fastp_gpu_ctx* ctx) {
+    const DevParams& dp = ctx->dp;
+    const char* tile_name = nullptr;
+    const void* tile = tile_kernel_for(ctx, &tile_name);
+    const int tile_bytes = ctx->L.total * 4, st_bytes = ctx->st_lds_dwords * 4, ln_bytes = ctx->ln_lds.total * 4;
+    std::vector<KernelLds> t = {
+        {tile_name, tile, tile_bytes, tile_bytes},
+        {"hash kernel", (const void*)fq_hash_kernel, tile_bytes, tile_bytes},
+        {"text kernel", (const void*)fq_text_kernel, (long long)TEXT_WAVES * text_wave_bytes((dp.max_len + 8 + 7) & ~7), aux_lds_cap(ctx)},
+        {"deflate kernel", (const void*)fq_deflate_kernel, (long long)sizeof(DefLds), (int)sizeof(DefLds)},
+        {"deflate kernel (levels 5 to 9)", (const void*)fq_deflate_chain_kernel, (long long)sizeof(DefChainLds), (int)sizeof(DefChainLds)},
+        {"inflate kernel", (const void*)fq_inflate_kernel, inflate_lane_lds_bytes(), inflate_lane_lds_bytes()}};
+    if (ctx->split) {   // (form 4's kernel has its attribute in a form 5 context as well)
+        if (ctx->st_form == 5) t.push_back({"Stats kernel (form 5)", (const void*)ctx->st5_fn, st_bytes, st_bytes});
+        t.push_back({"Stats kernel", (const void*)fq_stats_kernel, ctx->st_form == 5 ? LDS_NO_CHECK : st_bytes, st_bytes});
+#ifdef FQ_PROFILE_ABLATION
+        if (ctx->st_form == 5) t.push_back({"Stats kernel (ablation)", (const void*)stats5_kernel_for(ST5_ABLATION), LDS_NO_CHECK, st_bytes});
+#endif
+    }
+    if (ctx->lane) {   // the instantiation that hashes nothing, and the one that hashes for Duplicate
+        t.push_back({"lane kernel", (const void*)lane_kernel_for(ctx->ln_swm, 0, dp.paired != 0, lane_ext(dp)), ln_bytes, ln_bytes});
+        if (dp.dup_enabled)
+            t.push_back({"lane kernel", (const void*)lane_kernel_for(ctx->ln_swm, dp.dup_bufnum, dp.paired != 0, lane_ext(dp)), LDS_NO_CHECK, ln_bytes});
+    }
+    if (ctx->split && dp.front_per_read)
+        t.push_back({"front Stats kernel", (const void*)fq_front_stats_kernel, (long long)front_stats_lds_bytes(ctx), (int)front_stats_lds_bytes(ctx)});
+    if (ctx->split && dp.corr_lane)
+        t.push_back({"correction Stats kernel", (const void*)fq_corr_stats_kernel, (long long)corr_stats_lds_bytes(ctx), (int)corr_stats_lds_bytes(ctx)});
+    // attribute only: the count kernel sizes its tables to aux_lds_cap at each launch like the text kernel; a card with less LDS
+    // than the wave inflate kernel takes inflates with the lane kernel only
+    t.push_back({"overrepresentation count kernel", (const void*)fq_ovr_count_kernel, LDS_NO_CHECK, aux_lds_cap(ctx)});
+    if ((int)sizeof(IwLds) <= ctx->lds_bytes) t.push_back({"inflate wave kernel", (const void*)fq_inflate_wave_kernel, LDS_NO_CHECK, (int)sizeof(IwLds)});
+    return t;
+}
+
+// every kernel's dynamic LDS against what the device gives a workgroup: a layout that does not fit fails here, never at a launch
+static int check_kernel_lds(fastp_gpu_ctx* ctx) {
+    ctx->kernel_lds = kernel_lds_table(ctx);
+    for (const KernelLds& k : ctx->kernel_lds)
+        if (k.need > ctx->lds_bytes)
+            return fail(ctx, FASTP_GPU_E_INVALID, std::string(k.name) + ": " + std::to_string(k.need) + " bytes of LDS per workgroup, the device has " +
+                                                      std::to_string(ctx->lds_bytes));
+    return 0;
+}
+
+// the most units one launch takes, and the Stats slabs such a launch needs
+static int plan_launch_size(fastp_gpu_ctx* ctx) {
+    const int cap_tiles = ctx->sw.max_tiles_per_block;
+    long long mp = (long long)ctx->blocks * ctx->tiles_per_block * ctx->L.P;
+    if (ctx->split) {   // the per-read kernel has no packed counters; a Stats workgroup takes <= CYC_MAX_READS units
+        mp = (long long)ctx->st_blocks * CYC_MAX_READS;   // (form 4 takes such a launch as several rounds of workgroups)
+        if (ctx->st_form == 5) mp *= 2;                   // (one workgroup per CU: two rounds, as many units per launch as before)
+        if (cap_tiles > 0) mp = std::min(mp, (long long)ctx->blocks * cap_tiles * ctx->L.P);
+    }
+    if (mp > (1ll << DUP_IDX_BITS) - 1) mp = (1ll << DUP_IDX_BITS) - 1;
+    if (ctx->split && ctx->dp.corr_lane) {   // the launch's correction list (fill_launch_buffers): an entry for every base of every pair
+        // 2^29 entries (6 GiB with the chains) - or, on a card with 64 GiB to spare, just under 2^30: a -c / --merge step of 4 Mi
+        // pairs of 2x150 is then ONE launch instead of two (2 * index + 1 still fits an int)
+        long long entries = 1ll << 29;
+        size_t mfree = 0, mtotal = 0;
+        if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess && mfree >= ((size_t)64 << 30)) entries = (1ll << 30) - 64;
+        (void)hipGetLastError();
+        mp = std::min(mp, entries / std::max(1, ctx->dp.max_len));
+    }
+    mp = mp / ctx->L.P * ctx->L.P;
+    ctx->max_pairs_per_launch = (int)mp;
+    // a slab per workgroup of the largest launch: rounds of st_blocks for form 4, two rounds for form 5
+    if (ctx->split)
+        ctx->st_max_grid = ctx->st_form == 4 ? (ctx->max_pairs_per_launch + ST4_MAX_READS - 1) / ST4_MAX_READS + ctx->st_blocks : 2 * ctx->st_blocks + 2;
+    ctx->slab_dwords = ctx->L.acc_end - ctx->L.acc_cyc;
+    return 0;
+}
+
+// FASTP_GPU_VERBOSE=1: the geometry lines on stderr
+static int print_geometry(fastp_gpu_ctx* ctx) {
+    if (!ctx->sw.verbose) return 0;
+    if (ctx->exact_all) fprintf(stderr, "fastp_gpu: FASTP_GPU_EXACT=1, every unit takes the text kernel\n");
+    fprintf(stderr, "fastp_gpu: %s, tile P=%d (%d rows), %d threads, LDS %d bytes, %d workgroups, %d units/launch; stats kernel form %d, %d x %d threads, LDS %d bytes\n",
+            ctx->lane ? "lane plan" : (ctx->split ? "split plan" : "fused plan"), ctx->L.P, ctx->L.NR, ctx->cfg.threads, ctx->L.total * 4, ctx->blocks,
+            ctx->max_pairs_per_launch, ctx->st_form, ctx->st_blocks, ctx->st_threads, ctx->st_lds_dwords * 4);
+    if (ctx->lane)
+        fprintf(stderr, "fastp_gpu: lane kernel %d x %d threads (%d per CU), LDS %d bytes per workgroup (stage %d + read-1 sums %d per wavefront), SWM %d, ext %d\n",
+                ctx->ln_blocks, ctx->ln_threads, ctx->ln_blocks / std::max(1, ctx->cus), ctx->ln_lds.total * 4, ctx->ln_lds.stage_dwords * 4,
+                ctx->ln_lds.part_dwords * 4, ctx->ln_swm, (int)lane_ext(ctx->dp));
+    return 0;
+}
+
+#ifndef FQ_HOSTSIM
+// a second stream that really runs beside the first (fq_probe_wait_kernel): up to six candidates, the ones that share the
+// first stream's queue are held until the search ends (the next one is then given another queue) and closed afterwards
+static int probe_tail_stream(fastp_gpu_ctx* ctx) {
+    int* d_flag = nullptr;
+    HIP_TRY(ctx, hipMalloc((void**)&d_flag, 2 * sizeof(int)));
+    std::vector<hipStream_t> rejected;
+    const int tries = 6;
+    for (int t = 0; t < tries && !ctx->tail; t++) {
+        hipStream_t cand = nullptr;
+        HIP_TRY(ctx, hipStreamCreateWithFlags(&cand, hipStreamNonBlocking));
+        HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 2 * sizeof(int), ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        hipLaunchKernelGGL(fq_probe_wait_kernel, dim3(1), dim3(64), 0, ctx->stream, d_flag, 2000000ll);
+        hipLaunchKernelGGL(fq_probe_set_kernel, dim3(1), dim3(64), 0, cand, d_flag);
+        HIP_TRY(ctx, hipStreamSynchronize(cand));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        int h[2] = {0, 0};
+        HIP_TRY(ctx, hipMemcpy(h, d_flag, sizeof(h), hipMemcpyDeviceToHost));
+        if (h[1] != 0) ctx->tail = cand;
+        else rejected.push_back(cand);
+    }
+    if (!ctx->tail) { ctx->tail = rejected.back(); rejected.pop_back(); }   // (none runs beside it: correct, one behind the other)
+    if (ctx->sw.verbose) fprintf(stderr, "fastp_gpu: second stream: candidate %d of %d runs beside the first\n", (int)rejected.size() + 1, tries);
+    for (hipStream_t r : rejected) (void)hipStreamDestroy(r);
+    (void)hipFree(d_flag);
+    return 0;
+}
+#endif
+
+// the launch stream and, in the split plans, the tail stream with the two events that order them
+static int create_streams(fastp_gpu_ctx* ctx) {
+    HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
+    fq::timeline("create: launch stream created");
+    if (!ctx->split) return 0;
+#ifdef FQ_HOSTSIM
+    HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->tail, hipStreamNonBlocking));
+#else
+    const int rc = probe_tail_stream(ctx);
+    if (rc) return rc;
+#endif
+    fq::timeline("create: second stream probed");
+    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_k1, hipEventDisableTiming));
+    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_tail, hipEventDisableTiming));
+    return 0;
+}
+
+static int set_kernel_attributes(fastp_gpu_ctx* ctx) {
+    for (const KernelLds& k : ctx->kernel_lds) {
+        const hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.set);
+        if (e != hipSuccess)
+            return fail(ctx, FASTP_GPU_E_HIP, std::string("hipFuncSetAttribute(") + k.name + ", MaxDynamicSharedMemorySize, " + std::to_string(k.set) + "): " + hipGetErrorString(e));
+    }
+    fq::timeline("create: kernel attributes set");
+    return 0;
+}
+
+static int upload(fastp_gpu_ctx* ctx, void** dptr, const void* src, size_t bytes) {
+    if (bytes == 0) { *dptr = nullptr; return 0; }
+    HIP_TRY(ctx, hipMalloc(dptr, bytes));
+    HIP_TRY(ctx, hipMemcpy(*dptr, src, bytes, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// the buffers whose size create knows (slabs, bloom filter) and the tables the kernels read
+static int upload_tables(fastp_gpu_ctx* ctx) {
+    const HostLuts& luts = ctx->luts;
+    if (ctx->split) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_st_slabs, (size_t)ctx->st_max_grid * ctx->st_slab_dwords * 4));
+    if (ctx->lane) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_ln_slabs, (size_t)ctx->ln_blocks * ctx->ln_lds.n_misc * 4));
+    struct { void** dptr; const void* src; size_t bytes; } tables[] = {
+        {(void**)&ctx->d_ov_limit, luts.ov_limit.data(), luts.ov_limit.size() * 2},
+        {(void**)&ctx->d_lowq, luts.lowq_limit.data(), luts.lowq_limit.size() * 2},
+        {(void**)&ctx->d_cplx, luts.cplx_min.data(), luts.cplx_min.size() * 2},
+        {(void**)&ctx->d_primes, luts.dup_primes.data(), luts.dup_primes.size() * 4},
+        {(void**)&ctx->d_planes, luts.dup_planes.data(), luts.dup_planes.size() * 4},
+        {(void**)&ctx->d_posum, luts.dup_posum.data(), luts.dup_posum.size() * 8},
+        {(void**)&ctx->d_fasta_words, luts.fasta_words.data(), luts.fasta_words.size() * 4},
+        {(void**)&ctx->d_fasta_len, luts.fasta_len.data(), luts.fasta_len.size() * 4}};
+    int rc = 0;
+    for (const auto& t : tables)
+        if ((rc = upload(ctx, t.dptr, t.src, t.bytes))) return rc;
+    if (ctx->dp.overrep) {
+        for (int m = 0; m < 2; m++) {
+            if ((rc = upload(ctx, (void**)&ctx->d_ovr_table[m], luts.ovr_table[m].data(), luts.ovr_table[m].size() * 4))) return rc;
+            if ((rc = upload(ctx, (void**)&ctx->d_ovr_sym[m], luts.ovr_sym[m].data(), luts.ovr_sym[m].size()))) return rc;
+            if ((rc = upload(ctx, (void**)&ctx->d_ovr_len[m], luts.ovr_len[m].data(), luts.ovr_len[m].size() * 4))) return rc;
+        }
+        const uint64_t zero = 0;
+        if ((rc = upload(ctx, (void**)&ctx->d_post_seen, &zero, sizeof(zero)))) return rc;
+    }
+    std::vector<int64_t> zero((size_t)ctx->cl.total, 0);
+    zero[0] = FASTP_GPU_ABI_VERSION;
+    zero[1] = ctx->cl.cycles;
+    zero[2] = ctx->dp.isize_max;
+    if ((rc = upload(ctx, (void**)&ctx->d_ctr, zero.data(), zero.size() * 8))) return rc;
+    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_slabs, (size_t)ctx->blocks * ctx->slab_dwords * 4));
+    if (ctx->dp.dup_enabled) {
+        const size_t bytes = (size_t)(ctx->dp.dup_bits >> 3) * ctx->dp.dup_bufnum;
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_bitmap, bytes));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_bitmap, 0, bytes, ctx->stream));
+    }
+    if (ctx->sw.phase_timing) {
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_phase, 16 * sizeof(u64)));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_phase, 0, 16 * sizeof(u64), ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// form 5 contexts: what stays free beside the Stats kernel's waves, and for whom
+static int choose_finish_threads(fastp_gpu_ctx* ctx) {
+#ifndef FQ_HOSTSIM
+    if (!(ctx->split && ctx->st_form == 5)) return 0;
+    int32_t kr[KERNEL_REGS_N];
+    const int rc = fastp_gpu_debug_kernel_regs(ctx, kr, KERNEL_REGS_N);
+    if (rc) return rc;
+    const int waves = ctx->st_threads / 64 / 4, alloc = (kr[1] + 7) & ~7, left = 512 - waves * alloc;
+    // Duplicate's finish is a grid-stride loop over the units: any workgroup size does.  As 1024 lanes (four waves per SIMD) it
+    // never fitted what the Stats kernel leaves, waited for that kernel's workgroups to go and ended the step behind it; the
+    // largest size that fits runs beside it like losers and winners do.  Nothing fits beside a 128-VGPR instantiation: 1024 stays.
+    // Paired contexts only: a single-end unit has half the bases, the Stats kernel ends BEFORE Duplicate's chain does (10 M reads:
+    // 540 us against 40 + 230 + 320), and alone on the chip finish is slower in small workgroups - 234 us against 67, four times
+    // the workgroups and as many adds to one counter (profiles/r08_a_step_tail.txt: the single-end step was 8 - 10 % slower).
+    const int finish_a8 = (kr[13] + 7) & ~7;
+    for (int t = 1024; t >= 256 && ctx->dp.paired; t >>= 1)
+        if (kr[13] > 0 && t <= kr[14] && (t / 256) * finish_a8 <= left) { ctx->finish_threads = t; break; }
+    if (ctx->sw.verbose) {
+        const char* names[4] = {"fq_reduce_kernel", "fq_dup_losers_kernel", "fq_dup_winners_kernel", "fq_dup_finish_kernel"};
+        std::string fits;
+        for (int k = 0; k < 4; k++) {   // a workgroup of the kernel as launched (256 lanes = a wave per SIMD, 1024 = four) in what is left
+            const int a8 = (kr[4 + 3 * k] + 7) & ~7, wg_waves = std::max(1, (k == 3 ? ctx->finish_threads : kr[5 + 3 * k]) / 64 / 4);
+            if (a8 * wg_waves <= left)
+                fits += std::string(fits.empty() ? "" : ", ") + names[k] + " (" + std::to_string(wg_waves) + " x " + std::to_string(a8) + ")";
+        }
+        fprintf(stderr, "fastp_gpu: stats kernel instantiation %d: %d VGPRs (allocated %d), %d waves per SIMD, %d registers per SIMD left; a workgroup fits beside it of: %s; fq_dup_finish_kernel runs as %d lanes\n",
+                ctx->st5_inst, kr[1], alloc, waves, left, fits.empty() ? "none" : fits.c_str(), ctx->finish_threads);
+    }
+#endif
+    return 0;
+}
+
+extern "C" int fastp_gpu_create(const fastp_gpu_params* params, int device, fastp_gpu_ctx** out) {
+    if (!params || !out) return fail(nullptr, FASTP_GPU_E_INVALID, "null argument");
+    *out = nullptr;
+    int ndev = 0;
+    fq::timeline("create: begin");
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(nullptr, FASTP_GPU_E_NO_DEVICE, "no HIP device visible - the engine has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(nullptr, FASTP_GPU_E_NO_DEVICE, "device ordinal out of range");
+    // the one owner until the last line: a failing step returns its code, the message is fastp_gpu_last_error(nullptr)'s
+    std::unique_ptr<fastp_gpu_ctx, void (*)(fastp_gpu_ctx*)> owner(new fastp_gpu_ctx(), fastp_gpu_destroy);
+    fastp_gpu_ctx* ctx = owner.get();
+    ctx->sw = read_switches();
+    ctx->params = *params;
+    ctx->device = device;
+    ctx->exact_all = ctx->sw.exact != 0;   // tests: every unit through the text kernel (fq_text.h)
+    int rc;
+    if ((rc = own_param_strings(ctx)) || (rc = read_params_and_device(ctx)) || (rc = choose_plan(ctx)) || (rc = plan_stats_kernel(ctx)) ||
+        (rc = plan_lane_kernel(ctx)) || (rc = check_kernel_lds(ctx)) || (rc = plan_launch_size(ctx)))
+        return rc;
+    fastp_gpu_counter_layout_for_params(&ctx->params, &ctx->cl);
+    if ((rc = print_geometry(ctx))) return rc;
+    fq::timeline("create: plan chosen (device properties, occupancy queries)");
+    if ((rc = create_streams(ctx)) || (rc = set_kernel_attributes(ctx)) || (rc = upload_tables(ctx))) return rc;
+    fill_arg_templates(ctx);
+    if ((rc = choose_finish_threads(ctx))) return rc;
+    fq::timeline("create: end (tables uploaded, bloom filter cleared)");
+    *out = owner.release();
+    return FASTP_GPU_OK;
+}
+
+// debugging aid (not part of the drop-in surface): cycles spent per phase of the fused kernel,
+// summed over workgroups, when the context was created with FASTP_GPU_PHASE_TIMING=1
+extern "C" int fastp_gpu_debug_phase_cycles(fastp_gpu_ctx* ctx, uint64_t* out16) {
+    if (!ctx || !out16 || !ctx->d_phase) return FASTP_GPU_E_INVALID;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(out16, ctx->d_phase, 16 * sizeof(u64), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemset(ctx->d_phase, 0, 16 * sizeof(u64)));
     return FASTP_GPU_OK;
 }
 
@@ -1808,9 +1901,8 @@ static int launch_front_stats(Launch& l) {
         fs.rec[m] = (const u32*)l.a.res[m];
     }
     const size_t reads = (size_t)l.n * (ctx->dp.paired ? 2 : 1);
-    const size_t lds_bytes = (size_t)(ctx->dp.paired ? 2 : 1) * 34 * (size_t)ctx->cl.cycles * 4;
     const int fgrid = (int)std::max<size_t>(1, std::min<size_t>((size_t)ctx->cus * 4, (reads + 255) / 256));
-    hipLaunchKernelGGL(fq_front_stats_kernel, dim3(fgrid), dim3(256), lds_bytes, l.st, fs);
+    hipLaunchKernelGGL(fq_front_stats_kernel, dim3(fgrid), dim3(256), front_stats_lds_bytes(ctx), l.st, fs);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -1842,9 +1934,8 @@ static int launch_corr_stats(Launch& l) {
     cs.corr_head = lo.corr_head;
     cs.corr_next = lo.corr_next;
     // persistent workgroups: the deltas of a workgroup's reads meet in its LDS tables first (corr_stats_body)
-    const size_t lds_bytes = (size_t)(ctx->dp.paired ? 2 : 1) * (33 * (size_t)ctx->cl.cycles + 128 + KMER_BINS) * 4;
     const int cgrid = (int)std::max<size_t>(1, std::min<size_t>((size_t)ctx->cus * 2, (reads + 1023) / 1024));
-    hipLaunchKernelGGL(fq_corr_stats_kernel, dim3(cgrid), dim3(1024), lds_bytes, l.st, cs);
+    hipLaunchKernelGGL(fq_corr_stats_kernel, dim3(cgrid), dim3(1024), corr_stats_lds_bytes(ctx), l.st, cs);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -2371,8 +2462,7 @@ extern "C" int fastp_gpu_inflate_bgzf(fastp_gpu_ctx* ctx, const uint8_t* comp, i
     if (how == 2 && !wave_fits) return fail(ctx, FASTP_GPU_E_INVALID, "FASTP_GPU_INFLATE=wave: the wave kernel's LDS does not fit this device");
     const bool lane_kernel = how ? how == 1 || !wave_fits : n_blocks > 6144 || !wave_fits;
     if (lane_kernel) {
-        const int lds_bytes = INF_ENTRIES * INF_LANES * 2 + INF_SBUF * INF_LANES * 4;
-        hipLaunchKernelGGL(fq_inflate_kernel, dim3((n_blocks + INF_LANES - 1) / INF_LANES), dim3(INF_LANES), lds_bytes, st, a);
+        hipLaunchKernelGGL(fq_inflate_kernel, dim3((n_blocks + INF_LANES - 1) / INF_LANES), dim3(INF_LANES), inflate_lane_lds_bytes(), st, a);
     } else {
         const int per_cu = std::max(1, ctx->lds_bytes / (int)sizeof(IwLds));
         hipLaunchKernelGGL(fq_inflate_wave_kernel, dim3(std::min(n_blocks, ctx->cus * per_cu)), dim3(64), sizeof(IwLds), st, a);
