@@ -178,6 +178,13 @@ class ParseInfo(C.Structure):
                 ("bad_kind", C.c_int32), ("max_seq_len", C.c_int32), ("n_exotic", C.c_int32), ("reserved", C.c_int32)]
 
 
+class EvalText(C.Structure):
+    """fastp_gpu_eval_text: the reads of one mate with letters outside ACGTN, for the fastp_gpu_eval_*_x calls -
+    fastp_gpu_batch's exotic_* for one mate (exotic_unit: HOST int32, ascending; exotic_text / exotic_off: DEVICE)"""
+    _fields_ = [("n_exotic", C.c_int32), ("exotic_dense", C.c_int32), ("exotic_unit", C.c_void_p),
+                ("exotic_text", C.c_void_p), ("exotic_off", C.c_void_p)]
+
+
 class InflateInfo(C.Structure):
     _fields_ = [("n_blocks", C.c_int32), ("first_bad", C.c_int32), ("consumed", C.c_int64), ("out_bytes", C.c_int64)]
 

@@ -198,10 +198,10 @@ extern "C" __global__ void __launch_bounds__(1024) fq_deflate_scan_kernel(Deflat
     deflate_scan_body(a, (u64*)fq_lds);
 }
 extern "C" __global__ void __launch_bounds__(256) fq_deflate_gather_kernel(DeflateArgs a) { deflate_gather_body(a); }
-extern "C" __global__ void __launch_bounds__(256) fq_eval_kmer_kernel(EvalKmerArgs a) { eval_kmer_body(a); }
-extern "C" __global__ void __launch_bounds__(256) fq_eval_census_kernel(EvalCensusArgs a) { eval_census_body(a); }
+extern "C" __global__ void __launch_bounds__(256) fq_eval_kmer_kernel(EvalKmerArgs a) { eval_kmer_body<false>(a, EvalText{}); }
+extern "C" __global__ void __launch_bounds__(256) fq_eval_census_kernel(EvalCensusArgs a) { eval_census_body<false>(a, EvalText{}); }
 extern "C" __global__ void __launch_bounds__(256) fq_eval_harvest_kernel(EvalCensusArgs a) { eval_harvest_body(a); }
-extern "C" __global__ void __launch_bounds__(256) fq_eval_text_kernel(EvalCensusArgs a) { eval_text_body(a); }
+extern "C" __global__ void __launch_bounds__(256) fq_eval_text_kernel(EvalCensusArgs a) { eval_text_body<false>(a, EvalText{}); }
 extern "C" __global__ void __launch_bounds__(64 * EVAL_MATCH_WAVES) fq_eval_match_kernel(EvalMatchArgs a) {
     extern __shared__ __attribute__((aligned(16))) u32 fq_lds[];
     eval_match_body(a, fq_lds);
@@ -210,10 +210,24 @@ extern "C" __global__ void __launch_bounds__(64) fq_eval_replay_kernel(EvalMatch
     extern __shared__ __attribute__((aligned(16))) u32 fq_lds[];
     eval_replay_body(a, fq_lds);
 }
-extern "C" __global__ void __launch_bounds__(256) fq_eval_seed_gather_kernel(EvalSeedArgs a) { eval_seed_gather_body(a); }
+extern "C" __global__ void __launch_bounds__(256) fq_eval_seed_gather_kernel(EvalSeedArgs a) { eval_seed_gather_body<false>(a, EvalText{}); }
 extern "C" __global__ void __launch_bounds__(1024) fq_eval_seed_walk_kernel(EvalSeedArgs a) {
     extern __shared__ __attribute__((aligned(16))) u32 fq_lds[];
     eval_seed_walk_body(a, fq_lds);
+}
+// the text-aware forms (reads with letters outside ACGTN, fastp_gpu_eval_*_x)
+extern "C" __global__ void __launch_bounds__(256) fq_eval_list_kernel(EvalListArgs a) { eval_list_body(a); }
+extern "C" __global__ void __launch_bounds__(256) fq_eval_kmer_x_kernel(EvalKmerArgs a, EvalText x) { eval_kmer_body<true>(a, x); }
+extern "C" __global__ void __launch_bounds__(256) fq_eval_census_x_kernel(EvalCensusArgs a, EvalText x) { eval_census_body<true>(a, x); }
+extern "C" __global__ void __launch_bounds__(256) fq_eval_text_x_kernel(EvalCensusArgs a, EvalText x) { eval_text_body<true>(a, x); }
+extern "C" __global__ void __launch_bounds__(64 * EVAL_MATCH_WAVES) fq_eval_match_x_kernel(EvalMatchArgs a, EvalText x) {
+    extern __shared__ __attribute__((aligned(16))) u32 fq_lds[];
+    eval_match_x_body(a, x, fq_lds);
+}
+extern "C" __global__ void __launch_bounds__(256) fq_eval_seed_gather_x_kernel(EvalSeedArgs a, EvalText x) { eval_seed_gather_body<true>(a, x); }
+extern "C" __global__ void __launch_bounds__(1024) fq_eval_seed_walk_x_kernel(EvalSeedArgs a, EvalText x) {
+    extern __shared__ __attribute__((aligned(16))) u32 fq_lds[];
+    eval_seed_walk_x_body(a, x, fq_lds);
 }
 extern "C" __global__ void __launch_bounds__(256) fq_fmts_corr_kernel(FmtsArgs f) { fmts_corr_body(f); }
 extern "C" __global__ void __launch_bounds__(256) fq_fmts_len_kernel(FmtsArgs f) {
@@ -387,6 +401,7 @@ struct fastp_gpu_ctx {
     int ovr_launches = 0; int ovr_plan[3] = {0, -1, -1};  // launch_overrep's last LDS plan (fastp_gpu_debug_overrep_plan)
     u8* d_def = nullptr; size_t def_cap = 0;              // deflate scratch: member slots | tokens | sizes | offsets | (levels 5..9) chains
     u8* d_eval = nullptr; size_t eval_cap = 0;            // Evaluator pre-pass: census table | hot list | text
+    u8* d_eval_x = nullptr; size_t eval_x_cap = 0;        // its text-aware calls: an offset per read | the listed reads
     u32* d_ovr_corr = nullptr; size_t ovr_corr_cap = 0;   // correction chains: head[reads] | next[capacity]
     u32* d_parse = nullptr; size_t parse_cap = 0;         // FASTQ parse scratch
     u64* d_fmt = nullptr; size_t fmt_cap = 0;             // FASTQ format scratch
@@ -513,7 +528,7 @@ extern "C" void fastp_gpu_destroy(fastp_gpu_ctx* ctx) {
     void* bufs[] = {ctx->d_ov_limit, ctx->d_lowq, ctx->d_cplx, ctx->d_primes, ctx->d_planes, ctx->d_posum, ctx->d_fasta_words, ctx->d_fasta_len, ctx->d_ctr, ctx->d_slabs,
                     ctx->d_bitmap, ctx->d_dup_pos, ctx->d_table, ctx->d_need, ctx->d_dupflag, ctx->d_stage, ctx->d_phase,
                     ctx->d_ovr_table[0], ctx->d_ovr_table[1], ctx->d_ovr_sym[0], ctx->d_ovr_sym[1], ctx->d_ovr_len[0],
-                    ctx->d_ovr_len[1], ctx->d_post_seen, ctx->d_ovr_work, ctx->d_parse, ctx->d_fmt, ctx->d_prefix, ctx->d_inf, ctx->d_ovr_corr, ctx->d_eval, ctx->d_def, ctx->d_setw, ctx->d_cfilter,
+                    ctx->d_ovr_len[1], ctx->d_post_seen, ctx->d_ovr_work, ctx->d_parse, ctx->d_fmt, ctx->d_prefix, ctx->d_inf, ctx->d_ovr_corr, ctx->d_eval, ctx->d_eval_x, ctx->d_def, ctx->d_setw, ctx->d_cfilter,
                     ctx->d_st_slabs, ctx->d_swin[0], ctx->d_swin[1], ctx->d_ln_slabs,
                     ctx->d_cs_map[0], ctx->d_cs_map[1], ctx->d_cs_blob, ctx->d_cs_items, ctx->d_cs_slots,
                     ctx->d_corr_int, ctx->d_corr_chain, ctx->d_x_unit, ctx->d_x_len, ctx->d_x_skip, ctx->d_al[0], ctx->d_al[1], ctx->d_al[2], ctx->d_al[3], ctx->d_x_text[0], ctx->d_x_text[1], ctx->d_x_off[0], ctx->d_x_off[1]};
@@ -3057,6 +3072,42 @@ static int eval_admit(fastp_gpu_ctx* ctx, const uint16_t* len, int32_t n, int64_
     return 0;
 }
 
+// The listed reads of a text-aware call (fastp_gpu_eval_text): checked, then turned into EvalText's word per read.
+// `on` stays false for NULL or an empty list: the call is the plain one.
+static int eval_check_text(fastp_gpu_ctx* ctx, const fastp_gpu_eval_text* x, int32_t n) {
+    if (!x || x->n_exotic == 0) return FASTP_GPU_OK;
+    if (x->n_exotic < 0 || !x->exotic_unit || !x->exotic_text || !x->exotic_off)
+        return fail(ctx, FASTP_GPU_E_INVALID, "n_exotic > 0 needs exotic_unit, exotic_text and exotic_off");
+    for (int k = 0; k < x->n_exotic; k++)
+        if (x->exotic_unit[k] < 0 || x->exotic_unit[k] >= n || (k && x->exotic_unit[k] <= x->exotic_unit[k - 1]))
+            return fail(ctx, FASTP_GPU_E_INVALID, "exotic_unit must be ascending read indexes below n");
+    return FASTP_GPU_OK;
+}
+static int eval_stage_text(fastp_gpu_ctx* ctx, const fastp_gpu_eval_text* x, int32_t n, EvalText& tx, bool& on) {
+    on = x && x->n_exotic > 0;
+    memset(&tx, 0, sizeof(tx));
+    if (!on) return FASTP_GPU_OK;
+    hipStream_t st = ctx->stream;
+    const size_t b_off = (size_t)n * 4;
+    int rc = ensure(ctx, (void**)&ctx->d_eval_x, &ctx->eval_x_cap, b_off + (size_t)x->n_exotic * 4);
+    if (rc) return rc;
+    EvalListArgs l;
+    memset(&l, 0, sizeof(l));
+    l.rawoff = (u32*)ctx->d_eval_x;
+    l.unit = (const int*)(ctx->d_eval_x + b_off);
+    l.n_exotic = x->n_exotic;
+    l.dense = x->exotic_dense ? 1 : 0;
+    l.off = x->exotic_off;
+    HIP_TRY(ctx, hipMemsetAsync(l.rawoff, 0xFF, b_off, st));
+    HIP_TRY(ctx, hipMemcpyAsync((void*)l.unit, x->exotic_unit, (size_t)x->n_exotic * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));   // the list is the caller's (pageable) memory
+    hipLaunchKernelGGL(fq_eval_list_kernel, dim3((unsigned)((x->n_exotic + 255) / 256)), dim3(256), 0, st, l);
+    HIP_TRY(ctx, hipGetLastError());
+    tx.text = x->exotic_text;
+    tx.rawoff = l.rawoff;
+    return FASTP_GPU_OK;
+}
+
 extern "C" int fastp_gpu_eval_seq_len(fastp_gpu_ctx* ctx, const uint16_t* len, int32_t n, int32_t* seq_len) {
     if (!ctx || !seq_len || n < 0 || (n > 0 && !len)) return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -3069,9 +3120,10 @@ extern "C" int fastp_gpu_eval_seq_len(fastp_gpu_ctx* ctx, const uint16_t* len, i
     return FASTP_GPU_OK;
 }
 
-extern "C" int fastp_gpu_eval_adapter_kmers(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len,
-                                            int32_t n, int32_t trim_tail1, uint32_t* counts, int64_t* records) {
+static int eval_adapter_kmers(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len, int32_t n,
+                              int32_t trim_tail1, uint32_t* counts, int64_t* records, const fastp_gpu_eval_text* x) {
     if (!ctx || !counts || n < 0 || (n > 0 && (!seq || !qual || !len))) return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
+    if (int rc = eval_check_text(ctx, x, n)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const int64_t READ_LIMIT = 256 * 1024, BASE_LIMIT = 151 * READ_LIMIT;   // evaluator.cpp:313-314
@@ -3093,19 +3145,36 @@ extern "C" int fastp_gpu_eval_adapter_kmers(fastp_gpu_ctx* ctx, const uint8_t* s
     a.counts = counts;
     const long long lanes = (long long)a.r.n * a.span;
     if (lanes > 0) {
-        hipLaunchKernelGGL(fq_eval_kmer_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, a);
+        EvalText tx;
+        bool text;
+        rc = eval_stage_text(ctx, x, n, tx, text);
+        if (rc) return rc;
+        const dim3 grid((unsigned)((lanes + 255) / 256));
+        if (text) hipLaunchKernelGGL(fq_eval_kmer_x_kernel, grid, dim3(256), 0, st, a, tx);
+        else hipLaunchKernelGGL(fq_eval_kmer_kernel, grid, dim3(256), 0, st, a);
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return FASTP_GPU_OK;
 }
+extern "C" int fastp_gpu_eval_adapter_kmers(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len,
+                                            int32_t n, int32_t trim_tail1, uint32_t* counts, int64_t* records) {
+    return eval_adapter_kmers(ctx, seq, qual, len, n, trim_tail1, counts, records, nullptr);
+}
+// Evaluator::seq2int (evaluator.cpp:577-626) on the listed reads' own letters: a window with anything but A T C G gives -1
+extern "C" int fastp_gpu_eval_adapter_kmers_x(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len,
+                                              int32_t n, int32_t trim_tail1, uint32_t* counts, int64_t* records,
+                                              const fastp_gpu_eval_text* x) {
+    return eval_adapter_kmers(ctx, seq, qual, len, n, trim_tail1, counts, records, x);
+}
 
-extern "C" int fastp_gpu_eval_overrep(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len, int32_t n,
-                                      int32_t seq_len, char* text, int64_t text_capacity, int64_t* off, int64_t* count,
-                                      int32_t max_seqs, int32_t* n_seqs) {
+static int eval_overrep(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len, int32_t n, int32_t seq_len,
+                        char* text, int64_t text_capacity, int64_t* off, int64_t* count, int32_t max_seqs, int32_t* n_seqs,
+                        const fastp_gpu_eval_text* x) {
     if (!ctx || !n_seqs || !off || n < 0 || max_seqs < 0 || text_capacity < 0 || (n > 0 && (!seq || !qual || !len)) ||
         (max_seqs > 0 && (!text || !count)))
         return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
+    if (int rc = eval_check_text(ctx, x, n)) return rc;
     *n_seqs = 0;
     off[0] = 0;
     if (seq_len < 1) return fail(ctx, FASTP_GPU_E_INVALID, "seq_len (Evaluator::computeSeqLen) must be positive");
@@ -3156,7 +3225,12 @@ extern "C" int fastp_gpu_eval_overrep(fastp_gpu_ctx* ctx, const uint8_t* seq, co
     HIP_TRY(ctx, hipMemsetAsync(base, 0, b_slot + b_count, st));
     HIP_TRY(ctx, hipMemsetAsync(a.n_hot, 0, 16, st));
     const long long lanes = (long long)a.r.n * a.span;
-    hipLaunchKernelGGL(fq_eval_census_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, a);
+    EvalText tx;
+    bool with_text;
+    rc = eval_stage_text(ctx, x, n, tx, with_text);
+    if (rc) return rc;
+    if (with_text) hipLaunchKernelGGL(fq_eval_census_x_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, a, tx);
+    else hipLaunchKernelGGL(fq_eval_census_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, a);
     HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(fq_eval_harvest_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, st, a);
     HIP_TRY(ctx, hipGetLastError());
@@ -3166,7 +3240,9 @@ extern "C" int fastp_gpu_eval_overrep(fastp_gpu_ctx* ctx, const uint8_t* seq, co
     if (n_hot > a.hot_cap) return fail(ctx, FASTP_GPU_E_UNSUPPORTED, "more than 4 Mi overrepresented substrings");
     std::map<std::string, long> hot;   // Options::overRepSeqs (evaluator.cpp:112-137)
     if (n_hot) {
-        hipLaunchKernelGGL(fq_eval_text_kernel, dim3((unsigned)(((size_t)n_hot * 16 + 255) / 256)), dim3(256), 0, st, a);
+        const dim3 grid((unsigned)(((size_t)n_hot * 16 + 255) / 256));
+        if (with_text) hipLaunchKernelGGL(fq_eval_text_x_kernel, grid, dim3(256), 0, st, a, tx);
+        else hipLaunchKernelGGL(fq_eval_text_kernel, grid, dim3(256), 0, st, a);
         HIP_TRY(ctx, hipGetLastError());
         std::vector<u64> hw(n_hot);
         std::vector<u32> hc(n_hot);
@@ -3202,15 +3278,28 @@ extern "C" int fastp_gpu_eval_overrep(fastp_gpu_ctx* ctx, const uint8_t* seq, co
     }
     return FASTP_GPU_OK;
 }
+extern "C" int fastp_gpu_eval_overrep(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len, int32_t n,
+                                      int32_t seq_len, char* text, int64_t text_capacity, int64_t* off, int64_t* count,
+                                      int32_t max_seqs, int32_t* n_seqs) {
+    return eval_overrep(ctx, seq, qual, len, n, seq_len, text, text_capacity, off, count, max_seqs, n_seqs, nullptr);
+}
+// computeOverRepSeq's raw substrings (evaluator.cpp:99-110, :115-160): a byte outside ACGTN equals only the same byte;
+// thresholds, the containment pass and the map's order work on the bytes
+extern "C" int fastp_gpu_eval_overrep_x(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len, int32_t n,
+                                        int32_t seq_len, char* text, int64_t text_capacity, int64_t* off, int64_t* count,
+                                        int32_t max_seqs, int32_t* n_seqs, const fastp_gpu_eval_text* x) {
+    return eval_overrep(ctx, seq, qual, len, n, seq_len, text, text_capacity, off, count, max_seqs, n_seqs, x);
+}
 
 // Evaluator::checkKnownAdapters: the match kernel over every (read, adapter), the replay of the loop's state machine over
 // the matched pairs, the final choice (:291-305) here.  The list is the caller's; it is walked in std::map order.
-extern "C" int fastp_gpu_eval_known_adapters(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len,
-                                             int32_t n, const char* const* adapters, int32_t n_adapters, int32_t* counts,
-                                             int32_t* mismatches, int64_t* checked_reads, int32_t* best) {
+static int eval_known_adapters(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len, int32_t n,
+                               const char* const* adapters, int32_t n_adapters, int32_t* counts, int32_t* mismatches,
+                               int64_t* checked_reads, int32_t* best, const fastp_gpu_eval_text* x) {
     if (!ctx || !checked_reads || !best || n < 0 || n_adapters < 0 || (n > 0 && (!seq || !qual || !len)) ||
         (n_adapters > 0 && (!adapters || !counts || !mismatches)))
         return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
+    if (int rc = eval_check_text(ctx, x, n)) return rc;
     *best = -1;
     *checked_reads = 0;
     if (n_adapters > EVAL_MAX_ADAPTERS) return fail(ctx, FASTP_GPU_E_UNSUPPORTED, "more than 1024 known adapters");
@@ -3272,8 +3361,15 @@ extern "C" int fastp_gpu_eval_known_adapters(fastp_gpu_ctx* ctx, const uint8_t* 
     HIP_TRY(ctx, hipMemcpyAsync(base, words.data(), b_words, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(base + b_words, alen.data(), (size_t)A * 2, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));   // (the staging vectors are pageable)
-    hipLaunchKernelGGL(fq_eval_match_kernel, dim3((unsigned)((a.r.n + EVAL_MATCH_WAVES - 1) / EVAL_MATCH_WAVES)), dim3(64 * EVAL_MATCH_WAVES),
-                       (size_t)EVAL_MATCH_WAVES * (EVAL_MATCH_LDS + a.bit_words * 32) * 4, st, a);
+    EvalText tx;
+    bool with_text;
+    rc = eval_stage_text(ctx, x, n, tx, with_text);
+    if (rc) return rc;
+    const dim3 grid((unsigned)((a.r.n + EVAL_MATCH_WAVES - 1) / EVAL_MATCH_WAVES));
+    const size_t lds = (size_t)EVAL_MATCH_WAVES * (EVAL_MATCH_LDS + a.bit_words * 32) * 4;
+    if (with_text)   // + 512 bytes of a listed read per wavefront
+        hipLaunchKernelGGL(fq_eval_match_x_kernel, grid, dim3(64 * EVAL_MATCH_WAVES), lds + (size_t)EVAL_MATCH_WAVES * 512, st, a, tx);
+    else hipLaunchKernelGGL(fq_eval_match_kernel, grid, dim3(64 * EVAL_MATCH_WAVES), lds, st, a);
     HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(fq_eval_replay_kernel, dim3(1), dim3(64), (size_t)A * 8, st, a);
     HIP_TRY(ctx, hipGetLastError());
@@ -3295,14 +3391,27 @@ extern "C" int fastp_gpu_eval_known_adapters(fastp_gpu_ctx* ctx, const uint8_t* 
     if (top >= 0 && (max_count > checked / 50 || (max_count > checked / 200 && res[2 + A + top] < checked))) *best = order[top];
     return FASTP_GPU_OK;
 }
+extern "C" int fastp_gpu_eval_known_adapters(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len,
+                                             int32_t n, const char* const* adapters, int32_t n_adapters, int32_t* counts,
+                                             int32_t* mismatches, int64_t* checked_reads, int32_t* best) {
+    return eval_known_adapters(ctx, seq, qual, len, n, adapters, n_adapters, counts, mismatches, checked_reads, best, nullptr);
+}
+// checkKnownAdapters' raw != (evaluator.cpp:266-287): a byte outside ACGTN is a mismatch inside the cmplen / 16 allowance
+extern "C" int fastp_gpu_eval_known_adapters_x(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len,
+                                               int32_t n, const char* const* adapters, int32_t n_adapters, int32_t* counts,
+                                               int32_t* mismatches, int64_t* checked_reads, int32_t* best,
+                                               const fastp_gpu_eval_text* x) {
+    return eval_known_adapters(ctx, seq, qual, len, n, adapters, n_adapters, counts, mismatches, checked_reads, best, x);
+}
 
 // Evaluator::getAdapterWithSeed's two scans and the two NucleotideTree::getDominantPath walks for one seed
-extern "C" int fastp_gpu_eval_adapter_seed(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len,
-                                           int32_t n, int32_t trim_tail1, uint32_t seed, char* forward, int32_t* forward_len,
-                                           char* backward, int32_t* backward_len, int32_t* reached_leaf, int64_t* hits) {
+static int eval_adapter_seed(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len, int32_t n,
+                             int32_t trim_tail1, uint32_t seed, char* forward, int32_t* forward_len, char* backward,
+                             int32_t* backward_len, int32_t* reached_leaf, int64_t* hits, const fastp_gpu_eval_text* x) {
     if (!ctx || !forward || !forward_len || !backward || !backward_len || !reached_leaf || !hits || n < 0 || seed >= (1u << 20) ||
         (n > 0 && (!seq || !qual || !len)))
         return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
+    if (int rc = eval_check_text(ctx, x, n)) return rc;
     *forward_len = *backward_len = 0;
     *reached_leaf = 1;
     *hits = 0;
@@ -3325,6 +3434,10 @@ extern "C" int fastp_gpu_eval_adapter_seed(fastp_gpu_ctx* ctx, const uint8_t* se
     a.seed = seed;
     const long long lanes = (long long)a.r.n * a.span;
     if (lanes == 0) return FASTP_GPU_OK;
+    EvalText tx;
+    bool with_text;
+    rc = eval_stage_text(ctx, x, n, tx, with_text);
+    if (rc) return rc;
     // count the hits, size the list by the count, list them
     const size_t b_head = 8 + 16 + 1024;   // n_hits | path_len[2], reached_leaf | the two paths
     u64 nh = 0;
@@ -3338,7 +3451,8 @@ extern "C" int fastp_gpu_eval_adapter_seed(fastp_gpu_ctx* ctx, const uint8_t* se
         a.hits = pass ? (u32*)(base + b_head) : nullptr;
         a.cap = nh;
         HIP_TRY(ctx, hipMemsetAsync(base, 0, 24, st));
-        hipLaunchKernelGGL(fq_eval_seed_gather_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, a);
+        if (with_text) hipLaunchKernelGGL(fq_eval_seed_gather_x_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, a, tx);
+        else hipLaunchKernelGGL(fq_eval_seed_gather_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, a);
         HIP_TRY(ctx, hipGetLastError());
         if (pass) break;
         HIP_TRY(ctx, hipMemcpyAsync(&nh, a.n_hits, 8, hipMemcpyDeviceToHost, st));
@@ -3348,7 +3462,8 @@ extern "C" int fastp_gpu_eval_adapter_seed(fastp_gpu_ctx* ctx, const uint8_t* se
     }
     const int one = 1;
     HIP_TRY(ctx, hipMemcpyAsync(a.path_len + 2, &one, 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(fq_eval_seed_walk_kernel, dim3(2), dim3(1024), 16, st, a);
+    if (with_text) hipLaunchKernelGGL(fq_eval_seed_walk_x_kernel, dim3(2), dim3(1024), 64, st, a, tx);   // 8 bins | their creators
+    else hipLaunchKernelGGL(fq_eval_seed_walk_kernel, dim3(2), dim3(1024), 16, st, a);
     HIP_TRY(ctx, hipGetLastError());
     u8 out[16 + 1024];
     HIP_TRY(ctx, hipMemcpyAsync(out, a.path_len, sizeof(out), hipMemcpyDeviceToHost, st));
@@ -3361,6 +3476,21 @@ extern "C" int fastp_gpu_eval_adapter_seed(fastp_gpu_ctx* ctx, const uint8_t* se
     memcpy(forward, out + 16, (size_t)head[0]);
     memcpy(backward, out + 16 + 512, (size_t)head[1]);
     return FASTP_GPU_OK;
+}
+extern "C" int fastp_gpu_eval_adapter_seed(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len,
+                                           int32_t n, int32_t trim_tail1, uint32_t seed, char* forward, int32_t* forward_len,
+                                           char* backward, int32_t* backward_len, int32_t* reached_leaf, int64_t* hits) {
+    return eval_adapter_seed(ctx, seq, qual, len, n, trim_tail1, seed, forward, forward_len, backward, backward_len, reached_leaf,
+                             hits, nullptr);
+}
+// the hit search by seq2int (evaluator.cpp:577-626) and NucleotideTree on raw bytes (nucleotidetree.cpp:42-88): eight
+// children by byte & 7, only 'N' cuts, a node prints its creator's byte
+extern "C" int fastp_gpu_eval_adapter_seed_x(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len,
+                                             int32_t n, int32_t trim_tail1, uint32_t seed, char* forward, int32_t* forward_len,
+                                             char* backward, int32_t* backward_len, int32_t* reached_leaf, int64_t* hits,
+                                             const fastp_gpu_eval_text* x) {
+    return eval_adapter_seed(ctx, seq, qual, len, n, trim_tail1, seed, forward, forward_len, backward, backward_len, reached_leaf,
+                             hits, x);
 }
 
 // ---- output text -> BGZF-framed gzip members (fq_deflate.h) ------------------------------------------------

@@ -7,6 +7,9 @@
 //   * the scans and tree walks of getAdapterWithSeed (evaluator.cpp:485-520) for one seed of the histogram.
 // All read the packed rows a batch already holds in HBM (2-bit bases + the N flag in the quality byte).  What the Evaluator
 // decides from the numbers stays on the host.
+// A read with a letter outside ACGTN (soft-masked lower case, IUPAC codes, '.') is stored there with code 0 for that letter,
+// so the text-aware forms (<true>, *_x_body; the fastp_gpu_eval_*_x entry points) take the bytes of the reads the caller
+// lists from the FASTQ text instead - EvalText below has what the reference does with such a byte in each loop.
 #pragma once
 #include "fq_intrin.h"
 #include "fq_types.h"
@@ -20,6 +23,52 @@ struct EvalReads {
     int n;               // reads the limits of the reference loop admit (computed by the host from `len`)
     int seq_stride, qual_stride;
 };
+
+FQ_DEV u32 eval_base(const u8* s, const u8* q, int j) {   // 0..3 = A T C G, 4 = N
+    return (q[j] & 0x80u) ? 4u : (u32)((s[j >> 2] >> (2 * (j & 3))) & 3u);
+}
+
+// ---- reads with letters outside ACGTN ------------------------------------------------------------------------
+// The listed reads' symbols come from the text, every other read's from its packed row.  What a byte b outside ACGTN does:
+//   seq2int (evaluator.cpp:577-626), histogram and hit search: a window holding anything but A T C G gives -1 - b acts as N
+//   checkKnownAdapters (:266-287): a raw != against the adapter's letter - a mismatch inside the cmplen / 16 allowance
+//   NucleotideTree::addSeq (nucleotidetree.cpp:42-55): only the byte 'N' cuts; b descends into child b & 7 (a / A share
+//     bin 1, n goes to bin 6 and goes on), and a node prints the byte of the sequence that created it (reads, then
+//     positions, ascending); getDominantPath (:57-88) sums and tests all eight children
+//   computeOverRepSeq (:99-160): raw substrings in a std::map - b equals only the same byte
+// rawoff is built once per call from the ascending list (eval_list_body): a word per read, no search per position.
+enum : u32 { EVAL_UNLISTED = 0xFFFFFFFFu };
+struct EvalText {
+    const u8* text;
+    const u32* rawoff;   // [n] byte offset of the read's sequence in text, EVAL_UNLISTED: the packed row is the read
+};
+struct EvalListArgs {
+    const int* unit;     // [n_exotic] ascending read indexes
+    int n_exotic, dense;
+    const u32* off;      // dense: the parser's line_off table ([4 * read + 1]); else an offset per listed read
+    u32* rawoff;         // [n], preset to EVAL_UNLISTED
+};
+FQ_DEV void eval_list_body(const EvalListArgs& a) {
+    const int k = block_id() * block_threads() + thread_id();
+    if (k >= a.n_exotic) return;
+    const int u = a.unit[k];
+    a.rawoff[u] = a.dense ? a.off[4 * (size_t)u + 1] : a.off[k];
+}
+FQ_DEV const u8* eval_raw(const EvalText& x, int rd) {   // the listed read's bytes, or null
+    const u32 o = x.rawoff[rd];
+    return o == EVAL_UNLISTED ? nullptr : x.text + o;
+}
+FQ_DEV u32 eval_byte(const u8* raw, const u8* s, const u8* q, int j) { return raw ? (u32)raw[j] : (u32)"ATCGN"[eval_base(s, q, j)]; }
+// the accessor: the raw byte of read rd at position j
+FQ_DEV u32 eval_byte(const EvalReads& r, const EvalText& x, int rd, int j) {
+    return eval_byte(eval_raw(x, rd), r.seq + (size_t)rd * r.seq_stride, r.qual + (size_t)rd * r.qual_stride, j);
+}
+// a census symbol: the packed form compares codes (0..4), the text-aware form bytes - of listed and unlisted reads alike,
+// so an all-ACGTN window hashes and compares the same whichever kind of read it came from
+template <bool X> FQ_DEV u32 eval_sym(const u8* raw, const u8* s, const u8* q, int j) {
+    if constexpr (X) return eval_byte(raw, s, q, j);
+    else return eval_base(s, q, j);
+}
 
 // ---- ten-mer histogram --------------------------------------------------------------------------------------
 // Evaluator::seq2int (evaluator.cpp:573-625) is a pure function of the window: the rolling update and the
@@ -38,23 +87,42 @@ FQ_DEV u32 eval_reverse_pairs20(u32 v) {   // 10 two-bit groups, first group to 
     return x >> 12;
 }
 
-FQ_DEV void eval_kmer_body(const EvalKmerArgs& a) {
+// Evaluator::seq2int for the window at `pos` of read rd: the key, or -1.  A listed read's window is read letter by letter
+// (anything but A T C G: -1); an unlisted read's packed row holds it exactly.
+template <bool X> FQ_DEV int eval_window_key(const EvalReads& r, const EvalText& x, int rd, int pos) {
+    if constexpr (X) {
+        const u8* raw = eval_raw(x, rd);
+        if (raw) {
+            u32 key = 0;
+            for (int k = 0; k < 10; k++) {
+                const u8 b = raw[pos + k];
+                const u32 c = b == 'A' ? 0u : b == 'T' ? 1u : b == 'C' ? 2u : b == 'G' ? 3u : 4u;
+                if (c > 3u) return -1;
+                key = (key << 2) | c;
+            }
+            return (int)key;
+        }
+    }
+    const u8* s = r.seq + (size_t)rd * r.seq_stride;
+    const u8* q = r.qual + (size_t)rd * r.qual_stride;
+    u32 nflag = 0;
+    for (int k = 0; k < 10; k++) nflag |= q[pos + k];
+    if (nflag & 0x80u) return -1;   // an N in the window
+    // 20 bits starting at base `pos`: bytes pos/4 .. (pos + 9)/4 hold them (3 or 4 bytes)
+    const int b = pos >> 2, nb = ((pos + 9) >> 2) - b;
+    u32 w = 0;
+    for (int k = 0; k <= nb; k++) w |= (u32)s[b + k] << (8 * k);
+    return (int)eval_reverse_pairs20((w >> (2 * (pos & 3))) & 0xFFFFFu);
+}
+
+template <bool X> FQ_DEV void eval_kmer_body(const EvalKmerArgs& a, const EvalText& x) {
     const long long t = (long long)block_id() * block_threads() + thread_id();
     const int rd = (int)(t / a.span), pos = 20 + (int)(t % a.span);
     if (rd >= a.r.n) return;
     const int rlen = a.r.len[rd];
     if (pos > rlen - 10 - a.shift_tail) return;
-    const u8* s = a.r.seq + (size_t)rd * a.r.seq_stride;
-    const u8* q = a.r.qual + (size_t)rd * a.r.qual_stride;
-    u32 nflag = 0;
-    for (int k = 0; k < 10; k++) nflag |= q[pos + k];
-    if (nflag & 0x80u) return;   // an N in the window
-    // 20 bits starting at base `pos`: bytes pos/4 .. (pos + 9)/4 hold them (3 or 4 bytes)
-    const int b = pos >> 2, nb = ((pos + 9) >> 2) - b;
-    u32 w = 0;
-    for (int k = 0; k <= nb; k++) w |= (u32)s[b + k] << (8 * k);
-    const u32 key = eval_reverse_pairs20((w >> (2 * (pos & 3))) & 0xFFFFFu);
-    if (key != 0u) g_atomic_add_u32(&a.counts[key], 1u);          // "set AAAAAAAAAA = 0" (evaluator.cpp:401-402)
+    const int key = eval_window_key<X>(a.r, x, rd, pos);
+    if (key > 0) g_atomic_add_u32(&a.counts[key], 1u);            // "set AAAAAAAAAA = 0" (evaluator.cpp:401-402)
 }
 
 // ---- substring census ---------------------------------------------------------------------------------------
@@ -80,17 +148,14 @@ struct EvalCensusArgs {
     u8* text;                  // [hot_cap * 152] a row of characters per hot substring
 };
 
-FQ_DEV u32 eval_base(const u8* s, const u8* q, int j) {   // 0..3 = A T C G, 4 = N
-    return (q[j] & 0x80u) ? 4u : (u32)((s[j >> 2] >> (2 * (j & 3))) & 3u);
-}
-
-FQ_DEV void eval_census_body(const EvalCensusArgs& a) {
+template <bool X> FQ_DEV void eval_census_body(const EvalCensusArgs& a, const EvalText& x) {
     const long long t = (long long)block_id() * block_threads() + thread_id();
     const int rd = (int)(t / a.span), pos = (int)(t % a.span);
     if (rd >= a.r.n) return;
     const int rlen = a.r.len[rd];
     const u8* s = a.r.seq + (size_t)rd * a.r.seq_stride;
     const u8* q = a.r.qual + (size_t)rd * a.r.qual_stride;
+    const u8* raw = X ? eval_raw(x, rd) : nullptr;
     u64 h = 0x9E3779B97F4A7C15ull;
     int done = 0;
     // the steps grow (the last one may be smaller than the others: hash restarted then)
@@ -98,7 +163,7 @@ FQ_DEV void eval_census_body(const EvalCensusArgs& a) {
         const int step = a.step[si];
         if (step <= 0 || pos >= rlen - step) continue;   // for(i = 0; i < rlen - step; i++)
         if (step < done) { h = 0x9E3779B97F4A7C15ull; done = 0; }
-        for (; done < step; done++) h = (h ^ (u64)(eval_base(s, q, pos + done) + 1u)) * 0x100000001B3ull;
+        for (; done < step; done++) h = (h ^ (u64)(eval_sym<X>(raw, s, q, pos + done) + 1u)) * 0x100000001B3ull;
         u64 hs = (h ^ (u64)step) * 0xD6E8FEB86659FD93ull;
         hs ^= hs >> 32;
         const u64 mine = ((u64)(rd + 1) << 40) | ((u64)pos << 24) | ((u64)si << 21) | (hs & 0x1FFFFFull);
@@ -120,8 +185,9 @@ FQ_DEV void eval_census_body(const EvalCensusArgs& a) {
                 if (same && !(rd2 == rd && pos2 == pos)) {
                     const u8* s2 = a.r.seq + (size_t)rd2 * a.r.seq_stride;
                     const u8* q2 = a.r.qual + (size_t)rd2 * a.r.qual_stride;
+                    const u8* raw2 = X ? eval_raw(x, rd2) : nullptr;
                     for (int k = 0; k < step; k++)
-                        if (eval_base(s, q, pos + k) != eval_base(s2, q2, pos2 + k)) {
+                        if (eval_sym<X>(raw, s, q, pos + k) != eval_sym<X>(raw2, s2, q2, pos2 + k)) {
                             same = false;
                             break;
                         }
@@ -160,7 +226,7 @@ FQ_DEV void eval_harvest_body(const EvalCensusArgs& a) {
     }
 }
 
-FQ_DEV void eval_text_body(const EvalCensusArgs& a) {
+template <bool X> FQ_DEV void eval_text_body(const EvalCensusArgs& a, const EvalText& x) {
     // 16 lanes per hot substring
     const u32 t = (u32)block_id() * (u32)block_threads() + (u32)thread_id();
     const u32 k = t >> 4, gl = t & 15u;
@@ -171,7 +237,8 @@ FQ_DEV void eval_text_body(const EvalCensusArgs& a) {
     const u8* s = a.r.seq + (size_t)rd * a.r.seq_stride;
     const u8* q = a.r.qual + (size_t)rd * a.r.qual_stride;
     u8* o = a.text + (size_t)k * 152;
-    for (int j = (int)gl; j < step; j += 16) o[j] = (u8)"ATCGN"[eval_base(s, q, pos + j)];
+    const u8* raw = X ? eval_raw(x, rd) : nullptr;
+    for (int j = (int)gl; j < step; j += 16) o[j] = (u8)eval_byte(raw, s, q, pos + j);
 }
 
 // ---- known-adapter check (Evaluator::checkKnownAdapters, evaluator.cpp:220-306) -----------------------------
@@ -292,6 +359,55 @@ FQ_DEV void eval_match_body(const EvalMatchArgs& a, u32* lds) {
     }
 }
 
+// The text-aware form.  An unlisted read's packed row is exact, so its wavefront runs the body above; a listed read's
+// bytes are staged in LDS behind the packed stages of all wavefronts (128 dwords each: 512 bytes) and every lane runs
+// the reference's inner loop (:269-279) on them as it is written: a raw != against the adapter's letter, left once the
+// allowance is exceeded.  `first` is the wavefront's own of the packed layout, and the results have the same form.
+FQ_DEV void eval_match_x_body(const EvalMatchArgs& a, const EvalText& x, u32* lds) {
+    const int lane = lane_id(), rd = block_id() * EVAL_MATCH_WAVES + wave_id();
+    if (rd >= a.r.n) return;
+    const u8* raw = eval_raw(x, rd);
+    if (!raw) {
+        eval_match_body(a, lds);
+        return;
+    }
+    u32* first = lds + wave_id() * (EVAL_MATCH_LDS + a.bit_words * 32) + EVAL_MATCH_LDS;
+    u8* rb = (u8*)(lds + EVAL_MATCH_WAVES * (EVAL_MATCH_LDS + a.bit_words * 32) + wave_id() * 128);
+    const int rlen = a.r.len[rd] < 512 ? a.r.len[rd] : 512;
+    for (int i = lane; i < rlen; i += 64) rb[i] = raw[i];
+    for (int k = lane; k < a.bit_words * 32; k += 64) first[k] = 0xFFFFFFFFu;
+    wave_sync();
+    const int npos = rlen - 8;
+    u32* bits = a.bits + (size_t)rd * a.bit_words;
+    if (npos <= 0) {
+        if (lane < a.bit_words) bits[lane] = 0u;
+        return;
+    }
+    for (int pos = lane; pos < npos; pos += 64)
+        for (int ad = 0; ad < a.n_adapters; ad++) {
+            const int alen = (int)a.alen[ad];
+            if (alen >= rlen) continue;          // :260
+            const u64* aw = a.words + (size_t)ad * a.ad_words;
+            const int cmplen = rlen - pos < alen ? rlen - pos : alen, allowed = cmplen >> 4;
+            int mism = 0;
+            u64 w = 0;
+            for (int i = 0; i < cmplen && mism <= allowed; i++) {
+                if ((i & 31) == 0) w = aw[i >> 5];
+                mism += (u8)"ATCG"[(w >> (2 * (i & 31))) & 3u] != rb[pos + i];
+            }
+            if (mism <= allowed) lds_min_u32(&first[ad], ((u32)pos << 8) | (u32)mism);   // the smallest position wins
+        }
+    wave_sync();
+    if (lane < a.bit_words) {
+        u32 dn = 0u;
+        for (int j = 0; j < 32; j++) dn |= (u32)(first[lane * 32 + j] != 0xFFFFFFFFu) << j;
+        bits[lane] = dn;
+        u8* mm = a.mm + (size_t)rd * a.n_adapters;
+        for (int ad = lane * 32; ad < lane * 32 + 32 && ad < a.n_adapters; ad++)
+            if (first[ad] != 0xFFFFFFFFu) mm[ad] = (u8)first[ad];
+    }
+}
+
 // One wavefront.  Only matched pairs change the loop's state, so reads are taken 64 at a time (a lane each) and lane 0
 // walks the set bits of the ones that matched something.  LDS: counts | mismatches.
 // The exits: `checkedReads > 100000` is read index 100000; `checkedBases > 100000000` cannot bind before it while a
@@ -372,21 +488,13 @@ struct EvalSeedArgs {
     int* path_len;           // [2], then [2] = 1 unless a walk ended without a dominant base
 };
 
-FQ_DEV void eval_seed_gather_body(const EvalSeedArgs& a) {
+template <bool X> FQ_DEV void eval_seed_gather_body(const EvalSeedArgs& a, const EvalText& x) {
     const long long t = (long long)block_id() * block_threads() + thread_id();
     const int rd = (int)(t / a.span), pos = 20 + (int)(t % a.span);   // span <= 480: pos < MAX_SEARCH_LENGTH
     if (rd >= a.r.n) return;
     const int rlen = a.r.len[rd];
     if (pos > rlen - 10 - a.shift_tail) return;
-    const u8* s = a.r.seq + (size_t)rd * a.r.seq_stride;
-    const u8* q = a.r.qual + (size_t)rd * a.r.qual_stride;
-    u32 nflag = 0;
-    for (int k = 0; k < 10; k++) nflag |= q[pos + k];
-    if (nflag & 0x80u) return;
-    const int b = pos >> 2, nb = ((pos + 9) >> 2) - b;
-    u32 w = 0;
-    for (int k = 0; k <= nb; k++) w |= (u32)s[b + k] << (8 * k);
-    if (eval_reverse_pairs20((w >> (2 * (pos & 3))) & 0xFFFFFu) != a.seed) return;
+    if (eval_window_key<X>(a.r, x, rd, pos) != (int)a.seed) return;
     const u64 k = __hip_atomic_fetch_add(a.n_hits, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (a.hits && k < a.cap) a.hits[k] = ((u32)rd << 9) | (u32)pos;
 }
@@ -447,6 +555,86 @@ FQ_DEV void eval_seed_walk_body(const EvalSeedArgs& a, u32* lds) {
         }
         last = (u32)pick;
         if (tid == 0) path[depth] = (u8)"ATCG"[pick];
+    }
+    if (tid == 0) {
+        a.path_len[dir] = depth;
+        if (!leaf) g_atomic_exch_u32((u32*)&a.path_len[2], 0u);
+    }
+}
+
+// The text-aware walk: the tree as nucleotidetree.cpp builds it from raw bytes.  Eight bins by byte & 7, only the byte 'N'
+// ends a sequence (addSeq :45-47), and the character a node prints is the byte of the sequence that created it (:48-51) -
+// the lowest (read, pos) among the hits that reach it, which is the smallest hit word.  LDS: 8 counts | 8 smallest words.
+// the byte depth d of a hit's sequence holds, 256: the sequence has ended (its end, or an 'N')
+FQ_DEV u32 eval_seed_byte(const EvalSeedArgs& a, const EvalText& x, u32 hit, int dir, int d) {
+    const int rd = (int)((hit >> 9) & 0x1FFFFFu), pos = (int)(hit & 511u);
+    int j;
+    if (dir == 0) {
+        j = pos + 10 + d;
+        if (j >= (int)a.r.len[rd] - a.shift_tail) return 256u;
+    } else {
+        j = pos - 1 - d;
+        if (j < 0) return 256u;
+    }
+    const u32 b = eval_byte(a.r, x, rd, j);
+    return b == (u32)'N' ? 256u : b;
+}
+
+FQ_DEV void eval_seed_walk_x_body(const EvalSeedArgs& a, const EvalText& x, u32* lds) {
+    const int dir = block_id(), tid = thread_id(), T = block_threads();
+    const u32 dead = dir == 0 ? 0x80000000u : 0x40000000u;
+    const u64 nh = *a.n_hits < a.cap ? *a.n_hits : a.cap;
+    u8* path = a.path + 512 * dir;
+    int depth = 0;
+    u32 last = 0;
+    bool leaf = true;
+    for (; depth < 512; depth++) {
+        if (tid < 16) lds[tid] = tid < 8 ? 0u : 0xFFFFFFFFu;
+        block_sync();
+        u32 c[8], lo[8];
+#pragma unroll
+        for (int b = 0; b < 8; b++) { c[b] = 0u; lo[b] = 0xFFFFFFFFu; }
+        for (u64 k = (u64)tid; k < nh; k += (u64)T) {
+            const u32 h = __hip_atomic_load(&a.hits[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (h & dead) continue;
+            // (a live hit's byte at depth - 1 is no 'N' and lies inside its sequence: it would have died there)
+            u32 b = 256u;
+            if (depth == 0 || (eval_seed_byte(a, x, h, dir, depth - 1) & 7u) == last) b = eval_seed_byte(a, x, h, dir, depth);
+            if (b > 255u) {
+                g_atomic_or_u32(&a.hits[k], dead);   // (the other direction's workgroup owns the other bit of the word)
+                continue;
+            }
+            const u32 word = h & 0x3FFFFFFFu;
+#pragma unroll
+            for (u32 e = 0; e < 8u; e++) {
+                const bool in = (b & 7u) == e;
+                c[e] += in;
+                lo[e] = in && word < lo[e] ? word : lo[e];
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < 8; b++)
+            if (c[b]) {
+                lds_add_u32(&lds[b], c[b]);
+                lds_min_u32(&lds[8 + b], lo[b]);
+            }
+        block_sync();
+        u32 n[8], total = 0;
+#pragma unroll
+        for (int b = 0; b < 8; b++) { n[b] = lds[b]; total += n[b]; }
+        int pick = -1;   // children[0..7] in order; at most one can hold 95 %
+#pragma unroll
+        for (int b = 0; b < 8; b++)
+            if (pick < 0 && n[b] && total >= 50u && (double)n[b] / (double)total >= 0.95) pick = b;
+        const u32 creator = pick >= 0 ? lds[8 + pick] : 0u;
+        block_sync();
+        if (total < 50u) break;                      // NUM_THRESHOLD
+        if (pick < 0) {
+            leaf = false;
+            break;
+        }
+        last = (u32)pick;
+        if (tid == 0) path[depth] = (u8)eval_seed_byte(a, x, creator, dir, depth);
     }
     if (tid == 0) {
         a.path_len[dir] = depth;

@@ -17,7 +17,7 @@ _LIBS: dict[str, C.CDLL] = {}
 EXPORTS = [
     "fastp_gpu_default_params", "fastp_gpu_seq_stride", "fastp_gpu_qual_stride", "fastp_gpu_cycles_for",
     "fastp_gpu_counter_layout_for", "fastp_gpu_counter_layout_for_params", "fastp_gpu_create", "fastp_gpu_destroy", "fastp_gpu_last_error",
-    "fastp_gpu_pack_reads", "fastp_gpu_pack_reads_x", "fastp_gpu_bgzf_index", "fastp_gpu_inflate_bgzf", "fastp_gpu_parse_fastq", "fastp_gpu_parse_exotic", "fastp_gpu_phred64_to_33", "fastp_gpu_host_writes_overlapped", "fastp_gpu_format_fastq", "fastp_gpu_format_streams", "fastp_gpu_format_all_streams", "fastp_gpu_deflate_bgzf", "fastp_gpu_deflate_bgzf_level", "fastp_gpu_adapter_census", "fastp_gpu_adapter_census_size", "fastp_gpu_adapter_census_read", "fastp_gpu_adapter_census_load", "fastp_gpu_device_alloc", "fastp_gpu_device_free", "fastp_gpu_device_upload", "fastp_gpu_device_download", "fastp_gpu_eval_seq_len", "fastp_gpu_eval_adapter_kmers", "fastp_gpu_eval_overrep", "fastp_gpu_eval_known_adapters", "fastp_gpu_eval_adapter_seed", "fastp_gpu_submit_host", "fastp_gpu_submit_device", "fastp_gpu_synchronize",
+    "fastp_gpu_pack_reads", "fastp_gpu_pack_reads_x", "fastp_gpu_bgzf_index", "fastp_gpu_inflate_bgzf", "fastp_gpu_parse_fastq", "fastp_gpu_parse_exotic", "fastp_gpu_phred64_to_33", "fastp_gpu_host_writes_overlapped", "fastp_gpu_format_fastq", "fastp_gpu_format_streams", "fastp_gpu_format_all_streams", "fastp_gpu_deflate_bgzf", "fastp_gpu_deflate_bgzf_level", "fastp_gpu_adapter_census", "fastp_gpu_adapter_census_size", "fastp_gpu_adapter_census_read", "fastp_gpu_adapter_census_load", "fastp_gpu_device_alloc", "fastp_gpu_device_free", "fastp_gpu_device_upload", "fastp_gpu_device_download", "fastp_gpu_eval_seq_len", "fastp_gpu_eval_adapter_kmers", "fastp_gpu_eval_overrep", "fastp_gpu_eval_known_adapters", "fastp_gpu_eval_adapter_seed", "fastp_gpu_eval_adapter_kmers_x", "fastp_gpu_eval_overrep_x", "fastp_gpu_eval_known_adapters_x", "fastp_gpu_eval_adapter_seed_x", "fastp_gpu_submit_host", "fastp_gpu_submit_device", "fastp_gpu_synchronize",
     "fastp_gpu_counters_device", "fastp_gpu_counters", "fastp_gpu_kernel_time",
     "fastp_gpu_counters_export", "fastp_gpu_counters_import",
     "fastp_gpu_dup_scan_bytes", "fastp_gpu_submit_pass1_device", "fastp_gpu_dup_bitmap_bytes", "fastp_gpu_dup_bitmap_export",
@@ -437,27 +437,54 @@ class GpuEngine:
         self._check(fn(self.h, len_ptr, n, C.byref(out)))
         return int(out.value)
 
-    def eval_adapter_kmers(self, seq_ptr, qual_ptr, len_ptr, n, trim_tail1, counts_ptr):
-        """4^10 ten-mer histogram into DEVICE uint32[1 << 20] at counts_ptr; returns the records used"""
-        fn = self.lib.fastp_gpu_eval_adapter_kmers
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
-                       C.POINTER(C.c_int64)]
-        rec = C.c_int64(0)
-        self._check(fn(self.h, seq_ptr, qual_ptr, len_ptr, n, trim_tail1, counts_ptr, C.byref(rec)))
-        return int(rec.value)
+    # `exotic` (every call below): None, or (units, text_ptr, off_ptr, dense) naming the reads with letters outside ACGTN -
+    # ascending int32 read indexes (HOST), the DEVICE text that holds their sequence bytes, the DEVICE offsets (dense: the
+    # parser's line_off table) - which sends the call through its fastp_gpu_eval_*_x form (abi.EvalText); units None: that
+    # form with a NULL list
+    @staticmethod
+    def _eval_text(exotic):
+        """-> (abi.EvalText or None, the object that keeps its host list alive)"""
+        if exotic is None:
+            return None, None
+        units, text_ptr, off_ptr, dense = exotic
+        if units is None:             # the _x form with a NULL list: the plain call by another name
+            return None, None
+        units = np.ascontiguousarray(units, dtype=np.int32)
+        x = abi.EvalText(len(units), int(bool(dense)), units.ctypes.data if len(units) else None, text_ptr, off_ptr)
+        return x, units
 
-    def eval_overrep(self, seq_ptr, qual_ptr, len_ptr, n, seq_len, max_seqs=1 << 16, text_capacity=1 << 22, check=True):
-        """Evaluator::computeOverRepSeq: returns (rc, [(sequence bytes, count)] in std::map order)"""
-        fn = self.lib.fastp_gpu_eval_overrep
+    def _eval_fn(self, name, argtypes, exotic):
+        """the plain entry point, or with `exotic` its _x form: (function, trailing arguments, keep-alive)"""
+        x, keep = self._eval_text(exotic)
+        fn = getattr(self.lib, name + ("_x" if exotic is not None else ""))
         fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_char_p, C.c_int64,
-                       C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)]
+        fn.argtypes = argtypes + ([C.POINTER(abi.EvalText)] if exotic is not None else [])
+        tail = [] if exotic is None else [C.byref(x) if x is not None else None]
+        return fn, tail, (x, keep)
+
+    def eval_adapter_kmers(self, seq_ptr, qual_ptr, len_ptr, n, trim_tail1, counts_ptr, exotic=None, check=True):
+        """4^10 ten-mer histogram into DEVICE uint32[1 << 20] at counts_ptr; returns the records used"""
+        fn, tail, keep = self._eval_fn("fastp_gpu_eval_adapter_kmers",
+                                       [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                        C.POINTER(C.c_int64)], exotic)
+        rec = C.c_int64(0)
+        rc = fn(self.h, seq_ptr, qual_ptr, len_ptr, n, trim_tail1, counts_ptr, C.byref(rec), *tail)
+        if check:
+            self._check(rc)
+            return int(rec.value)
+        return rc, int(rec.value)
+
+    def eval_overrep(self, seq_ptr, qual_ptr, len_ptr, n, seq_len, max_seqs=1 << 16, text_capacity=1 << 22, check=True,
+                     exotic=None):
+        """Evaluator::computeOverRepSeq: returns (rc, [(sequence bytes, count)] in std::map order)"""
+        fn, tail, keep = self._eval_fn("fastp_gpu_eval_overrep",
+                                       [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_char_p, C.c_int64,
+                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)], exotic)
         text = C.create_string_buffer(max(1, text_capacity))
         off = (C.c_int64 * (max_seqs + 1))()
         cnt = (C.c_int64 * max(1, max_seqs))()
         ns = C.c_int32(0)
-        rc = fn(self.h, seq_ptr, qual_ptr, len_ptr, n, seq_len, text, text_capacity, off, cnt, max_seqs, C.byref(ns))
+        rc = fn(self.h, seq_ptr, qual_ptr, len_ptr, n, seq_len, text, text_capacity, off, cnt, max_seqs, C.byref(ns), *tail)
         if check:
             self._check(rc)
         if rc != 0:
@@ -465,35 +492,35 @@ class GpuEngine:
         raw = text.raw
         return rc, [(raw[off[i]:off[i + 1]], int(cnt[i])) for i in range(ns.value)]
 
-    def eval_known_adapters(self, seq_ptr, qual_ptr, len_ptr, n, adapters, check=True):
+    def eval_known_adapters(self, seq_ptr, qual_ptr, len_ptr, n, adapters, check=True, exotic=None):
         """Evaluator::checkKnownAdapters over `adapters` (a list of bytes): returns (rc, counts int32[len(adapters)],
         mismatches int32[len(adapters)], checked_reads, best) - best an index into `adapters` or -1"""
-        fn = self.lib.fastp_gpu_eval_known_adapters
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int32,
-                       C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        fn, tail, keep = self._eval_fn("fastp_gpu_eval_known_adapters",
+                                       [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)], exotic)
         na = len(adapters)
         arr = (C.c_char_p * max(1, na))(*[bytes(x) for x in adapters])
         counts = np.zeros(max(1, na), dtype=np.int32)
         mism = np.zeros(max(1, na), dtype=np.int32)
         checked, best = C.c_int64(0), C.c_int32(-1)
         rc = fn(self.h, seq_ptr, qual_ptr, len_ptr, n, arr, na, counts.ctypes.data, mism.ctypes.data, C.byref(checked),
-                C.byref(best))
+                C.byref(best), *tail)
         if check:
             self._check(rc)
         return rc, counts[:na], mism[:na], int(checked.value), int(best.value)
 
-    def eval_adapter_seed(self, seq_ptr, qual_ptr, len_ptr, n, trim_tail1, seed, check=True):
+    def eval_adapter_seed(self, seq_ptr, qual_ptr, len_ptr, n, trim_tail1, seed, check=True, exotic=None):
         """the scans and dominant-path walks of Evaluator::getAdapterWithSeed for one seed (a bin of eval_adapter_kmers):
-        returns (rc, forward bytes, backward bytes - as the tree returns it, not reversed -, reached_leaf, hits)"""
-        fn = self.lib.fastp_gpu_eval_adapter_seed
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p,
-                       C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+        returns (rc, forward bytes, backward bytes - as the tree returns it, not reversed -, reached_leaf, hits).
+        With `exotic` the paths may hold any byte (a tree node prints the byte of the sequence that created it)"""
+        fn, tail, keep = self._eval_fn("fastp_gpu_eval_adapter_seed",
+                                       [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p,
+                                        C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int64)], exotic)
         fwd, bwd = C.create_string_buffer(abi.MAX_READ_LEN), C.create_string_buffer(abi.MAX_READ_LEN)
         nf, nb, leaf, hits = C.c_int32(0), C.c_int32(0), C.c_int32(1), C.c_int64(0)
         rc = fn(self.h, seq_ptr, qual_ptr, len_ptr, n, trim_tail1, seed, fwd, C.byref(nf), bwd, C.byref(nb), C.byref(leaf),
-                C.byref(hits))
+                C.byref(hits), *tail)
         if check:
             self._check(rc)
         return rc, fwd.raw[:nf.value], bwd.raw[:nb.value], bool(leaf.value), int(hits.value)

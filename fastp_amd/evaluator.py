@@ -8,6 +8,11 @@ The loops over the reads run on the device, through the engine's Evaluator calls
 10000-read gate, the top-10 seeds, the fold / count / complexity tests, the assembly of the adapter from a seed's two
 paths, matchKnownAdapter, the reachedLeaf rule - are restated here once, in the reference's order.
 
+Reads with letters outside ACGTN (soft-masked lower case, IUPAC codes, '.') are stored in the packed rows as if the
+letter were an A; `detect_adapter(..., exotic=...)` names them and the calls take their symbols from the FASTQ text
+(the `fastp_gpu_eval_*_x` forms), so the answer is the reference's for such samples too.  `detect_adapter_in_file` and
+`overrep_in_file` do this on their own.
+
 The list of known adapters is the caller's (the reference compiles its own in; this package ships none):
 `load_adapter_list` reads one from a file.
 
@@ -68,21 +73,33 @@ def match_known_adapter(seq: bytes, known_adapters) -> bytes:
     return b""
 
 
-def detect_adapter(g: engine.GpuEngine, seq_ptr, qual_ptr, len_ptr, n, known_adapters, trim_tail1: int = 0) -> bytes:
+def detect_adapter(g: engine.GpuEngine, seq_ptr, qual_ptr, len_ptr, n, known_adapters, trim_tail1: int = 0, exotic=None) -> bytes:
     """evalAdapterAndReadNum's adapter for the n reads whose packed rows (one mate) are at the DEVICE pointers, laid
-    out for `g`'s max_len: the adapter sequence, or b"" when none is found.  known_adapters: distinct bytes of ACGT."""
+    out for `g`'s max_len: the adapter sequence, or b"" when none is found.  known_adapters: distinct bytes of ACGT.
+
+    exotic: None, or (units, text_ptr, off_ptr, dense) for the reads with letters outside ACGTN - ascending int32 read
+    indexes, the DEVICE text holding their sequence bytes and the DEVICE offsets (dense: the parser's line_off table), as
+    the engine's eval_* calls take them.  After `parse_fastq`: (g.parse_exotic(), the chunk, its line_off table, True).
+
+    The result is what the reference returns, and with such reads it may itself hold a letter outside ACGT: a tree node
+    prints the byte of the read that created it (nucleotidetree.cpp:48-51).  The reference then ends with "the adapter
+    <adapter_sequence> can only have bases in {A, T, C, G}" (options.cpp:375-381), and `fastp_gpu_create` refuses such a
+    string as adapter_seq_r1 / r2 the same way (FASTP_GPU_E_INVALID, "adapter sequence may only contain A, T, C, G"):
+    what to do with such a result is the caller's decision."""
+    if exotic is not None and len(exotic[0]) == 0:
+        exotic = None
     known = [bytes(a) for a in known_adapters]
     # the reads the loading loop admits (:328-343)
     lens = g.device_download(len_ptr, 2 * min(n, READ_LIMIT)).view(np.uint16) if n > 0 else np.zeros(0, np.uint16)
     records = int(min(len(lens), np.searchsorted(np.cumsum(lens.astype(np.int64)), BASE_LIMIT, side="left") + 1)) if len(lens) else 0
     if records < 10000:                              # :357
         return b""
-    rc, _, _, _, best = g.eval_known_adapters(seq_ptr, qual_ptr, len_ptr, records, known)
+    rc, _, _, _, best = g.eval_known_adapters(seq_ptr, qual_ptr, len_ptr, records, known, exotic=_first(exotic, records))
     if best >= 0 and len(known[best]) > 8:           # :367
         return known[best]
     counts_ptr = g.device_alloc(4 << 20)
     try:
-        g.eval_adapter_kmers(seq_ptr, qual_ptr, len_ptr, records, trim_tail1, counts_ptr)
+        g.eval_adapter_kmers(seq_ptr, qual_ptr, len_ptr, records, trim_tail1, counts_ptr, exotic=_first(exotic, records))
         counts = g.device_download(counts_ptr, 4 << 20).view(np.uint32)
     finally:
         g.device_free(counts_ptr)
@@ -98,7 +115,7 @@ def detect_adapter(g: engine.GpuEngine, seq_ptr, qual_ptr, len_ptr, n, known_ada
         if sum(1 for s in range(len(seq) - 1) if seq[s] != seq[s + 1]) < 3:
             continue
         # getAdapterWithSeed :485-539
-        _, fwd, bwd, reached_leaf, _ = g.eval_adapter_seed(seq_ptr, qual_ptr, len_ptr, records, trim_tail1, key)
+        _, fwd, bwd, reached_leaf, _ = g.eval_adapter_seed(seq_ptr, qual_ptr, len_ptr, records, trim_tail1, key, exotic=_first(exotic, records))
         adapter = (bwd[::-1] + seq + fwd)[:60]
         matched = match_known_adapter(adapter, known)
         if matched:
@@ -108,13 +125,23 @@ def detect_adapter(g: engine.GpuEngine, seq_ptr, qual_ptr, len_ptr, n, known_ada
     return b""
 
 
-def _read_prefix(path: str) -> tuple[bytes, int, int]:
-    """the records the loading loop :328-343 reads from a plain or gzip-compressed FASTQ: (text, records, longest read)"""
+def _first(exotic, n):
+    """`exotic` cut to the listed reads below n (the calls take a list of indexes inside [0, n)); None if none is left"""
+    if exotic is None:
+        return None
+    units = np.asarray(exotic[0], dtype=np.int32)
+    units = units[:int(np.searchsorted(units, n))]   # (one offset per listed read: the first len(units) are the kept reads')
+    return (units,) + tuple(exotic[1:]) if len(units) else None
+
+
+def _read_prefix(path: str, read_limit: int = READ_LIMIT, base_limit: int = BASE_LIMIT) -> tuple[bytes, int, int]:
+    """the records a loading loop `while (records < read_limit && bases < base_limit)` (:328-343, :88) reads from a plain
+    or gzip-compressed FASTQ: (text, records, longest read)"""
     opener = gzip.open if path.endswith(".gz") else open
     out = []
     records = bases = longest = 0
     with opener(path, "rb") as f:
-        while records < READ_LIMIT and bases < BASE_LIMIT:
+        while records < read_limit and bases < base_limit:
             rec = [f.readline() for _ in range(4)]
             if not rec[0]:
                 break
@@ -127,36 +154,79 @@ def _read_prefix(path: str) -> tuple[bytes, int, int]:
     return b"".join(out), records, longest
 
 
-def detect_adapter_in_file(path: str, known_adapters, trim_tail1: int = 0, device: int = 0, lib_path: str | None = None) -> bytes:
-    """fastp's adapter auto-detection for one input file (plain or ".gz" FASTQ): reads the prefix the reference's
-    Evaluator would load, parses it on the device with an engine of its own and returns `detect_adapter`'s answer"""
-    text, records, longest = _read_prefix(path)
+def _check_longest(path, longest):
     if longest > abi.MAX_READ_LEN:
         raise ValueError(f"{path}: a read of {longest} bases; the device path holds reads of up to {abi.MAX_READ_LEN}")
+
+
+class _ParsedPrefix:
+    """a file's prefix parsed on the device with an engine of its own: packed rows, the chunk and its line table"""
+
+    def __init__(self, path, text, records, longest, device, lib_path):
+        max_len = max(longest, 32)
+        self.g = g = engine.GpuEngine(abi.default_params(False, max_len), device=device, lib_path=lib_path)
+        self.ptrs = []
+        try:
+            ss, qs = abi.seq_stride(max_len), abi.qual_stride(max_len)
+            cap = records + 2
+            t = self._alloc(len(text) + 32)
+            g.device_upload(t, text + b"\0" * ((-len(text)) % 16 + 16))
+            self.seq, self.qual, self.lens = self._alloc(cap * ss), self._alloc(cap * qs), self._alloc(cap * 2)
+            loff, llen = self._alloc(cap * 16), self._alloc(cap * 16)
+            info = g.parse_fastq(t, len(text), True, cap, self.seq, self.qual, self.lens, loff, llen)
+            if info.first_bad != -1:
+                raise ValueError(f"{path}: record {info.first_bad} is not FASTQ the device parser takes")
+            self.n = int(info.n_records)
+            # records with letters outside ACGTN: their symbols come from the chunk (fastp_gpu_eval_*_x)
+            self.exotic = (g.parse_exotic(), t, loff, True) if info.n_exotic else None
+        except BaseException:
+            self.close()
+            raise
+
+    def _alloc(self, nbytes):
+        self.ptrs.append(self.g.device_alloc(nbytes))
+        return self.ptrs[-1]
+
+    def close(self):
+        for p in self.ptrs:
+            self.g.device_free(p)
+        self.ptrs = []
+        self.g.close()
+
+
+def detect_adapter_in_file(path: str, known_adapters, trim_tail1: int = 0, device: int = 0, lib_path: str | None = None) -> bytes:
+    """fastp's adapter auto-detection for one input file (plain or ".gz" FASTQ): reads the prefix the reference's
+    Evaluator would load, parses it on the device with an engine of its own and returns `detect_adapter`'s answer.
+    Records with letters outside ACGTN are handed on as the parser lists them, so a soft-masked file gets the reference's
+    answer; see `detect_adapter` for an answer that holds such a letter itself."""
+    text, records, longest = _read_prefix(path)
+    _check_longest(path, longest)
     if records < 10000:
         return b""
-    max_len = max(longest, 32)
-    g = engine.GpuEngine(abi.default_params(False, max_len), device=device, lib_path=lib_path)
-    ptrs = []
+    p = _ParsedPrefix(path, text, records, longest, device, lib_path)
     try:
-        ss, qs = abi.seq_stride(max_len), abi.qual_stride(max_len)
-        cap = records + 2
-
-        def alloc(nbytes):
-            ptrs.append(g.device_alloc(nbytes))
-            return ptrs[-1]
-        t = alloc(len(text) + 32)
-        g.device_upload(t, text + b"\0" * ((-len(text)) % 16 + 16))
-        seq, qual, lens = alloc(cap * ss), alloc(cap * qs), alloc(cap * 2)
-        loff, llen = alloc(cap * 16), alloc(cap * 16)
-        info = g.parse_fastq(t, len(text), True, cap, seq, qual, lens, loff, llen)
-        if info.first_bad != -1:
-            raise ValueError(f"{path}: record {info.first_bad} is not FASTQ the device parser takes")
-        return detect_adapter(g, seq, qual, lens, int(info.n_records), known_adapters, trim_tail1)
+        return detect_adapter(p.g, p.seq, p.qual, p.lens, p.n, known_adapters, trim_tail1, exotic=p.exotic)
     finally:
-        for p in ptrs:
-            g.device_free(p)
-        g.close()
+        p.close()
+
+
+def overrep_in_file(path: str, seq_len: int, device: int = 0, lib_path: str | None = None, max_seqs: int = 1 << 16,
+                    text_capacity: int = 1 << 22) -> dict:
+    """Evaluator::computeOverRepSeq (evaluator.cpp:78-169) for one input file (plain or ".gz" FASTQ) and the sequence length
+    computeSeqLen found: reads the records its loop reads (while fewer than 151 * 10000 bases were seen), parses them on the
+    device and returns {sequence bytes: count}, the map Options::overRepSeqs starts from.  Sequences of reads with letters
+    outside ACGTN carry those bytes, as the reference's raw substrings do."""
+    text, records, longest = _read_prefix(path, read_limit=1 << 62, base_limit=151 * 10000)
+    _check_longest(path, longest)
+    if records == 0:
+        return {}
+    p = _ParsedPrefix(path, text, records, longest, device, lib_path)
+    try:
+        _, seqs = p.g.eval_overrep(p.seq, p.qual, p.lens, p.n, seq_len, max_seqs=max_seqs, text_capacity=text_capacity,
+                                   exotic=p.exotic)
+        return dict(seqs)
+    finally:
+        p.close()
 
 
 def load_adapter_list(path: str) -> list[bytes]:

@@ -677,6 +677,50 @@ int fastp_gpu_eval_adapter_seed(fastp_gpu_ctx* ctx, const uint8_t* seq, const ui
                                 int32_t n, int32_t trim_tail1, uint32_t seed, char* forward, int32_t* forward_len,
                                 char* backward, int32_t* backward_len, int32_t* reached_leaf, int64_t* hits);
 
+/* ---- the same four loops for samples with letters outside ACGTN ----------------------------------
+ * A packed row stores such a letter (soft-masked lower case, an IUPAC code, '.') as code 0 without the N flag, so the
+ * plain calls above see an 'A' there.  The _x calls take, beside the plain call's arguments, the reads that hold such
+ * letters and where their sequence bytes are - the fields and meaning of fastp_gpu_batch's exotic_* for one mate:
+ * exotic_unit (HOST memory) lists n_exotic ascending read indexes in [0, n); exotic_text and exotic_off are DEVICE
+ * memory; exotic_dense = 1: exotic_off is fastp_gpu_parse_fastq's line_off table (entry [4 * read + 1] is the read's
+ * sequence line in exotic_text, the parsed chunk); 0: exotic_off[k] is the byte offset of listed read k's sequence.
+ * After fastp_gpu_parse_fastq the list is fastp_gpu_parse_exotic's.  A listed read's symbols are its bytes, every other
+ * read's come from its packed row, and a byte b outside ACGTN is treated as the reference treats it:
+ *   _adapter_kmers_x, and the hit search of _adapter_seed_x - Evaluator::seq2int (evaluator.cpp:577-626): a window
+ *     holding anything but A T C G gives -1; b acts as N, 'a' is not 'A'.
+ *   _known_adapters_x - checkKnownAdapters (evaluator.cpp:266-287): a raw != against the adapter's letters; b is a
+ *     mismatch that counts towards cmplen / 16 and does not end the compare.
+ *   _adapter_seed_x - NucleotideTree::addSeq / getDominantPath (nucleotidetree.cpp:42-88): only the byte 'N' cuts a
+ *     sequence; every other byte descends into child b & 7 of eight ('a' and 'A' share one, 'n' goes on where 'N'
+ *     stops), all eight are summed and tested, and a node prints the byte of the sequence that created it - the first
+ *     in insertion order, reads then positions ascending.  forward / backward may therefore hold any byte.
+ *   _overrep_x - computeOverRepSeq (evaluator.cpp:99-110, :115-160): raw substrings in a std::map; b equals only the
+ *     same byte, and thresholds, the containment pass and the map's byte order work on raw bytes.  text may hold any byte.
+ * x == NULL or n_exotic == 0: exactly the plain call (the same kernels).  FASTP_GPU_E_INVALID, with nothing written to
+ * the outputs: a list that is not ascending, an index outside [0, n), n_exotic < 0, or a NULL exotic_unit / exotic_text /
+ * exotic_off with n_exotic > 0. */
+typedef struct fastp_gpu_eval_text {
+    int32_t n_exotic;
+    int32_t exotic_dense;
+    const int32_t* exotic_unit;   /* HOST memory */
+    const uint8_t* exotic_text;   /* DEVICE memory */
+    const uint32_t* exotic_off;   /* DEVICE memory */
+} fastp_gpu_eval_text;
+int fastp_gpu_eval_adapter_kmers_x(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len,
+                                   int32_t n, int32_t trim_tail1, uint32_t* counts, int64_t* records,
+                                   const fastp_gpu_eval_text* x);
+int fastp_gpu_eval_overrep_x(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len, int32_t n,
+                             int32_t seq_len, char* text, int64_t text_capacity, int64_t* off /* [max_seqs + 1] */,
+                             int64_t* count /* [max_seqs] */, int32_t max_seqs, int32_t* n_seqs, const fastp_gpu_eval_text* x);
+int fastp_gpu_eval_known_adapters_x(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len,
+                                    int32_t n, const char* const* adapters, int32_t n_adapters, int32_t* counts /* [n_adapters] */,
+                                    int32_t* mismatches /* [n_adapters] */, int64_t* checked_reads, int32_t* best,
+                                    const fastp_gpu_eval_text* x);
+int fastp_gpu_eval_adapter_seed_x(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint16_t* len,
+                                  int32_t n, int32_t trim_tail1, uint32_t seed, char* forward, int32_t* forward_len,
+                                  char* backward, int32_t* backward_len, int32_t* reached_leaf, int64_t* hits,
+                                  const fastp_gpu_eval_text* x);
+
 /* Process one batch whose buffers (and result buffers) live in HOST memory:
  * H2D copy, kernels, D2H copy, synchronous. */
 int fastp_gpu_submit_host(fastp_gpu_ctx* ctx, const fastp_gpu_batch* batch, fastp_gpu_results* res);
