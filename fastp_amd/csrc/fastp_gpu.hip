@@ -419,9 +419,8 @@ struct fastp_gpu_ctx {
     void* d_x_text[2] = {nullptr, nullptr}; size_t x_text_cap[2] = {0, 0};   // host submits: the raw text + offsets staged in HBM
     void* d_x_off[2] = {nullptr, nullptr}; size_t x_off_cap[2] = {0, 0};
     std::vector<int32_t> parse_exotic;                     // records of the last fastp_gpu_parse_fastq call with letters outside ACGTN
-    // staging for submit_host
-    void* d_stage = nullptr; size_t stage_cap = 0;
-    // fastp_gpu_submit_host_async: device staging, completion event and what to finish per slot
+    // host submits: device staging, completion event and what to finish per slot.  The public slots, then the one
+    // fastp_gpu_submit_host uses (no slot number reaches it)
     struct AsyncSlot {
         void* d_stage = nullptr; size_t cap = 0;
         hipEvent_t done = nullptr;
@@ -431,7 +430,7 @@ struct fastp_gpu_ctx {
         const void* d_corr = nullptr;         // the batch's sparse lists in the slot's device staging: copied out when the batch
         const void* d_ev = nullptr;           // has arrived, as many entries as were written (not their whole capacity per batch)
         hipStream_t copy = nullptr;
-    } aslot[FASTP_GPU_ASYNC_SLOTS];
+    } aslot[FASTP_GPU_ASYNC_SLOTS + 1];
     u64* d_phase = nullptr;   // optional per-phase cycle counters (FASTP_GPU_PHASE_TIMING=1)
     // adapter census (fq_census.h): FilterResult::mAdapter1 / mAdapter2 as two persistent tables, allocated at the first use
     u8* d_cs_map[2] = {nullptr, nullptr};
@@ -526,7 +525,7 @@ extern "C" void fastp_gpu_destroy(fastp_gpu_ctx* ctx) {
     }
     for (auto& pr : ctx->free_events) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     void* bufs[] = {ctx->d_ov_limit, ctx->d_lowq, ctx->d_cplx, ctx->d_primes, ctx->d_planes, ctx->d_posum, ctx->d_fasta_words, ctx->d_fasta_len, ctx->d_ctr, ctx->d_slabs,
-                    ctx->d_bitmap, ctx->d_dup_pos, ctx->d_table, ctx->d_need, ctx->d_dupflag, ctx->d_stage, ctx->d_phase,
+                    ctx->d_bitmap, ctx->d_dup_pos, ctx->d_table, ctx->d_need, ctx->d_dupflag, ctx->d_phase,
                     ctx->d_ovr_table[0], ctx->d_ovr_table[1], ctx->d_ovr_sym[0], ctx->d_ovr_sym[1], ctx->d_ovr_len[0],
                     ctx->d_ovr_len[1], ctx->d_post_seen, ctx->d_ovr_work, ctx->d_parse, ctx->d_fmt, ctx->d_prefix, ctx->d_inf, ctx->d_ovr_corr, ctx->d_eval, ctx->d_eval_x, ctx->d_def, ctx->d_setw, ctx->d_cfilter,
                     ctx->d_st_slabs, ctx->d_swin[0], ctx->d_swin[1], ctx->d_ln_slabs,
@@ -1043,28 +1042,36 @@ static int print_geometry(fastp_gpu_ctx* ctx) {
 // first stream's queue are held until the search ends (the next one is then given another queue) and closed afterwards
 static int probe_tail_stream(fastp_gpu_ctx* ctx) {
     int* d_flag = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&d_flag, 2 * sizeof(int)));
-    std::vector<hipStream_t> rejected;
+    std::vector<hipStream_t> held;   // the candidates so far: all but the chosen one are closed on the way out
     const int tries = 6;
-    for (int t = 0; t < tries && !ctx->tail; t++) {
-        hipStream_t cand = nullptr;
-        HIP_TRY(ctx, hipStreamCreateWithFlags(&cand, hipStreamNonBlocking));
-        HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 2 * sizeof(int), ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        hipLaunchKernelGGL(fq_probe_wait_kernel, dim3(1), dim3(64), 0, ctx->stream, d_flag, 2000000ll);
-        hipLaunchKernelGGL(fq_probe_set_kernel, dim3(1), dim3(64), 0, cand, d_flag);
-        HIP_TRY(ctx, hipStreamSynchronize(cand));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        int h[2] = {0, 0};
-        HIP_TRY(ctx, hipMemcpy(h, d_flag, sizeof(h), hipMemcpyDeviceToHost));
-        if (h[1] != 0) ctx->tail = cand;
-        else rejected.push_back(cand);
-    }
-    if (!ctx->tail) { ctx->tail = rejected.back(); rejected.pop_back(); }   // (none runs beside it: correct, one behind the other)
-    if (ctx->sw.verbose) fprintf(stderr, "fastp_gpu: second stream: candidate %d of %d runs beside the first\n", (int)rejected.size() + 1, tries);
-    for (hipStream_t r : rejected) (void)hipStreamDestroy(r);
-    (void)hipFree(d_flag);
-    return 0;
+    auto search = [&]() -> int {
+        HIP_TRY(ctx, hipMalloc((void**)&d_flag, 2 * sizeof(int)));
+        for (int t = 0, beside = 0; t < tries && !beside; t++) {
+            hipStream_t cand = nullptr;
+            HIP_TRY(ctx, hipStreamCreateWithFlags(&cand, hipStreamNonBlocking));
+            held.push_back(cand);
+            HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 2 * sizeof(int), ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            hipLaunchKernelGGL(fq_probe_wait_kernel, dim3(1), dim3(64), 0, ctx->stream, d_flag, 2000000ll);
+            HIP_TRY(ctx, hipGetLastError());
+            hipLaunchKernelGGL(fq_probe_set_kernel, dim3(1), dim3(64), 0, cand, d_flag);
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipStreamSynchronize(cand));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            int h[2] = {0, 0};
+            HIP_TRY(ctx, hipMemcpy(h, d_flag, sizeof(h), hipMemcpyDeviceToHost));
+            beside = h[1];
+        }
+        ctx->tail = held.back();   // (if none runs beside the first, the last one: correct, one behind the other)
+        held.pop_back();
+        if (ctx->sw.verbose) fprintf(stderr, "fastp_gpu: second stream: candidate %d of %d runs beside the first\n", (int)held.size() + 1, tries);
+        return 0;
+    };
+    const int rc = search();
+    if (rc) (void)hipDeviceSynchronize();   // a probe kernel may still be running: it reads and writes d_flag
+    for (hipStream_t s : held) (void)hipStreamDestroy(s);
+    if (d_flag) (void)hipFree(d_flag);
+    return rc;
 }
 #endif
 
@@ -1238,6 +1245,19 @@ static int ensure(fastp_gpu_ctx* ctx, void** buf, size_t* cap, size_t need) {
     *cap = want;
     return 0;
 }
+
+// A scratch buffer's layout, stated once: the pieces in order, each `bytes` rounded up to `align` long.  A site runs its takes
+// on a null base first - nothing is handed out, `off` ends as the size to `ensure` - and again on the buffer for the pointers.
+struct Carve {
+    u8* base;
+    size_t off = 0;
+    explicit Carve(void* b) : base((u8*)b) {}
+    template <class T = u8> T* take(size_t bytes, size_t align = 1) {
+        const size_t at = off;
+        off += (bytes + align - 1) / align * align;
+        return base ? (T*)(base + at) : nullptr;
+    }
+};
 
 static int get_events(fastp_gpu_ctx* ctx, hipEvent_t* a, hipEvent_t* b) {
     if (ctx->pending_events.size() >= 64) drain_events(ctx);
@@ -3089,12 +3109,16 @@ static int eval_stage_text(fastp_gpu_ctx* ctx, const fastp_gpu_eval_text* x, int
     if (!on) return FASTP_GPU_OK;
     hipStream_t st = ctx->stream;
     const size_t b_off = (size_t)n * 4;
-    int rc = ensure(ctx, (void**)&ctx->d_eval_x, &ctx->eval_x_cap, b_off + (size_t)x->n_exotic * 4);
-    if (rc) return rc;
     EvalListArgs l;
     memset(&l, 0, sizeof(l));
-    l.rawoff = (u32*)ctx->d_eval_x;
-    l.unit = (const int*)(ctx->d_eval_x + b_off);
+    auto lay = [&](Carve c) {
+        l.rawoff = c.take<u32>(b_off);
+        l.unit = c.take<int>((size_t)x->n_exotic * 4);
+        return c.off;
+    };
+    int rc = ensure(ctx, (void**)&ctx->d_eval_x, &ctx->eval_x_cap, lay(Carve(nullptr)));
+    if (rc) return rc;
+    lay(Carve(ctx->d_eval_x));
     l.n_exotic = x->n_exotic;
     l.dense = x->exotic_dense ? 1 : 0;
     l.off = x->exotic_off;
@@ -3210,19 +3234,21 @@ static int eval_overrep(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8_t* q
     if (cap > (1ull << 31)) return fail(ctx, FASTP_GPU_E_UNSUPPORTED, "substring census larger than 2^30 items");
     // a substring over its threshold occurs >= 3 times
     a.hot_cap = (u32)std::min<uint64_t>(items / 3 + 16, 1u << 22);
-    const size_t b_slot = cap * 8, b_count = cap * 4, b_hot = (size_t)a.hot_cap * 8, b_hc = (size_t)a.hot_cap * 4,
-                 b_text = (size_t)a.hot_cap * 152;
-    rc = ensure(ctx, (void**)&ctx->d_eval, &ctx->eval_cap, b_slot + b_count + b_hot + b_hc + 16 + b_text);
+    const size_t b_slot = cap * 8, b_count = cap * 4;
+    auto lay = [&](Carve c) {
+        a.slot = c.take<u64>(b_slot);
+        a.count = c.take<u32>(b_count);
+        a.hot = c.take<u64>((size_t)a.hot_cap * 8);
+        a.hot_count = c.take<u32>((size_t)a.hot_cap * 4);
+        a.n_hot = c.take<u32>(16);
+        a.text = c.take((size_t)a.hot_cap * 152);
+        return c.off;
+    };
+    rc = ensure(ctx, (void**)&ctx->d_eval, &ctx->eval_cap, lay(Carve(nullptr)));
     if (rc) return rc;
-    u8* base = ctx->d_eval;
-    a.slot = (u64*)base;
-    a.count = (u32*)(base + b_slot);
-    a.hot = (u64*)(base + b_slot + b_count);
-    a.hot_count = (u32*)(base + b_slot + b_count + b_hot);
-    a.n_hot = (u32*)(base + b_slot + b_count + b_hot + b_hc);
-    a.text = base + b_slot + b_count + b_hot + b_hc + 16;
+    lay(Carve(ctx->d_eval));
     a.mask = (u32)(cap - 1);
-    HIP_TRY(ctx, hipMemsetAsync(base, 0, b_slot + b_count, st));
+    HIP_TRY(ctx, hipMemsetAsync(a.slot, 0, b_slot + b_count, st));
     HIP_TRY(ctx, hipMemsetAsync(a.n_hot, 0, 16, st));
     const long long lanes = (long long)a.r.n * a.span;
     EvalText tx;
@@ -3347,19 +3373,21 @@ static int eval_known_adapters(fastp_gpu_ctx* ctx, const uint8_t* seq, const uin
             words[(size_t)i * a.ad_words + k / 32] |= code << (2 * (k % 32));
         }
     }
-    const size_t b_words = words.size() * 8, b_alen = ((size_t)A * 2 + 7) & ~(size_t)7, b_cnt = (size_t)A * 8 + 8,
-                 b_bits = (((size_t)a.r.n * a.bit_words * 4) + 7) & ~(size_t)7, b_mm = (size_t)a.r.n * A;
-    int rc = ensure(ctx, (void**)&ctx->d_eval, &ctx->eval_cap, b_words + b_alen + b_cnt + b_bits + b_mm);
+    const size_t b_cnt = 8 + (size_t)A * 8;   // checkedReads | possibleCounts, mismatches: they come back in one copy
+    auto lay = [&](Carve c) {
+        a.words = c.take<u64>(words.size() * 8);
+        a.alen = c.take<u16>((size_t)A * 2, 8);
+        a.checked = c.take<long long>(8);
+        a.counts = c.take<int>((size_t)A * 8);
+        a.bits = c.take<u32>((size_t)a.r.n * a.bit_words * 4, 8);
+        a.mm = c.take((size_t)a.r.n * A);
+        return c.off;
+    };
+    int rc = ensure(ctx, (void**)&ctx->d_eval, &ctx->eval_cap, lay(Carve(nullptr)));
     if (rc) return rc;
-    u8* base = ctx->d_eval;
-    a.words = (const u64*)base;
-    a.alen = (const u16*)(base + b_words);
-    a.checked = (long long*)(base + b_words + b_alen);
-    a.counts = (int*)(base + b_words + b_alen + 8);
-    a.bits = (u32*)(base + b_words + b_alen + b_cnt);
-    a.mm = base + b_words + b_alen + b_cnt + b_bits;
-    HIP_TRY(ctx, hipMemcpyAsync(base, words.data(), b_words, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + b_words, alen.data(), (size_t)A * 2, hipMemcpyHostToDevice, st));
+    lay(Carve(ctx->d_eval));
+    HIP_TRY(ctx, hipMemcpyAsync((void*)a.words, words.data(), words.size() * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync((void*)a.alen, alen.data(), (size_t)A * 2, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));   // (the staging vectors are pageable)
     EvalText tx;
     bool with_text;
@@ -3439,18 +3467,21 @@ static int eval_adapter_seed(fastp_gpu_ctx* ctx, const uint8_t* seq, const uint8
     rc = eval_stage_text(ctx, x, n, tx, with_text);
     if (rc) return rc;
     // count the hits, size the list by the count, list them
-    const size_t b_head = 8 + 16 + 1024;   // n_hits | path_len[2], reached_leaf | the two paths
     u64 nh = 0;
     for (int pass = 0; pass < 2; pass++) {
-        rc = ensure(ctx, (void**)&ctx->d_eval, &ctx->eval_cap, b_head + (size_t)nh * 4);
+        auto lay = [&](Carve c) {   // n_hits | path_len[2], reached_leaf | the two paths | the hit list
+            a.n_hits = c.take<u64>(8);
+            a.path_len = c.take<int>(16);
+            a.path = c.take(1024);
+            a.hits = c.take<u32>((size_t)nh * 4);
+            return c.off;
+        };
+        rc = ensure(ctx, (void**)&ctx->d_eval, &ctx->eval_cap, lay(Carve(nullptr)));
         if (rc) return rc;
-        u8* base = ctx->d_eval;
-        a.n_hits = (u64*)base;
-        a.path_len = (int*)(base + 8);
-        a.path = base + 24;
-        a.hits = pass ? (u32*)(base + b_head) : nullptr;
+        lay(Carve(ctx->d_eval));
+        if (!pass) a.hits = nullptr;
         a.cap = nh;
-        HIP_TRY(ctx, hipMemsetAsync(base, 0, 24, st));
+        HIP_TRY(ctx, hipMemsetAsync(a.n_hits, 0, 24, st));
         if (with_text) hipLaunchKernelGGL(fq_eval_seed_gather_x_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, a, tx);
         else hipLaunchKernelGGL(fq_eval_seed_gather_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, a);
         HIP_TRY(ctx, hipGetLastError());
@@ -3512,28 +3543,31 @@ extern "C" int fastp_gpu_deflate_bgzf_level(fastp_gpu_ctx* ctx, const uint8_t* t
     // tokens per input byte + a member slot per block - so a larger round only costs HBM
     const int round = (int)std::min<int64_t>(total_blocks, (int64_t)ctx->cus * 8);
     const int chain_grid = chain ? std::min(round, ctx->cus * std::max(1, ctx->lds_bytes / (int)sizeof(DefChainLds))) : 0;
+    DeflateArgs scratch;
+    memset(&scratch, 0, sizeof(scratch));
     if (round > 0) {
-        const size_t b_slots = (size_t)round * DEF_SLOT, b_tok = (size_t)round * DEF_BLOCK * 4, b_sizes = (size_t)round * 4 + 8,
-                     b_offs = ((size_t)round + 1) * 8, b_prev = (size_t)chain_grid * DEF_PREV * 2;   // (a chain array per RESIDENT workgroup: 128 KB x 5 per CU)
-        int rc = ensure(ctx, (void**)&ctx->d_def, &ctx->def_cap, b_slots + b_tok + b_sizes + b_offs + b_prev);
+        auto lay = [&](Carve c) {
+            scratch.slots = c.take((size_t)round * DEF_SLOT);
+            scratch.tokens = c.take<u32>((size_t)round * DEF_BLOCK * 4);
+            scratch.sizes = c.take<u32>((size_t)round * 4 + 8);
+            scratch.offs = c.take<u64>(((size_t)round + 1) * 8);
+            if (chain) scratch.prev = c.take<u16>((size_t)chain_grid * DEF_PREV * 2);   // (a chain array per RESIDENT workgroup: 128 KB x 5 per CU)
+            return c.off;
+        };
+        int rc = ensure(ctx, (void**)&ctx->d_def, &ctx->def_cap, lay(Carve(nullptr)));
         if (rc) return rc;
+        lay(Carve(ctx->d_def));
     }
     u64 written = 0;   // bytes needed so far
     for (int64_t b0 = 0; b0 < total_blocks; b0 += round) {
-        DeflateArgs a;
-        memset(&a, 0, sizeof(a));
+        DeflateArgs a = scratch;
         a.nblocks = (int)std::min<int64_t>(round, total_blocks - b0);
         a.text = text + (size_t)b0 * DEF_BLOCK;
         a.nbytes = (u64)std::min<int64_t>(nbytes - b0 * DEF_BLOCK, (int64_t)a.nblocks * DEF_BLOCK);
-        a.slots = ctx->d_def;
-        a.tokens = (u32*)(ctx->d_def + (size_t)round * DEF_SLOT);
-        a.sizes = (u32*)((u8*)a.tokens + (size_t)round * DEF_BLOCK * 4);
-        a.offs = (u64*)((u8*)a.sizes + (size_t)round * 4 + 8);
         a.out = out;
         a.out_base = written;
         a.out_cap = (u64)out_capacity;
         if (chain) {
-            a.prev = (u16*)((u8*)a.offs + ((size_t)round + 1) * 8);
             a.depth = chain_depth;
             a.lazy_max = chain_lazy;
             const int grid = std::min(a.nblocks, chain_grid);
@@ -3631,96 +3665,7 @@ static int stage_exotic(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, fastp_gpu_
     return FASTP_GPU_OK;
 }
 
-extern "C" int fastp_gpu_submit_host(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, fastp_gpu_results* res) {
-    if (!ctx || !b || !res) return fail(ctx, FASTP_GPU_E_INVALID, "null argument");
-    if (b->n < 0) return fail(ctx, FASTP_GPU_E_INVALID, "negative batch size");
-    if (b->n == 0) { if (res->n_corrections) *res->n_corrections = 0; return FASTP_GPU_OK; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t n = (size_t)b->n;
-    const size_t ss = fastp_gpu_seq_stride(ctx->dp.max_len), qs = fastp_gpu_qual_stride(ctx->dp.max_len);
-    const int mates = ctx->dp.paired ? 2 : 1;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t per_mate_in = al(n * ss) + al(n * qs) + al(n * 2);
-    const size_t per_mate_out = al(n * sizeof(fastp_gpu_read_result));
-    const size_t pair_out = ctx->dp.paired ? al(n * sizeof(fastp_gpu_pair_result)) : 0;
-    const size_t corr_out = (res->corrections && res->corrections_capacity > 0)
-                                ? al((size_t)res->corrections_capacity * sizeof(fastp_gpu_correction)) : 0;
-    const size_t ev_out = (res->adapter_events && res->adapter_events_capacity > 0)
-                              ? al((size_t)res->adapter_events_capacity * sizeof(fastp_gpu_adapter_event)) : 0;
-    const size_t total = mates * (per_mate_in + per_mate_out) + pair_out + corr_out + ev_out + 512;
-    int rc = ensure(ctx, &ctx->d_stage, &ctx->stage_cap, total);
-    if (rc) return rc;
-    char* base = (char*)ctx->d_stage;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base + off; off += al(bytes); return p; };
-    fastp_gpu_batch db = *b;
-    fastp_gpu_results dr = *res;
-    hipStream_t st = ctx->stream;
-    const void* hs[2][3] = {{b->seq1, b->qual1, b->len1}, {b->seq2, b->qual2, b->len2}};
-    void* dsq[2][3];
-    for (int m = 0; m < mates; m++) {
-        if (!hs[m][0] || !hs[m][1] || !hs[m][2]) return fail(ctx, FASTP_GPU_E_INVALID, "missing input buffer");
-        dsq[m][0] = take(n * ss);
-        dsq[m][1] = take(n * qs);
-        dsq[m][2] = take(n * 2);
-        HIP_TRY(ctx, hipMemcpyAsync(dsq[m][0], hs[m][0], n * ss, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(dsq[m][1], hs[m][1], n * qs, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(dsq[m][2], hs[m][2], n * 2, hipMemcpyHostToDevice, st));
-    }
-    db.seq1 = (const uint8_t*)dsq[0][0]; db.qual1 = (const uint8_t*)dsq[0][1]; db.len1 = (const uint16_t*)dsq[0][2];
-    if (mates == 2) {
-        db.seq2 = (const uint8_t*)dsq[1][0]; db.qual2 = (const uint8_t*)dsq[1][1]; db.len2 = (const uint16_t*)dsq[1][2];
-    }
-    dr.r1 = (fastp_gpu_read_result*)take(n * sizeof(fastp_gpu_read_result));
-    if (mates == 2) {
-        dr.r2 = (fastp_gpu_read_result*)take(n * sizeof(fastp_gpu_read_result));
-        dr.pair = (fastp_gpu_pair_result*)take(n * sizeof(fastp_gpu_pair_result));
-    }
-    if (corr_out) dr.corrections = (fastp_gpu_correction*)take((size_t)res->corrections_capacity * sizeof(fastp_gpu_correction));
-    else { dr.corrections = nullptr; dr.corrections_capacity = 0; }
-    dr.n_corrections = (int32_t*)take(sizeof(int32_t));
-    if (ev_out) dr.adapter_events = (fastp_gpu_adapter_event*)take((size_t)res->adapter_events_capacity * sizeof(fastp_gpu_adapter_event));
-    else { dr.adapter_events = nullptr; dr.adapter_events_capacity = 0; }
-    dr.n_adapter_events = (int32_t*)take(sizeof(int32_t));
-    rc = stage_exotic(ctx, b, &db, st);
-    if (!rc) rc = fastp_gpu_submit_device(ctx, &db, &dr, st);
-    if (rc) {   // copies from the caller's pinned buffers are queued: they must have drained before the caller may reuse them
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(res->r1, dr.r1, n * sizeof(fastp_gpu_read_result), hipMemcpyDeviceToHost, st));
-    if (mates == 2) {
-        HIP_TRY(ctx, hipMemcpyAsync(res->r2, dr.r2, n * sizeof(fastp_gpu_read_result), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipMemcpyAsync(res->pair, dr.pair, n * sizeof(fastp_gpu_pair_result), hipMemcpyDeviceToHost, st));
-    }
-    int32_t ncorr = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&ncorr, dr.n_corrections, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    int32_t nev = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&nev, dr.n_adapter_events, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (res->n_adapter_events) *res->n_adapter_events = nev < res->adapter_events_capacity ? nev : res->adapter_events_capacity;
-    if (ev_out && nev > 0) {
-        const int32_t take_n = nev < res->adapter_events_capacity ? nev : res->adapter_events_capacity;
-        HIP_TRY(ctx, hipMemcpy(res->adapter_events, dr.adapter_events, (size_t)take_n * sizeof(fastp_gpu_adapter_event),
-                               hipMemcpyDeviceToHost));
-        if (nev > res->adapter_events_capacity) return fail(ctx, FASTP_GPU_E_OVERFLOW, "adapter event list capacity exceeded");
-    }
-    if (res->n_corrections) *res->n_corrections = ncorr;
-    if (corr_out && ncorr > 0) {
-        if (ncorr > res->corrections_capacity) {
-            if (res->n_corrections) *res->n_corrections = res->corrections_capacity;
-            HIP_TRY(ctx, hipMemcpy(res->corrections, dr.corrections,
-                                   (size_t)res->corrections_capacity * sizeof(fastp_gpu_correction), hipMemcpyDeviceToHost));
-            return fail(ctx, FASTP_GPU_E_OVERFLOW, "correction list capacity exceeded");
-        }
-        HIP_TRY(ctx, hipMemcpy(res->corrections, dr.corrections, (size_t)ncorr * sizeof(fastp_gpu_correction),
-                               hipMemcpyDeviceToHost));
-    }
-    return FASTP_GPU_OK;
-}
-
-
-// ---- asynchronous host submits (include/fastp_gpu.h "Pipelined host submits") ----
+// ---- host submits (include/fastp_gpu.h "Pipelined host submits"; fastp_gpu_submit_host is one submit and its wait) ----
 extern "C" int fastp_gpu_host_alloc(fastp_gpu_ctx* ctx, int64_t bytes, void** ptr) {
     if (!ctx || !ptr || bytes < 0) return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -3733,75 +3678,74 @@ extern "C" int fastp_gpu_host_free(fastp_gpu_ctx* ctx, void* ptr) {
     return FASTP_GPU_OK;
 }
 
-extern "C" int fastp_gpu_submit_host_async(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, fastp_gpu_results* res, int slot) {
-    if (!ctx || !b || !res) return fail(ctx, FASTP_GPU_E_INVALID, "null argument");
-    if (slot < 0 || slot >= FASTP_GPU_ASYNC_SLOTS) return fail(ctx, FASTP_GPU_E_INVALID, "slot out of range");
-    if (b->n <= 0) return fail(ctx, FASTP_GPU_E_INVALID, "empty batch");
-    fastp_gpu_ctx::AsyncSlot& sl = ctx->aslot[slot];
-    if (sl.busy) return fail(ctx, FASTP_GPU_E_INVALID, "slot still in flight: fastp_gpu_wait it first");
+// One batch in host memory through a slot: its rows into the slot's device staging, the step, the records back - all queued
+// on the context's stream, the slot's event behind them.  Nothing is queued before every input has been checked; once
+// something is, a failure drains the stream (the caller may reuse its buffers as soon as the call has returned).
+static int submit_slot(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, fastp_gpu_results* res, fastp_gpu_ctx::AsyncSlot& sl) {
+    const int mates = ctx->dp.paired ? 2 : 1;
+    const void* hs[2][3] = {{b->seq1, b->qual1, b->len1}, {b->seq2, b->qual2, b->len2}};
+    for (int m = 0; m < mates; m++)
+        if (!hs[m][0] || !hs[m][1] || !hs[m][2]) return fail(ctx, FASTP_GPU_E_INVALID, "missing input buffer");
+    if (!res->r1 || (mates == 2 && (!res->r2 || !res->pair))) return fail(ctx, FASTP_GPU_E_INVALID, "missing result buffer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!sl.done) HIP_TRY(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
     if (!sl.counts) HIP_TRY(ctx, hipHostMalloc((void**)&sl.counts, 64));
     const size_t n = (size_t)b->n;
-    const size_t ss = fastp_gpu_seq_stride(ctx->dp.max_len), qs = fastp_gpu_qual_stride(ctx->dp.max_len);
-    const int mates = ctx->dp.paired ? 2 : 1;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t in_bytes[3] = {n * fastp_gpu_seq_stride(ctx->dp.max_len), n * fastp_gpu_qual_stride(ctx->dp.max_len), n * 2};
     const size_t corr_cap = (res->corrections && res->corrections_capacity > 0) ? (size_t)res->corrections_capacity : 0;
     const size_t ev_cap = (res->adapter_events && res->adapter_events_capacity > 0) ? (size_t)res->adapter_events_capacity : 0;
-    const size_t total = mates * (al(n * ss) + al(n * qs) + al(n * 2) + al(n * sizeof(fastp_gpu_read_result))) +
-                         al(n * sizeof(fastp_gpu_pair_result)) + al(corr_cap * sizeof(fastp_gpu_correction)) +
-                         al(ev_cap * sizeof(fastp_gpu_adapter_event)) + 1024;
-    int rc = ensure(ctx, &sl.d_stage, &sl.cap, total);
-    if (rc) return rc;
-    char* base = (char*)sl.d_stage;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base + off; off += al(bytes); return p; };
-    hipStream_t st = ctx->stream;
-    fastp_gpu_batch db = *b;
+    void* dsq[2][3];
     fastp_gpu_results dr;
     memset(&dr, 0, sizeof(dr));
-    const void* hs[2][3] = {{b->seq1, b->qual1, b->len1}, {b->seq2, b->qual2, b->len2}};
-    void* dsq[2][3];
-    for (int m = 0; m < mates; m++) {
-        if (!hs[m][0] || !hs[m][1] || !hs[m][2]) return fail(ctx, FASTP_GPU_E_INVALID, "missing input buffer");
-        dsq[m][0] = take(n * ss);
-        dsq[m][1] = take(n * qs);
-        dsq[m][2] = take(n * 2);
-        HIP_TRY(ctx, hipMemcpyAsync(dsq[m][0], hs[m][0], n * ss, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(dsq[m][1], hs[m][1], n * qs, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(dsq[m][2], hs[m][2], n * 2, hipMemcpyHostToDevice, st));
-    }
+    dr.corrections_capacity = (int32_t)corr_cap;
+    dr.adapter_events_capacity = (int32_t)ev_cap;
+    auto lay = [&](Carve c) {   // every piece on a 256-byte boundary
+        for (int m = 0; m < mates; m++)
+            for (int k = 0; k < 3; k++) dsq[m][k] = c.take(in_bytes[k], 256);
+        dr.r1 = c.take<fastp_gpu_read_result>(n * sizeof(fastp_gpu_read_result), 256);
+        if (mates == 2) {
+            dr.r2 = c.take<fastp_gpu_read_result>(n * sizeof(fastp_gpu_read_result), 256);
+            dr.pair = c.take<fastp_gpu_pair_result>(n * sizeof(fastp_gpu_pair_result), 256);
+        }
+        if (corr_cap) dr.corrections = c.take<fastp_gpu_correction>(corr_cap * sizeof(fastp_gpu_correction), 256);
+        dr.n_corrections = c.take<int32_t>(sizeof(int32_t), 256);
+        if (ev_cap) dr.adapter_events = c.take<fastp_gpu_adapter_event>(ev_cap * sizeof(fastp_gpu_adapter_event), 256);
+        dr.n_adapter_events = c.take<int32_t>(sizeof(int32_t), 256);
+        return c.off;
+    };
+    int rc = ensure(ctx, &sl.d_stage, &sl.cap, lay(Carve(nullptr)));
+    if (rc) return rc;
+    lay(Carve(sl.d_stage));
+    hipStream_t st = ctx->stream;
+    fastp_gpu_batch db = *b;
     db.seq1 = (const uint8_t*)dsq[0][0]; db.qual1 = (const uint8_t*)dsq[0][1]; db.len1 = (const uint16_t*)dsq[0][2];
     if (mates == 2) {
         db.seq2 = (const uint8_t*)dsq[1][0]; db.qual2 = (const uint8_t*)dsq[1][1]; db.len2 = (const uint16_t*)dsq[1][2];
     }
-    dr.r1 = (fastp_gpu_read_result*)take(n * sizeof(fastp_gpu_read_result));
-    if (mates == 2) {
-        dr.r2 = (fastp_gpu_read_result*)take(n * sizeof(fastp_gpu_read_result));
-        dr.pair = (fastp_gpu_pair_result*)take(n * sizeof(fastp_gpu_pair_result));
-    }
-    if (corr_cap) { dr.corrections = (fastp_gpu_correction*)take(corr_cap * sizeof(fastp_gpu_correction)); dr.corrections_capacity = (int32_t)corr_cap; }
-    dr.n_corrections = (int32_t*)take(sizeof(int32_t));
-    if (ev_cap) { dr.adapter_events = (fastp_gpu_adapter_event*)take(ev_cap * sizeof(fastp_gpu_adapter_event)); dr.adapter_events_capacity = (int32_t)ev_cap; }
-    dr.n_adapter_events = (int32_t*)take(sizeof(int32_t));
-    rc = stage_exotic(ctx, b, &db, st);
-    if (!rc) rc = fastp_gpu_submit_device(ctx, &db, &dr, st);
-    if (rc) {   // copies from the caller's pinned buffers are queued: they must have drained before the caller may reuse them
+    auto queue = [&]() -> int {
+        for (int m = 0; m < mates; m++)
+            for (int k = 0; k < 3; k++) HIP_TRY(ctx, hipMemcpyAsync(dsq[m][k], hs[m][k], in_bytes[k], hipMemcpyHostToDevice, st));
+        if (int e = stage_exotic(ctx, b, &db, st)) return e;
+        if (int e = fastp_gpu_submit_device(ctx, &db, &dr, st)) return e;
+        HIP_TRY(ctx, hipMemcpyAsync(res->r1, dr.r1, n * sizeof(fastp_gpu_read_result), hipMemcpyDeviceToHost, st));
+        if (mates == 2) {
+            HIP_TRY(ctx, hipMemcpyAsync(res->r2, dr.r2, n * sizeof(fastp_gpu_read_result), hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipMemcpyAsync(res->pair, dr.pair, n * sizeof(fastp_gpu_pair_result), hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(&sl.counts[0], dr.n_corrections, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(&sl.counts[1], dr.n_adapter_events, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipEventRecord(sl.done, st));
+        return FASTP_GPU_OK;
+    };
+    rc = queue();
+    if (rc) {   // copies from and to the caller's buffers may be queued: they must have drained before the caller may reuse them
         (void)hipStreamSynchronize(st);
         return rc;
     }
-    HIP_TRY(ctx, hipMemcpyAsync(res->r1, dr.r1, n * sizeof(fastp_gpu_read_result), hipMemcpyDeviceToHost, st));
-    if (mates == 2) {
-        HIP_TRY(ctx, hipMemcpyAsync(res->r2, dr.r2, n * sizeof(fastp_gpu_read_result), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipMemcpyAsync(res->pair, dr.pair, n * sizeof(fastp_gpu_pair_result), hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(&sl.counts[0], dr.n_corrections, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(&sl.counts[1], dr.n_adapter_events, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     // the sparse lists (--correction / --adapter_fasta) come out in finish_slot: their fill is only known once the batch has run,
     // and copying their whole capacity with every batch multiplied the D2H traffic of a window by ten
-    sl.d_corr = corr_cap ? dr.corrections : nullptr;
-    sl.d_ev = ev_cap ? dr.adapter_events : nullptr;
-    HIP_TRY(ctx, hipEventRecord(sl.done, st));
+    sl.d_corr = dr.corrections;
+    sl.d_ev = dr.adapter_events;
     sl.res = *res;
     sl.busy = true;
     return FASTP_GPU_OK;
@@ -3825,12 +3769,32 @@ static int finish_slot(fastp_gpu_ctx* ctx, fastp_gpu_ctx::AsyncSlot& sl) {
     return FASTP_GPU_OK;
 }
 
-extern "C" int fastp_gpu_wait(fastp_gpu_ctx* ctx, int slot) {
-    if (!ctx || slot < 0 || slot >= FASTP_GPU_ASYNC_SLOTS) return fail(ctx, FASTP_GPU_E_INVALID, "slot out of range");
-    fastp_gpu_ctx::AsyncSlot& sl = ctx->aslot[slot];
+static int wait_slot(fastp_gpu_ctx* ctx, fastp_gpu_ctx::AsyncSlot& sl) {
     if (!sl.busy) return FASTP_GPU_OK;
     HIP_TRY(ctx, hipEventSynchronize(sl.done));
     return finish_slot(ctx, sl);
+}
+
+extern "C" int fastp_gpu_submit_host(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, fastp_gpu_results* res) {
+    if (!ctx || !b || !res) return fail(ctx, FASTP_GPU_E_INVALID, "null argument");
+    if (b->n < 0) return fail(ctx, FASTP_GPU_E_INVALID, "negative batch size");
+    if (b->n == 0) { if (res->n_corrections) *res->n_corrections = 0; return FASTP_GPU_OK; }
+    fastp_gpu_ctx::AsyncSlot& sl = ctx->aslot[FASTP_GPU_ASYNC_SLOTS];   // the context's own slot
+    const int rc = submit_slot(ctx, b, res, sl);
+    return rc ? rc : wait_slot(ctx, sl);
+}
+
+extern "C" int fastp_gpu_submit_host_async(fastp_gpu_ctx* ctx, const fastp_gpu_batch* b, fastp_gpu_results* res, int slot) {
+    if (!ctx || !b || !res) return fail(ctx, FASTP_GPU_E_INVALID, "null argument");
+    if (slot < 0 || slot >= FASTP_GPU_ASYNC_SLOTS) return fail(ctx, FASTP_GPU_E_INVALID, "slot out of range");
+    if (b->n <= 0) return fail(ctx, FASTP_GPU_E_INVALID, "empty batch");
+    if (ctx->aslot[slot].busy) return fail(ctx, FASTP_GPU_E_INVALID, "slot still in flight: fastp_gpu_wait it first");
+    return submit_slot(ctx, b, res, ctx->aslot[slot]);
+}
+
+extern "C" int fastp_gpu_wait(fastp_gpu_ctx* ctx, int slot) {
+    if (!ctx || slot < 0 || slot >= FASTP_GPU_ASYNC_SLOTS) return fail(ctx, FASTP_GPU_E_INVALID, "slot out of range");
+    return wait_slot(ctx, ctx->aslot[slot]);
 }
 
 extern "C" int fastp_gpu_poll(fastp_gpu_ctx* ctx, int slot) {

@@ -554,6 +554,50 @@ class GpuEngine:
     def synchronize(self):
         self._check(self.lib.fastp_gpu_synchronize(self.h))
 
+    # ---- pipelined host submits (include/fastp_gpu.h "Pipelined host submits") ----
+    def host_alloc(self, nbytes: int) -> int:
+        """page-locked host memory (fastp_gpu_host_alloc): what the batches and result arrays of submit_host_async live in"""
+        fn = self.lib.fastp_gpu_host_alloc
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
+        p = C.c_void_p()
+        self._check(fn(self.h, nbytes, C.byref(p)))
+        return int(p.value)
+
+    def host_free(self, ptr: int):
+        fn = self.lib.fastp_gpu_host_free
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p]
+        self._check(fn(self.h, ptr))
+
+    @staticmethod
+    def host_view(ptr: int, shape, dtype) -> np.ndarray:
+        """a numpy array over memory of host_alloc (no copy; it must not outlive the allocation)"""
+        shape = tuple(np.atleast_1d(shape))
+        nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        return np.ctypeslib.as_array((C.c_uint8 * nbytes).from_address(ptr)).view(dtype).reshape(shape)
+
+    def submit_host_async(self, batch: abi.Batch, results: abi.Results, slot: int, check=True) -> int:
+        """queue one batch on `slot`; `batch`, `results` and what they point to stay untouched until the slot has been waited for"""
+        fn = self.lib.fastp_gpu_submit_host_async
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(abi.Batch), C.POINTER(abi.Results), C.c_int]
+        rc = fn(self.h, C.byref(batch), C.byref(results), slot)
+        if check:
+            self._check(rc)
+        return rc
+
+    def wait(self, slot: int, check=True) -> int:
+        fn = self.lib.fastp_gpu_wait
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int]
+        rc = fn(self.h, slot)
+        if check:
+            self._check(rc)
+        return rc
+
+    def poll(self, slot: int) -> int:
+        """1: the slot's batch has arrived (the slot is free), 0: still running, < 0: an error code"""
+        fn = self.lib.fastp_gpu_poll
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int]
+        return int(fn(self.h, slot))
+
     def reset(self):
         """a new run on the same context (fresh Stats / FilterResult / Duplicate)"""
         self._check(self.lib.fastp_gpu_reset(self.h))
