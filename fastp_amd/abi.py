@@ -209,6 +209,13 @@ N_OUTPUTS = 6  # FASTP_GPU_OUT1, OUT2, FAILED, MERGED, UNPAIRED1, UNPAIRED2
 N_ALL_OUTPUTS = 7  # ... and FASTP_GPU_OVERLAPPED (OUT_OVERLAPPED, --overlapped_out's stream): fastp_gpu_format_all_streams
 OUT_OVERLAPPED = 6   # FASTP_GPU_OVERLAPPED: the host glue's and fastp_gpu_format_all_streams' seventh stream
 OVOUT_HIT = 0x8000   # fastp_gpu_read_result.reserved of read 1 with overlapped_out
+PACK_SIZE = 1000     # the reference's PACK_SIZE: --split / --split_by_lines change files between two packs only
+
+
+class PackCuts(C.Structure):
+    """fastp_gpu_pack_cuts: cut = DEVICE u64 [2][max_packs + 1], passed = DEVICE u32 [max_packs]"""
+    _fields_ = [("first_unit", C.c_int64), ("pack_size", C.c_int32), ("max_packs", C.c_int32),
+                ("cut", C.c_void_p), ("passed", C.c_void_p)]
 
 
 class CounterLayout(C.Structure):

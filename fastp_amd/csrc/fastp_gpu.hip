@@ -392,6 +392,9 @@ struct fastp_gpu_ctx {
     u32* d_prefix = nullptr;                           // sharded runs: OR of the preceding shards' bitmaps
     bool has_prefix = false;
     bool host_overlapped = false;   // fastp_gpu_host_writes_overlapped: the caller assembles --overlapped_out's stream from the records
+    bool fmt_interleaved = false;   // fastp_gpu_format_interleaved: --stdout's one stream for a passing pair
+    bool cuts_armed = false;        // fastp_gpu_format_pack_cuts: the plan of the next format call
+    fastp_gpu_pack_cuts cuts = {};
     // overrepresentation analysis
     u32* d_ovr_table[2] = {nullptr, nullptr};
     u8* d_ovr_sym[2] = {nullptr, nullptr};
@@ -2294,6 +2297,25 @@ extern "C" int fastp_gpu_host_writes_overlapped(fastp_gpu_ctx* ctx, int on) {
     return FASTP_GPU_OK;
 }
 
+extern "C" int fastp_gpu_format_interleaved(fastp_gpu_ctx* ctx, int on) {
+    if (!ctx) return FASTP_GPU_E_INVALID;
+    if (!ctx->dp.paired) return fail(ctx, FASTP_GPU_E_INVALID, "interleaved output (--stdout) needs paired input: out1 is the stream of a single-end run");
+    if (ctx->dp.merge) return fail(ctx, FASTP_GPU_E_INVALID, "interleaved output (--stdout) in merge mode: the merged stream goes to standard output");
+    ctx->fmt_interleaved = on != 0;
+    return FASTP_GPU_OK;
+}
+
+extern "C" int fastp_gpu_format_pack_cuts(fastp_gpu_ctx* ctx, const fastp_gpu_pack_cuts* plan) {
+    if (!ctx) return FASTP_GPU_E_INVALID;
+    ctx->cuts_armed = false;
+    if (!plan) return FASTP_GPU_OK;
+    if (plan->first_unit < 0 || plan->pack_size < 1 || plan->max_packs < 1 || !plan->cut || !plan->passed)
+        return fail(ctx, FASTP_GPU_E_INVALID, "pack cuts: first_unit >= 0, pack_size >= 1, max_packs >= 1 and both device arrays are needed");
+    ctx->cuts = *plan;
+    ctx->cuts_armed = true;
+    return FASTP_GPU_OK;
+}
+
 extern "C" int fastp_gpu_phred64_to_33(fastp_gpu_ctx* ctx, int32_t n, uint8_t* text, const uint32_t* line_off, const uint32_t* line_len, uint8_t* qual_rows) {
     if (!ctx || n < 0) return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
     if (n == 0) return FASTP_GPU_OK;
@@ -2584,6 +2606,15 @@ static int format_streams_impl(fastp_gpu_ctx* ctx, const int ns, int32_t n, cons
                                const fastp_gpu_format_options* opts, uint8_t* const* out, const int64_t* out_capacity, int64_t* out_len) {
     if (!ctx || !m1 || !out || !out_capacity || !out_len || n < 0) return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
     for (int q = 0; q < ns; q++) out_len[q] = 0;
+    // fastp_gpu_format_pack_cuts arms one call: this one
+    const bool cuts_on = ctx->cuts_armed;
+    const fastp_gpu_pack_cuts cuts = ctx->cuts;
+    ctx->cuts_armed = false;
+    u32 slices = 0;
+    if (cuts_on) {
+        if (n > 0) slices = (u32)((cuts.first_unit + n - 1) / cuts.pack_size - cuts.first_unit / cuts.pack_size + 1);
+        if (slices > (u32)cuts.max_packs) return fail(ctx, FASTP_GPU_E_INVALID, "pack cuts: the call's units span more packs than max_packs");
+    }
     const bool paired = ctx->dp.paired != 0;
     if (paired != (m2 != nullptr)) return fail(ctx, FASTP_GPU_E_INVALID, "mate 2 must be given exactly for a paired engine");
     if (paired && !pair) return fail(ctx, FASTP_GPU_E_INVALID, "a paired engine needs the pair records");
@@ -2624,9 +2655,17 @@ static int format_streams_impl(fastp_gpu_ctx* ctx, const int ns, int32_t n, cons
             f.prefix_len = (u32)pl;
         }
     }
-    if (n == 0) return FASTP_GPU_OK;
+    f.interleaved = (paired && !f.merge && ctx->fmt_interleaved) ? 1 : 0;
+    if (n == 0) {
+        if (cuts_on) {   // the closing entry alone
+            HIP_TRY(ctx, hipSetDevice(ctx->device));
+            for (int q = 0; q < 2; q++) HIP_TRY(ctx, hipMemsetAsync(cuts.cut + (size_t)q * (cuts.max_packs + 1), 0, 8, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        return FASTP_GPU_OK;
+    }
     // the streams this configuration can write to need a buffer
-    const bool need[FMTS_ALL_STREAMS] = {true, paired, f.want_failed != 0, f.merge != 0, paired && f.want_u1, paired && f.want_u2, f.overlapped_out != 0};
+    const bool need[FMTS_ALL_STREAMS] = {true, paired && !f.interleaved, f.want_failed != 0, f.merge != 0, paired && f.want_u1, paired && f.want_u2, f.overlapped_out != 0};
     for (int q = 0; q < ns; q++) {
         if (out_capacity[q] < 0 || (need[q] && !out[q])) return fail(ctx, FASTP_GPU_E_INVALID, "null output buffer for a stream the options ask for");
         f.out[q] = out[q];
@@ -2652,6 +2691,14 @@ static int format_streams_impl(fastp_gpu_ctx* ctx, const int ns, int32_t n, cons
     f.pair = (const u32*)pair;
     f.corrections = (const u32*)corrections;
     f.n_corrections = n_corrections;
+    if (cuts_on) {   // (a single-end call never touches stream 1's offsets: they are zero)
+        f.cut[0] = cuts.cut;
+        f.cut[1] = cuts.cut + (size_t)cuts.max_packs + 1;
+        f.passed = cuts.passed;
+        f.first_unit = (u64)cuts.first_unit;
+        f.pack_size = (u32)cuts.pack_size;
+        HIP_TRY(ctx, hipMemsetAsync(f.passed, 0, (size_t)slices * 4, st));
+    }
     int32_t ncorr = 0;
     if (corrections && n_corrections) {
         HIP_TRY(ctx, hipMemcpyAsync(&ncorr, n_corrections, 4, hipMemcpyDeviceToHost, st));
@@ -3527,6 +3574,47 @@ extern "C" int fastp_gpu_eval_adapter_seed_x(fastp_gpu_ctx* ctx, const uint8_t* 
 // ---- output text -> BGZF-framed gzip members (fq_deflate.h) ------------------------------------------------
 // the reference's -z (1..9; 0 = the default) -> the match stage: levels up to 4 are the one-candidate greedy stage, 5..7 and 8..9
 // the chain stage at two depths (DESIGN.md 7 has the table and what each tier costs)
+// a round = what is in flight at once (a wavefront per block, eight per CU): the scratch is sized by it - 4 bytes of
+// tokens per input byte + a member slot per block - so a larger round only costs HBM.  table_entries: room for the block
+// table of fastp_gpu_deflate_bgzf_segments behind it (*d_table).
+static int deflate_scratch(fastp_gpu_ctx* ctx, int round, bool chain, int chain_grid, size_t table_entries, DeflateArgs& scratch,
+                           DefBlockEnt** d_table) {
+    memset(&scratch, 0, sizeof(scratch));
+    if (round <= 0) return 0;
+    auto lay = [&](Carve c) {
+        if (d_table) *d_table = c.take<DefBlockEnt>(table_entries * sizeof(DefBlockEnt), 16);   // (in front: its u64 fields stay aligned)
+        scratch.slots = c.take((size_t)round * DEF_SLOT);
+        scratch.tokens = c.take<u32>((size_t)round * DEF_BLOCK * 4);
+        scratch.sizes = c.take<u32>((size_t)round * 4 + 8);
+        scratch.offs = c.take<u64>(((size_t)round + 1) * 8);
+        if (chain) scratch.prev = c.take<u16>((size_t)chain_grid * DEF_PREV * 2);   // (a chain array per RESIDENT workgroup: 128 KB x 5 per CU)
+        return c.off;
+    };
+    int rc = ensure(ctx, (void**)&ctx->d_def, &ctx->def_cap, lay(Carve(nullptr)));
+    if (rc) return rc;
+    lay(Carve(ctx->d_def));
+    return 0;
+}
+// the three kernels of one round: members into their slots, their offsets, members to their place in the output
+static int deflate_launch_round(fastp_gpu_ctx* ctx, DeflateArgs& a, bool chain, int chain_grid, u32 chain_depth, u32 chain_lazy) {
+    hipStream_t st = ctx->stream;
+    if (chain) {
+        a.depth = chain_depth;
+        a.lazy_max = chain_lazy;
+        const int grid = std::min(a.nblocks, chain_grid);
+        hipLaunchKernelGGL(fq_deflate_chain_kernel, dim3(grid), dim3(64), sizeof(DefChainLds), st, a);
+    } else {
+        const int grid = std::min(a.nblocks, ctx->cus * std::max(1, ctx->lds_bytes / (int)sizeof(DefLds)));
+        hipLaunchKernelGGL(fq_deflate_kernel, dim3(grid), dim3(64), sizeof(DefLds), st, a);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(fq_deflate_scan_kernel, dim3(1), dim3(1024), 1024 * 8, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(fq_deflate_gather_kernel, dim3(std::min(a.nblocks, ctx->cus * 16)), dim3(256), 0, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
 extern "C" int fastp_gpu_deflate_bgzf_level(fastp_gpu_ctx* ctx, const uint8_t* text, int64_t nbytes, int write_eof, int level, uint8_t* out,
                                             int64_t out_capacity, int64_t* out_len) {
     if (!ctx || !out_len || nbytes < 0 || out_capacity < 0 || (nbytes > 0 && !text) || (out_capacity > 0 && !out))
@@ -3539,25 +3627,11 @@ extern "C" int fastp_gpu_deflate_bgzf_level(fastp_gpu_ctx* ctx, const uint8_t* t
     hipStream_t st = ctx->stream;
     static const uint8_t eof_member[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const int64_t total_blocks = (nbytes + DEF_BLOCK - 1) / DEF_BLOCK;
-    // a round = what is in flight at once (a wavefront per block, eight per CU): the scratch is sized by it - 4 bytes of
-    // tokens per input byte + a member slot per block - so a larger round only costs HBM
     const int round = (int)std::min<int64_t>(total_blocks, (int64_t)ctx->cus * 8);
     const int chain_grid = chain ? std::min(round, ctx->cus * std::max(1, ctx->lds_bytes / (int)sizeof(DefChainLds))) : 0;
     DeflateArgs scratch;
-    memset(&scratch, 0, sizeof(scratch));
-    if (round > 0) {
-        auto lay = [&](Carve c) {
-            scratch.slots = c.take((size_t)round * DEF_SLOT);
-            scratch.tokens = c.take<u32>((size_t)round * DEF_BLOCK * 4);
-            scratch.sizes = c.take<u32>((size_t)round * 4 + 8);
-            scratch.offs = c.take<u64>(((size_t)round + 1) * 8);
-            if (chain) scratch.prev = c.take<u16>((size_t)chain_grid * DEF_PREV * 2);   // (a chain array per RESIDENT workgroup: 128 KB x 5 per CU)
-            return c.off;
-        };
-        int rc = ensure(ctx, (void**)&ctx->d_def, &ctx->def_cap, lay(Carve(nullptr)));
-        if (rc) return rc;
-        lay(Carve(ctx->d_def));
-    }
+    int rc = deflate_scratch(ctx, round, chain, chain_grid, 0, scratch, nullptr);
+    if (rc) return rc;
     u64 written = 0;   // bytes needed so far
     for (int64_t b0 = 0; b0 < total_blocks; b0 += round) {
         DeflateArgs a = scratch;
@@ -3567,20 +3641,8 @@ extern "C" int fastp_gpu_deflate_bgzf_level(fastp_gpu_ctx* ctx, const uint8_t* t
         a.out = out;
         a.out_base = written;
         a.out_cap = (u64)out_capacity;
-        if (chain) {
-            a.depth = chain_depth;
-            a.lazy_max = chain_lazy;
-            const int grid = std::min(a.nblocks, chain_grid);
-            hipLaunchKernelGGL(fq_deflate_chain_kernel, dim3(grid), dim3(64), sizeof(DefChainLds), st, a);
-        } else {
-            const int grid = std::min(a.nblocks, ctx->cus * std::max(1, ctx->lds_bytes / (int)sizeof(DefLds)));
-            hipLaunchKernelGGL(fq_deflate_kernel, dim3(grid), dim3(64), sizeof(DefLds), st, a);
-        }
-        HIP_TRY(ctx, hipGetLastError());
-        hipLaunchKernelGGL(fq_deflate_scan_kernel, dim3(1), dim3(1024), 1024 * 8, st, a);
-        HIP_TRY(ctx, hipGetLastError());
-        hipLaunchKernelGGL(fq_deflate_gather_kernel, dim3(std::min(a.nblocks, ctx->cus * 16)), dim3(256), 0, st, a);
-        HIP_TRY(ctx, hipGetLastError());
+        rc = deflate_launch_round(ctx, a, chain, chain_grid, chain_depth, chain_lazy);
+        if (rc) return rc;
         u64 bytes = 0;
         HIP_TRY(ctx, hipMemcpyAsync(&bytes, a.offs + a.nblocks, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -3601,6 +3663,74 @@ extern "C" int fastp_gpu_deflate_bgzf_level(fastp_gpu_ctx* ctx, const uint8_t* t
 extern "C" int fastp_gpu_deflate_bgzf(fastp_gpu_ctx* ctx, const uint8_t* text, int64_t nbytes, int write_eof, uint8_t* out,
                                       int64_t out_capacity, int64_t* out_len) {
     return fastp_gpu_deflate_bgzf_level(ctx, text, nbytes, write_eof, 0, out, out_capacity, out_len);
+}
+
+// the same kernels with a block table: the blocks of every segment (DEF_BLOCK bytes from the segment's start on), the
+// end-of-file members written by the gather kernel behind the last block of a flagged segment.  The rounds run over the
+// table, whatever segment a block belongs to.
+extern "C" int fastp_gpu_deflate_bgzf_segments(fastp_gpu_ctx* ctx, const uint8_t* text, int32_t n_segments, const int64_t* seg_off,
+                                               const uint8_t* seg_eof, int level, uint8_t* out, int64_t out_capacity, int64_t* seg_out_off) {
+    if (!ctx || n_segments < 0 || !seg_off || !seg_out_off || out_capacity < 0 || (out_capacity > 0 && !out))
+        return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
+    if (level < 0 || level > 9) return fail(ctx, FASTP_GPU_E_INVALID, "compression level outside 0..9");
+    for (int32_t i = 0; i <= n_segments; i++) seg_out_off[i] = 0;
+    if (seg_off[0] < 0) return fail(ctx, FASTP_GPU_E_INVALID, "negative segment offset");
+    for (int32_t i = 0; i < n_segments; i++)
+        if (seg_off[i + 1] < seg_off[i]) return fail(ctx, FASTP_GPU_E_INVALID, "segment offsets must ascend");
+    if (n_segments > 0 && seg_off[n_segments] > seg_off[0] && !text) return fail(ctx, FASTP_GPU_E_INVALID, "bad argument");
+    const bool chain = level >= 5;
+    const u32 chain_depth = level >= 8 ? 16u : 4u, chain_lazy = 32u;
+    std::vector<DefBlockEnt> table;
+    std::vector<size_t> seg_first((size_t)n_segments + 1);   // a segment's first table entry
+    u64 eof_bytes = 0;
+    for (int32_t i = 0; i < n_segments; i++) {
+        seg_first[i] = table.size();
+        const bool eof = seg_eof && seg_eof[i];
+        for (int64_t at = seg_off[i]; at < seg_off[i + 1]; at += DEF_BLOCK)
+            table.push_back(DefBlockEnt{(u64)at, (u32)std::min<int64_t>(DEF_BLOCK, seg_off[i + 1] - at), 0u, eof_bytes});
+        if (eof) {
+            if (table.size() == seg_first[i]) table.push_back(DefBlockEnt{(u64)seg_off[i], 0u, 0u, eof_bytes});
+            table.back().eof = 1;
+            eof_bytes += 28;
+        }
+    }
+    seg_first[n_segments] = table.size();
+    const int64_t total_blocks = (int64_t)table.size();
+    if (total_blocks == 0) return FASTP_GPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int round = (int)std::min<int64_t>(total_blocks, (int64_t)ctx->cus * 8);
+    const int chain_grid = chain ? std::min(round, ctx->cus * std::max(1, ctx->lds_bytes / (int)sizeof(DefChainLds))) : 0;
+    DeflateArgs scratch;
+    DefBlockEnt* d_table = nullptr;
+    int rc = deflate_scratch(ctx, round, chain, chain_grid, table.size(), scratch, &d_table);
+    if (rc) return rc;
+    // (synchronous: `table` is pageable and dies with this call, whatever path it returns by)
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipMemcpy(d_table, table.data(), table.size() * sizeof(DefBlockEnt), hipMemcpyHostToDevice));
+    std::vector<u64> member_at(table.size() + 1);   // where each block's member starts, without the end-of-file members
+    std::vector<u64> offs((size_t)round + 1);
+    u64 written = 0;
+    for (int64_t b0 = 0; b0 < total_blocks; b0 += round) {
+        DeflateArgs a = scratch;
+        a.nblocks = (int)std::min<int64_t>(round, total_blocks - b0);
+        a.text = text;
+        a.table = d_table + b0;
+        a.out = out;
+        a.out_base = written;
+        a.out_cap = (u64)out_capacity;
+        rc = deflate_launch_round(ctx, a, chain, chain_grid, chain_depth, chain_lazy);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(offs.data(), a.offs, ((size_t)a.nblocks + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        for (int b = 0; b < a.nblocks; b++) member_at[(size_t)b0 + b] = written + offs[b];
+        written += offs[a.nblocks];
+    }
+    member_at[table.size()] = written;
+    for (int32_t i = 0; i < n_segments; i++) seg_out_off[i] = (int64_t)(member_at[seg_first[i]] + (seg_first[i] < table.size() ? table[seg_first[i]].shift : eof_bytes));
+    seg_out_off[n_segments] = (int64_t)(written + eof_bytes);
+    if (written + eof_bytes > (u64)out_capacity) return fail(ctx, FASTP_GPU_E_OVERFLOW, "output buffer too small (see seg_out_off[n_segments] for the needed size)");
+    return FASTP_GPU_OK;
 }
 
 extern "C" int fastp_gpu_device_alloc(fastp_gpu_ctx* ctx, int64_t bytes, void** dev_ptr) {

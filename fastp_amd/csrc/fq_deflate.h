@@ -34,9 +34,18 @@ enum {
     DEF_NLL = 288, DEF_ND = 32, DEF_NCL = 20
 };
 
+// fastp_gpu_deflate_bgzf_segments: the blocks of a round when they are not the text cut every DEF_BLOCK bytes
+struct DefBlockEnt {
+    u64 start;           // of the block in `text`
+    u32 len;             // <= DEF_BLOCK; 0: no member (an empty segment that still gets the end-of-file member)
+    u32 eof;             // bgzip's end-of-file member follows this block's member (the block ends a file)
+    u64 shift;           // bytes of the end-of-file members in front of this block's member, over the whole call
+};
+
 struct DeflateArgs {
     const u8* text;
     u64 nbytes;          // of this round
+    const DefBlockEnt* table;   // [nblocks] or null: block blk is text[blk * DEF_BLOCK, + DEF_BLOCK) cut at nbytes
     int nblocks;
     u8* slots;           // [nblocks][DEF_SLOT]
     u32* tokens;         // [nblocks][DEF_BLOCK]
@@ -578,8 +587,12 @@ template <class LDS> FQ_DEV u32 def_parse_chain(LDS& S, const u8* in, u32 n, u32
 }
 
 template <class LDS> FQ_DEV void deflate_block(const DeflateArgs& a, LDS& S, int blk, int lane) {
-    const u64 start = (u64)blk * DEF_BLOCK;
-    const u32 n = (u32)(a.nbytes - start < (u64)DEF_BLOCK ? a.nbytes - start : (u64)DEF_BLOCK);
+    const u64 start = a.table ? a.table[blk].start : (u64)blk * DEF_BLOCK;
+    const u32 n = a.table ? a.table[blk].len : (u32)(a.nbytes - start < (u64)DEF_BLOCK ? a.nbytes - start : (u64)DEF_BLOCK);
+    if (a.table && n == 0u) {   // (wave-uniform)
+        if (lane == 0) a.sizes[blk] = 0;
+        return;
+    }
     // (Staging the block's text in LDS was measured and dropped: 93 KB per block leaves one wavefront per CU, and a
     // single wavefront's time is set by instruction latency either way - 3.5 ms per block against 4.1 from global memory
     // with five blocks per CU in flight.)
@@ -794,7 +807,11 @@ FQ_DEV void deflate_scan_body(const DeflateArgs& a, u64* lds) {
 FQ_DEV void deflate_gather_body(const DeflateArgs& a) {
     for (int blk = block_id(); blk < a.nblocks; blk += grid_blocks()) {
         const u32 sz = a.sizes[blk];
-        const u64 at = a.out_base + a.offs[blk];
+        const u64 at = a.out_base + a.offs[blk] + (a.table ? a.table[blk].shift : 0ull);
+        if (a.table && a.table[blk].eof && at + sz + 28u <= a.out_cap && thread_id() < 28) {
+            const u8 eof_member[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+            a.out[at + sz + (u32)thread_id()] = eof_member[thread_id()];
+        }
         if (at + sz > a.out_cap) continue;   // the host reports the needed size
         const u8* src = a.slots + (size_t)blk * DEF_SLOT + 2;
         u8* dst = a.out + at;

@@ -4038,7 +4038,7 @@ FQ_DEV void fmts_route(const FmtsArgs& f, int g, u32 e[2]) {
     const bool wf = f.want_failed != 0;
     if (p1 && p2) {  // :577-594
         e[0] = fmts_em(0, 0, 0, 0);
-        e[1] = fmts_em(1, 1, 0, 0);
+        e[1] = fmts_em(f.interleaved ? 0 : 1, 1, 0, 0);   // --stdout (:577-585): read 2's record behind read 1's in one stream
     } else if (p1) {  // :595-605
         if (f.want_u1) {
             e[0] = fmts_em(4, 0, 0, 0);
@@ -4332,6 +4332,20 @@ FQ_DEV u32 fmts_put_mtag(u8* dst, u32 m1, u32 m2, int gl) {
     return 8u + d1 + 1u + d2;
 }
 
+// passed[slice] += the wave's units with an out1 record, one atomic per wave and slice.  Every lane of the wave calls it;
+// a wave touches at most two slices when pack_size >= 64, as many as it holds units when the packs are smaller.
+FQ_DEV void fmts_count_passed(const FmtsArgs& f, bool valid, u32 slice, bool pass) {
+    u64 todo = ballot(valid);
+    while (todo) {
+        const int leader = __builtin_ctzll(todo);
+        const u32 s = shfl(slice, leader);
+        const bool mine = valid && slice == s;
+        const u64 hits = ballot(mine && pass);
+        if (lane_id() == leader && hits) g_atomic_add_u32(&f.passed[s], (u32)popc64(hits));
+        todo &= ~ballot(mine);
+    }
+}
+
 template <int NS, int SLOTS>
 FQ_DEV void fmts_write_body(const FmtsArgs& f, u32* lds) {
     // lds: [NS][16 waves] wave sums, then per unit [SLOTS] u64 offsets of its emissions (block_threads * SLOTS * 2 dwords)
@@ -4352,6 +4366,14 @@ FQ_DEV void fmts_write_body(const FmtsArgs& f, u32* lds) {
                 fmts_rec<SLOTS>(f, g, e[k], names, r);
                 sz[k] = r.bytes;
             }
+    }
+    // fastp_gpu_format_pack_cuts: the slice of the call this unit lies in (units of one pack), and whether it starts it
+    u32 slice = 0;
+    bool slice_head = false;
+    if (f.cut[0] && g < f.n) {
+        const u64 gu = f.first_unit + (u64)g;
+        slice = (u32)(gu / f.pack_size - f.first_unit / f.pack_size);
+        slice_head = g == 0 || gu % f.pack_size == 0;
     }
     u64* eoff = (u64*)(lds + NS * 16);
     u64 off[SLOTS];
@@ -4378,6 +4400,7 @@ FQ_DEV void fmts_write_body(const FmtsArgs& f, u32* lds) {
         u64 base = f.blockbase[(size_t)q * f.nblocks + block_id()] + excl[q];
         for (int w = 0; w < nw; w++)
             if (w < wave) base += lds[q * 16 + w];
+        const u64 before = base;
         // a unit's emissions into one stream follow each other in slot order
 #pragma unroll
         for (int k = 0; k < SLOTS; k++)
@@ -4385,7 +4408,12 @@ FQ_DEV void fmts_write_body(const FmtsArgs& f, u32* lds) {
                 off[k] = base;
                 base += sz[k];
             }
+        if (q < 2 && f.cut[0] && g < f.n) {   // the pack table: the stream's offset where a slice starts, and where the call ends
+            if (slice_head) f.cut[q][slice] = before;
+            if (g == f.n - 1) f.cut[q][slice + 1u] = base;
+        }
     }
+    if (f.cut[0]) fmts_count_passed(f, g < f.n, slice, e[0] != FMTS_NONE && (e[0] & 7u) == 0u);
 #pragma unroll
     for (int k = 0; k < SLOTS; k++) eoff[SLOTS * tid + k] = off[k];
     block_sync();

@@ -164,11 +164,21 @@ struct ReadDone {
 };
 enum { SRC_PLAIN = 0, SRC_GZIP = 1, SRC_BGZF = 2 };
 struct WriteJob {
-    int oslot = -1;                // -1: stop; 3: only the host-built stream below (a trip whose device streams are all unwanted)
+    int oslot = -1;                // -1: stop; 3: only the host-built stream below (a trip whose device streams are all unwanted);
+                                   // 4: split outputs, behind the last trip: only `pieces` that finish files
     int64_t len[FASTP_GPU_N_HOST_OUTPUTS] = {0, 0, 0, 0, 0, 0, 0};   // ([FASTP_GPU_OVERLAPPED]: only when the device formats that stream)
     bool copy_pending = false;     // the device-to-host copy into pin_out[oslot] is in flight: wait for ev_out[oslot] first
     bool has_ov = false;           // --overlapped_out's records of this chunk, assembled on the host (may be empty: the writer takes one string per chunk)
     std::string ov;
+    // split outputs (fastp_gpu_stream_set_split): the trip's out1 / out2 bytes by file, in file order.  A trip's last piece may
+    // leave its file open; the job behind the last trip (oslot 4) only finishes files
+    struct Piece {
+        int32_t file = 0;              // 1-based
+        int64_t off[2] = {0, 0}, len[2] = {0, 0};   // in pin_out[oslot][q]
+        bool close = false;            // the file ends behind these bytes (compressed: the end-of-file member is among them)
+        bool finish = false;           // (oslot 4) no bytes: create the file if need be, end-of-file member if compressed, close
+    };
+    std::vector<Piece> pieces;
 };
 // the adapter strings of one chunk, in input order: entries [kind u8][len1 u16][len2 u16][bytes1][bytes2]
 struct ReplayJob {
@@ -253,6 +263,32 @@ struct fastp_gpu_stream {
     int32_t* h_counts = nullptr;   // pinned: n_corrections, n_adapter_events
     hipStream_t sx = nullptr, cp_in = nullptr;
     bool any_out = false;
+    bool il_out = false;           // --stdout of a paired run: out1 is the interleaved stream (fastp_gpu_stream_set_interleaved_output)
+    // --split / --split_by_lines (fastp_gpu_stream_set_split): the one worker's file state (threadconfig.cpp:127-157); it lives
+    // here, not in the context, so a re-plan and reads_to_process leave it alone
+    struct Split {
+        bool on = false, by_lines = false;
+        int64_t size = 0;
+        int32_t number = 0, digits = 0;
+        std::string out[2];
+        int64_t units = 0;             // global index of the next trip's unit 0
+        int32_t working = 0;           // mWorkingSplit
+        int64_t current = 0;           // mCurrentSplitReads
+        int64_t pack_units = 0, pack_passed = 0;   // of the pack a trip boundary cut in two
+        int32_t files = 1;             // opened per stream
+        int32_t max_packs = 0;
+        uint64_t* d_cut = nullptr;     // the formatter's pack table
+        uint32_t* d_passed = nullptr;
+        std::vector<uint64_t> cut;
+        std::vector<uint32_t> passed;
+        // after a pack: markProcessed; true = the next file was opened
+        bool pack_done() {
+            current += by_lines ? pack_passed : pack_units;
+            pack_units = pack_passed = 0;
+            if (current >= size && (by_lines || working + 1 < number)) { working++; files++; current = 0; return true; }
+            return false;
+        }
+    } split;
     int deflate_level = 0;         // of every compressed stream (fastp_gpu_stream_set_deflate_level, FASTP_GPU_STREAM_DEFLATE_LEVEL)
     bool started = false;          // fastp_gpu_stream_run was called: the level is fixed
 
@@ -311,6 +347,8 @@ void free_buffers(fastp_gpu_stream* s) {
     hfree(s->h_corr); hfree(s->h_ev); hfree(s->h_counts);
     s->h_corr = nullptr; s->h_ev = nullptr; s->h_counts = nullptr;
     for (int q = 0; q < FASTP_GPU_N_HOST_OUTPUTS; q++) free_output(s, q);
+    dfree(s->split.d_cut); dfree(s->split.d_passed);
+    s->split.d_cut = nullptr; s->split.d_passed = nullptr;
     for (int sl = 0; sl < 2; sl++)
         if (s->ev_out[sl]) { (void)hipEventDestroy(s->ev_out[sl]); s->ev_out[sl] = nullptr; }
     if (s->cp_out) { (void)hipStreamDestroy(s->cp_out); s->cp_out = nullptr; }
@@ -355,11 +393,12 @@ int alloc_outputs(fastp_gpu_stream* s) {
     const int64_t both = nf * s->text_cap + 2 * names + (int64_t)s->max_records * (96 + 2 * grow);   // every record of both mates + tags
     const int64_t one = s->text_cap + names + (int64_t)s->max_records * grow + 64;                   // out1 / out2: records only shrink, but for the name edit
     // (--overlapped_out's: parts of read 1's records with the UMI tag, fastp_gpu_format_all_streams' bound)
-    const int64_t caps[FASTP_GPU_N_HOST_OUTPUTS] = {one, one, both, both, both, both, one};
+    // (out1 as --stdout's interleaved stream: every record of both mates, fastp_gpu_format_interleaved's bound)
+    const int64_t caps[FASTP_GPU_N_HOST_OUTPUTS] = {s->il_out ? both : one, one, both, both, both, both, one};
     s->any_out = false;
     for (int q = 0; q < FASTP_GPU_N_HOST_OUTPUTS; q++) s->any_out = s->any_out || s->want[q];
     // the formatter wants a buffer for every stream the options can route to
-    const bool need[FASTP_GPU_N_HOST_OUTPUTS] = {true, s->paired, s->cfg.format.want_failed != 0, s->paired && s->p.merge,
+    const bool need[FASTP_GPU_N_HOST_OUTPUTS] = {true, s->paired && !s->il_out, s->cfg.format.want_failed != 0, s->paired && s->p.merge,
                                                  s->paired && s->cfg.format.want_unpaired1, s->paired && s->cfg.format.want_unpaired2, s->ov_device};
     for (int q = 0; q < FASTP_GPU_N_HOST_OUTPUTS; q++) {
         if (!s->any_out || !(need[q] || s->want[q]) || s->d_out[0][q]) continue;
@@ -371,7 +410,9 @@ int alloc_outputs(fastp_gpu_stream* s) {
         }
         int64_t host_bytes = caps[q];
         if (s->want[q] && s->compress[q]) {
-            s->gz_cap[q] = caps[q] + 31 * (caps[q] / 65280 + 1) + 64;
+            // (split outputs: a slice per pack of the trip, each with its own last member and maybe an end-of-file member -
+            // fastp_gpu_deflate_bgzf_segments' bound)
+            s->gz_cap[q] = caps[q] + 31 * (caps[q] / 65280 + 1) + 64 + (s->split.on ? (int64_t)(31 + 28) * (s->max_records / 1000 + 3) : 0);
             for (int sl = 0; sl < 2; sl++) S_HIP(s, hipMalloc((void**)&s->d_gz[sl][q], (size_t)s->gz_cap[q]));
             host_bytes = s->gz_cap[q];
         }
@@ -542,6 +583,7 @@ int replan(fastp_gpu_stream* s, int needed) {
         (void)hipFree(image);
         if (rc != FASTP_GPU_OK) return s->fail_ctx(rc, "fastp_gpu_dup_bitmap_import");
     }
+    if (s->il_out && fastp_gpu_format_interleaved(s->ctx, 1) != FASTP_GPU_OK) return s->fail_ctx(FASTP_GPU_E_HIP, "fastp_gpu_format_interleaved");
     if (fastp_gpu_stream_set_origin(s->ctx, s->st.units, post_reads) != FASTP_GPU_OK) return s->fail_ctx(FASTP_GPU_E_HIP, "fastp_gpu_stream_set_origin");
     if (s->census)
         for (int m = 0; m < 2; m++)
@@ -888,8 +930,68 @@ struct Run {
     Channel<int> q_ofree;
     Channel<ReplayJob> q_replay;
     int64_t out_pos[FASTP_GPU_N_HOST_OUTPUTS];
+    // split outputs, the writer thread's: the open file of each stream (ThreadConfig::initWriterForSplit)
+    int split_fd[2] = {-1, -1};
+    int32_t split_open = 0;            // its 1-based number, 0: none
+    int64_t split_pos[2] = {0, 0};
     explicit Run(fastp_gpu_stream* st) : s(st) {}
 };
+
+// dirname(out) / (num + "." + basename(out)), threadconfig.cpp:106-125
+std::string split_name(const std::string& out, int32_t file, int32_t digits) {
+    std::string num = std::to_string(file);
+    while ((int)num.size() < digits) num = "0" + num;
+    const size_t slash = out.rfind('/');
+    const size_t at = slash == std::string::npos ? 0 : slash + 1;
+    return out.substr(0, at) + num + "." + out.substr(at);
+}
+
+// the writer thread's side of a split job: pieces in file order; positional writes through the pool, files closed once the
+// pool has drained
+void write_split(Run* R, IoPool& pool, const WriteJob& j) {
+    fastp_gpu_stream* s = R->s;
+    const int ns = s->paired ? 2 : 1;
+    std::vector<int> to_close;
+    auto open_file = [&](int32_t file) {
+        if (R->split_open == file) return;
+        for (int q = 0; q < ns; q++) {
+            R->split_fd[q] = open(split_name(s->split.out[q], file, s->split.digits).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+            if (R->split_fd[q] < 0) R->io_err.store(3);
+            R->split_pos[q] = 0;
+        }
+        R->split_open = file;
+    };
+    auto put = [&](int q, const uint8_t* src, int64_t len) {
+        const int fd = R->split_fd[q];
+        if (len <= 0 || fd < 0) return;
+        const int64_t off = R->split_pos[q];
+        std::atomic<int>* err = &R->io_err;
+        pool.submit([fd, src, len, off, err] {
+            int64_t done = 0;
+            while (done < len) {
+                const ssize_t r = pwrite(fd, src + done, (size_t)(len - done), (off_t)(off + done));
+                if (r < 0 && errno == EINTR) continue;
+                if (r <= 0) { err->store(3); return; }
+                done += r;
+            }
+        });
+        R->split_pos[q] += len;
+        s->st.bytes_out[q] += len;
+    };
+    for (const WriteJob::Piece& pc : j.pieces) {
+        open_file(pc.file);
+        for (int q = 0; q < ns; q++) {
+            if (pc.finish) { if (s->compress[q]) put(q, BGZF_EOF, (int64_t)sizeof(BGZF_EOF)); }
+            else put(q, s->pin_out[j.oslot][q] + pc.off[q], pc.len[q]);
+        }
+        if (pc.close || pc.finish) {
+            for (int q = 0; q < ns; q++) { if (R->split_fd[q] >= 0) to_close.push_back(R->split_fd[q]); R->split_fd[q] = -1; }
+            R->split_open = 0;
+        }
+    }
+    pool.wait();
+    for (int fd : to_close) close(fd);
+}
 
 // a gzip stream that is not bgzip's: inflated on the host, member after member, as FastqReader::readToBufIgzip does
 // (src/fastqreader.cpp:88-149: a stream may hold several members; anything but a gzip header behind a member, or a
@@ -1161,6 +1263,12 @@ void writer_main(Run* R) {
         if (j.has_ov && !R->emit_err.load()) {   // --overlapped_out's records of the chunk, assembled on the host
             if (s->cfg.emit(s->cfg.user, FASTP_GPU_OVERLAPPED, j.ov.data(), (int64_t)j.ov.size()) != 0) R->emit_err.store(1);
             s->st.bytes_overlapped += (int64_t)j.ov.size();
+        }
+        if (s->split.on) {   // out1 / out2 by file; no other stream exists in this mode
+            write_split(R, pool, j);
+            s->st.write_s += now_s() - t0;
+            if (j.oslot < 2) R->q_ofree.put(j.oslot);
+            continue;
         }
         for (int q = 0; q < FASTP_GPU_N_HOST_OUTPUTS && j.oslot != 3; q++) {
             if (!s->want[q]) continue;
@@ -1504,15 +1612,86 @@ int run_loop(Run* R) {
                 uint8_t* const* d_out = s->d_out[wj.oslot];
                 int64_t lens[FASTP_GPU_N_HOST_OUTPUTS] = {};
                 const auto format = s->ov_device ? fastp_gpu_format_all_streams : fastp_gpu_format_streams;   // (seven entries or six of the same arrays)
+                if (s->split.on) {   // the pack table of this trip: where out1 / out2 may change files
+                    fastp_gpu_pack_cuts plan;
+                    plan.first_unit = s->split.units;
+                    plan.pack_size = 1000;   // PACK_SIZE, src/common.h:30
+                    plan.max_packs = s->split.max_packs;
+                    plan.cut = s->split.d_cut;
+                    plan.passed = s->split.d_passed;
+                    if (fastp_gpu_format_pack_cuts(s->ctx, &plan) != FASTP_GPU_OK) return s->fail_ctx(FASTP_GPU_E_HIP, "fastp_gpu_format_pack_cuts");
+                }
                 if (format(s->ctx, n, &io[0], s->paired ? &io[1] : nullptr, s->d_pair, s->d_corr, s->corr_cap ? s->d_nc : nullptr, &fo,
                            const_cast<uint8_t**>(d_out), s->out_cap, lens) != FASTP_GPU_OK)
                     return s->fail_ctx(FASTP_GPU_E_HIP, s->ov_device ? "fastp_gpu_format_all_streams" : "fastp_gpu_format_streams");
+                // split outputs: the one worker's state machine over the trip's packs -> the pieces of out1 / out2 by file, as
+                // ranges of table entries [e0, e1)
+                std::vector<std::pair<size_t, size_t>> ranges;
+                if (s->split.on) {
+                    fastp_gpu_stream::Split& sp = s->split;
+                    const size_t row = (size_t)sp.max_packs + 1;
+                    S_HIP(s, hipMemcpy(sp.cut.data(), sp.d_cut, 2 * row * 8, hipMemcpyDeviceToHost));
+                    S_HIP(s, hipMemcpy(sp.passed.data(), sp.d_passed, (size_t)sp.max_packs * 4, hipMemcpyDeviceToHost));
+                    size_t begin = 0, i = 0;
+                    for (int64_t u = sp.units; u < sp.units + n; i++) {
+                        const int64_t end = std::min<int64_t>(sp.units + n, (u / 1000 + 1) * 1000);
+                        sp.pack_units += end - u;
+                        sp.pack_passed += sp.passed[i];
+                        u = end;
+                        if (end % 1000 != 0) break;   // the pack goes on in the next trip (or is the input's last)
+                        const int32_t file = sp.working + 1;
+                        if (!sp.pack_done()) continue;
+                        WriteJob::Piece pc;
+                        pc.file = file;
+                        pc.close = true;
+                        wj.pieces.push_back(pc);
+                        ranges.emplace_back(begin, i + 1);
+                        begin = i + 1;
+                    }
+                    const size_t slices = n > 0 ? (size_t)((sp.units + n - 1) / 1000 - sp.units / 1000 + 1) : 0;
+                    if (begin < slices) {
+                        WriteJob::Piece pc;
+                        pc.file = sp.working + 1;
+                        wj.pieces.push_back(pc);
+                        ranges.emplace_back(begin, slices);
+                    }
+                    sp.units += n;
+                }
                 s->st.format_s += now_s() - t0;
                 t0 = now_s();
                 const uint8_t* src[FASTP_GPU_N_HOST_OUTPUTS];
                 for (int q = 0; q < FASTP_GPU_N_HOST_OUTPUTS; q++) {
                     src[q] = d_out[q];
                     if (!s->want[q]) { lens[q] = 0; continue; }
+                    if (s->split.on) {   // (q is out1 or out2)
+                        const uint64_t* cut = s->split.cut.data() + (size_t)q * ((size_t)s->split.max_packs + 1);
+                        const size_t np = ranges.size();
+                        if (!s->compress[q]) {
+                            for (size_t k = 0; k < np; k++) {
+                                wj.pieces[k].off[q] = (int64_t)cut[ranges[k].first];
+                                wj.pieces[k].len[q] = (int64_t)(cut[ranges[k].second] - cut[ranges[k].first]);
+                            }
+                            continue;
+                        }
+                        // one call for the whole trip: a segment per piece, the end-of-file member behind a file that ends
+                        std::vector<int64_t> seg_off(np + 1, 0), seg_out(np + 1, 0);
+                        std::vector<uint8_t> seg_eof(np + 1, 0);
+                        for (size_t k = 0; k < np; k++) {
+                            seg_off[k] = (int64_t)cut[ranges[k].first];
+                            seg_off[k + 1] = (int64_t)cut[ranges[k].second];
+                            seg_eof[k] = wj.pieces[k].close ? 1 : 0;
+                        }
+                        if (fastp_gpu_deflate_bgzf_segments(s->ctx, d_out[q], (int32_t)np, seg_off.data(), seg_eof.data(), s->deflate_level,
+                                                            s->d_gz[wj.oslot][q], s->gz_cap[q], seg_out.data()) != FASTP_GPU_OK)
+                            return s->fail_ctx(FASTP_GPU_E_HIP, "fastp_gpu_deflate_bgzf_segments");
+                        for (size_t k = 0; k < np; k++) {
+                            wj.pieces[k].off[q] = seg_out[k];
+                            wj.pieces[k].len[q] = seg_out[k + 1] - seg_out[k];
+                        }
+                        lens[q] = seg_out[np];
+                        src[q] = s->d_gz[wj.oslot][q];
+                        continue;
+                    }
                     if (s->compress[q] && lens[q] > 0) {
                         int64_t glen = 0;
                         if (fastp_gpu_deflate_bgzf_level(s->ctx, d_out[q], lens[q], 0, s->deflate_level, s->d_gz[wj.oslot][q], s->gz_cap[q], &glen) != FASTP_GPU_OK)
@@ -1631,6 +1810,56 @@ extern "C" int fastp_gpu_stream_set_overlapped_output(fastp_gpu_stream* s, int o
     return FASTP_GPU_OK;
 }
 
+extern "C" int fastp_gpu_stream_set_interleaved_output(fastp_gpu_stream* s, int on) {
+    if (!s || !s->ctx) return FASTP_GPU_E_INVALID;
+    if (s->started) return s->fail(FASTP_GPU_E_INVALID, "interleaved output (--stdout) is chosen before fastp_gpu_stream_run");
+    if (!s->paired) return s->fail(FASTP_GPU_E_INVALID, "interleaved output (--stdout) needs paired input: out1 is the stream of a single-end run");
+    if (s->p.merge) return s->fail(FASTP_GPU_E_INVALID, "interleaved output (--stdout) in merge mode: the merged stream goes to standard output");
+    if (s->split.on) return s->fail(FASTP_GPU_E_INVALID, "interleaved output (--stdout) cannot be combined with --split");
+    if (!s->want[FASTP_GPU_OUT1] || s->want[FASTP_GPU_OUT2])
+        return s->fail(FASTP_GPU_E_INVALID, "interleaved output (--stdout) needs want[OUT1] and no want[OUT2]: there is no out2");
+    if ((on != 0) == s->il_out) return FASTP_GPU_OK;
+    s->il_out = on != 0;
+    (void)hipSetDevice(s->cfg.device);
+    free_output(s, FASTP_GPU_OUT1);   // (sized for one mate at create; run() allocates for what is set now)
+    return FASTP_GPU_OK;
+}
+
+extern "C" int fastp_gpu_stream_set_split(fastp_gpu_stream* s, const fastp_gpu_stream_split* split) {
+    if (!s || !s->ctx) return FASTP_GPU_E_INVALID;
+    if (s->started) return s->fail(FASTP_GPU_E_INVALID, "--split is chosen before fastp_gpu_stream_run");
+    if (!split) return s->fail(FASTP_GPU_E_INVALID, "--split: null argument");
+    if (s->paired && s->p.merge) return s->fail(FASTP_GPU_E_INVALID, "--split cannot be combined with --merge");
+    if (s->il_out) return s->fail(FASTP_GPU_E_INVALID, "--split cannot be combined with interleaved output (--stdout)");
+    static const char* const other[] = {"--failed_out", "--merged_out", "--unpaired1", "--unpaired2", "--overlapped_out"};
+    for (int q = FASTP_GPU_FAILED; q < FASTP_GPU_N_HOST_OUTPUTS; q++)
+        if (s->want[q] || (q == FASTP_GPU_OVERLAPPED && s->cfg.want_overlapped))
+            return s->fail(FASTP_GPU_E_INVALID, std::string("--split writes out1 / out2 only: the reference drops ") + other[q - FASTP_GPU_FAILED] + " in this mode");
+    if (s->want[FASTP_GPU_OUT1] || s->want[FASTP_GPU_OUT2])
+        return s->fail(FASTP_GPU_E_INVALID, "--split: the stream is created with want[OUT1] = want[OUT2] = 0, the files are named here");
+    if (split->reads_per_file < 1) return s->fail(FASTP_GPU_E_INVALID, "--split / --split_by_lines: reads_per_file below 1");
+    if (!split->by_lines && (split->number < 2 || split->number > 999)) return s->fail(FASTP_GPU_E_INVALID, "--split: number outside 2..999");
+    if (split->digits < 0 || split->digits > 10) return s->fail(FASTP_GPU_E_INVALID, "--split_prefix_digits outside 0..10");
+    if (!split->out1 || !*split->out1) return s->fail(FASTP_GPU_E_INVALID, "--split: out1 is missing");
+    if (s->paired && (!split->out2 || !*split->out2)) return s->fail(FASTP_GPU_E_INVALID, "--split: out2 is missing on a paired stream");
+    fastp_gpu_stream::Split& sp = s->split;
+    sp.on = true;
+    sp.by_lines = split->by_lines != 0;
+    sp.size = split->reads_per_file;
+    sp.number = sp.by_lines ? 0 : split->number;
+    sp.digits = split->digits;
+    sp.out[0] = split->out1;
+    sp.out[1] = s->paired ? split->out2 : "";
+    s->want[FASTP_GPU_OUT1] = 1;
+    s->want[FASTP_GPU_OUT2] = s->paired ? 1 : 0;
+    (void)hipSetDevice(s->cfg.device);
+    free_output(s, FASTP_GPU_OUT1);
+    free_output(s, FASTP_GPU_OUT2);
+    return FASTP_GPU_OK;
+}
+
+extern "C" int32_t fastp_gpu_stream_split_files(const fastp_gpu_stream* s) { return s && s->split.on ? s->split.files : 0; }
+
 extern "C" int fastp_gpu_stream_overlapped_on_device(const fastp_gpu_stream* s) { return s && s->ov_device ? 1 : 0; }
 
 extern "C" int fastp_gpu_stream_set_adapter_census(fastp_gpu_stream* s, int on) {
@@ -1660,10 +1889,19 @@ extern "C" int fastp_gpu_stream_adapter_entry(fastp_gpu_stream* s, int is_r2, in
 extern "C" int fastp_gpu_stream_run(fastp_gpu_stream* s) {
     if (!s || !s->ctx) return FASTP_GPU_E_INVALID;
     s->started = true;
-    if (s->ov_device) {   // the seventh stream's buffers (and, when it is the only stream wanted, the ones the formatter needs)
+    if (s->ov_device || s->il_out || s->split.on) {   // the buffers of what the setters chose (the seventh stream; out1 at both mates' bound; the split outputs)
         S_HIP(s, hipSetDevice(s->cfg.device));
         const int rc = alloc_outputs(s);
         if (rc) return rc;
+    }
+    if (s->il_out && fastp_gpu_format_interleaved(s->ctx, 1) != FASTP_GPU_OK) return s->fail_ctx(FASTP_GPU_E_INVALID, "fastp_gpu_format_interleaved");
+    if (s->split.on && !s->split.d_cut) {
+        fastp_gpu_stream::Split& sp = s->split;
+        sp.max_packs = s->max_records / 1000 + 2;   // a trip holds at most max_records units
+        S_HIP(s, hipMalloc((void**)&sp.d_cut, 2 * ((size_t)sp.max_packs + 1) * 8));
+        S_HIP(s, hipMalloc((void**)&sp.d_passed, (size_t)sp.max_packs * 4));
+        sp.cut.assign(2 * ((size_t)sp.max_packs + 1), 0);
+        sp.passed.assign((size_t)sp.max_packs, 0);
     }
     const double t_start = now_s();
     fq::timeline("stream: run begin");
@@ -1685,7 +1923,24 @@ extern "C" int fastp_gpu_stream_run(fastp_gpu_stream* s) {
     R.q_ofree.put(1);
     std::thread reader(reader_main, &R), writer(writer_main, &R), replayer(replay_main, &R);
     int rc = run_loop(&R);
-    if (rc == FASTP_GPU_OK) {   // bgzip's empty last member ends every compressed stream
+    if (rc == FASTP_GPU_OK && s->split.on) {
+        // the input's last pack, short or empty (it may open one more file), then by-number mode's files that were never
+        // reached (ThreadConfig::writeEmptyFilesForSplitting); every file still to be finished gets a piece
+        fastp_gpu_stream::Split& sp = s->split;
+        WriteJob fin;
+        fin.oslot = 4;
+        auto finish = [&](int32_t file) {
+            WriteJob::Piece pc;
+            pc.file = file;
+            pc.finish = true;
+            fin.pieces.push_back(pc);
+        };
+        finish(sp.working + 1);
+        if (sp.pack_done()) finish(sp.working + 1);
+        while (!sp.by_lines && sp.working + 1 < sp.number) { sp.working++; sp.files++; finish(sp.working + 1); }
+        R.q_write.put(std::move(fin));
+    }
+    if (rc == FASTP_GPU_OK && !s->split.on) {   // bgzip's empty last member ends every compressed stream
         WriteJob eofs;
         eofs.oslot = 2;
         bool any = false;
@@ -1704,6 +1959,7 @@ extern "C" int fastp_gpu_stream_run(fastp_gpu_stream* s) {
     writer.join();
     replayer.join();
     for (int m = 0; m < s->nf; m++) close(R.fds[m]);
+    for (int q = 0; q < 2; q++) if (R.split_fd[q] >= 0) close(R.split_fd[q]);   // (a run that failed half way)
     if (rc == FASTP_GPU_OK && s->census)   // the maps as the census holds them: the accessors', and the caller's host object's
         for (int m = 0; m < 2 && rc == FASTP_GPU_OK; m++) {
             rc = census_fetch(s, m, &s->cmap[m]);

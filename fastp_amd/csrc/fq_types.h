@@ -325,6 +325,13 @@ struct FmtsArgs {
     const u32* corrections;  // fastp_gpu_correction, 2 dwords each
     const int* n_corrections;
     int corr_first;
+    int interleaved;         // fastp_gpu_format_interleaved: a passing pair's read 2 record follows read 1's in stream 0
+    // fastp_gpu_format_pack_cuts (cut[0] null: off): the write kernel leaves the byte offsets of out1 / out2 at the start of
+    // every slice of units that lie in one pack, and the slice's count of units with an out1 record
+    u64* cut[2];             // [slices + 1] per stream
+    u32* passed;             // [slices], zeroed by the host before the launch
+    u64 first_unit;          // global index of unit 0
+    u32 pack_size;
 };
 
 struct KernelArgs {

@@ -17,7 +17,7 @@ _LIBS: dict[str, C.CDLL] = {}
 EXPORTS = [
     "fastp_gpu_default_params", "fastp_gpu_seq_stride", "fastp_gpu_qual_stride", "fastp_gpu_cycles_for",
     "fastp_gpu_counter_layout_for", "fastp_gpu_counter_layout_for_params", "fastp_gpu_create", "fastp_gpu_destroy", "fastp_gpu_last_error",
-    "fastp_gpu_pack_reads", "fastp_gpu_pack_reads_x", "fastp_gpu_bgzf_index", "fastp_gpu_inflate_bgzf", "fastp_gpu_parse_fastq", "fastp_gpu_parse_exotic", "fastp_gpu_phred64_to_33", "fastp_gpu_host_writes_overlapped", "fastp_gpu_format_fastq", "fastp_gpu_format_streams", "fastp_gpu_format_all_streams", "fastp_gpu_deflate_bgzf", "fastp_gpu_deflate_bgzf_level", "fastp_gpu_adapter_census", "fastp_gpu_adapter_census_size", "fastp_gpu_adapter_census_read", "fastp_gpu_adapter_census_load", "fastp_gpu_device_alloc", "fastp_gpu_device_free", "fastp_gpu_device_upload", "fastp_gpu_device_download", "fastp_gpu_eval_seq_len", "fastp_gpu_eval_adapter_kmers", "fastp_gpu_eval_overrep", "fastp_gpu_eval_known_adapters", "fastp_gpu_eval_adapter_seed", "fastp_gpu_eval_adapter_kmers_x", "fastp_gpu_eval_overrep_x", "fastp_gpu_eval_known_adapters_x", "fastp_gpu_eval_adapter_seed_x", "fastp_gpu_submit_host", "fastp_gpu_submit_device", "fastp_gpu_synchronize",
+    "fastp_gpu_pack_reads", "fastp_gpu_pack_reads_x", "fastp_gpu_bgzf_index", "fastp_gpu_inflate_bgzf", "fastp_gpu_parse_fastq", "fastp_gpu_parse_exotic", "fastp_gpu_phred64_to_33", "fastp_gpu_host_writes_overlapped", "fastp_gpu_format_fastq", "fastp_gpu_format_streams", "fastp_gpu_format_all_streams", "fastp_gpu_format_interleaved", "fastp_gpu_format_pack_cuts", "fastp_gpu_deflate_bgzf", "fastp_gpu_deflate_bgzf_level", "fastp_gpu_deflate_bgzf_segments", "fastp_gpu_adapter_census", "fastp_gpu_adapter_census_size", "fastp_gpu_adapter_census_read", "fastp_gpu_adapter_census_load", "fastp_gpu_device_alloc", "fastp_gpu_device_free", "fastp_gpu_device_upload", "fastp_gpu_device_download", "fastp_gpu_eval_seq_len", "fastp_gpu_eval_adapter_kmers", "fastp_gpu_eval_overrep", "fastp_gpu_eval_known_adapters", "fastp_gpu_eval_adapter_seed", "fastp_gpu_eval_adapter_kmers_x", "fastp_gpu_eval_overrep_x", "fastp_gpu_eval_known_adapters_x", "fastp_gpu_eval_adapter_seed_x", "fastp_gpu_submit_host", "fastp_gpu_submit_device", "fastp_gpu_synchronize",
     "fastp_gpu_counters_device", "fastp_gpu_counters", "fastp_gpu_kernel_time",
     "fastp_gpu_counters_export", "fastp_gpu_counters_import",
     "fastp_gpu_dup_scan_bytes", "fastp_gpu_submit_pass1_device", "fastp_gpu_dup_bitmap_bytes", "fastp_gpu_dup_bitmap_export",
@@ -31,7 +31,7 @@ EXPORTS = [
     "fastp_gpu_host_adapter_entries", "fastp_gpu_host_adapter_entry", "fastp_gpu_host_add_adapter", "fastp_gpu_host_add_adapter_pair", "fastp_gpu_host_set_adapter_entries",
     # include/fastp_gpu_stream.h
     "fastp_gpu_stream_create", "fastp_gpu_stream_run", "fastp_gpu_stream_layout", "fastp_gpu_stream_counters", "fastp_gpu_stream_get_stats",
-    "fastp_gpu_stream_last_error", "fastp_gpu_stream_destroy", "fastp_gpu_stream_set_deflate_level", "fastp_gpu_stream_set_overlapped_output", "fastp_gpu_stream_overlapped_on_device", "fastp_gpu_stream_set_adapter_census", "fastp_gpu_stream_adapter_entries", "fastp_gpu_stream_adapter_entry", "fastp_gpu_stream_gunzip_file", "fastp_gpu_stream_gunzip_file_mt",
+    "fastp_gpu_stream_last_error", "fastp_gpu_stream_destroy", "fastp_gpu_stream_set_deflate_level", "fastp_gpu_stream_set_overlapped_output", "fastp_gpu_stream_overlapped_on_device", "fastp_gpu_stream_set_adapter_census", "fastp_gpu_stream_set_interleaved_output", "fastp_gpu_stream_set_split", "fastp_gpu_stream_split_files", "fastp_gpu_stream_adapter_entries", "fastp_gpu_stream_adapter_entry", "fastp_gpu_stream_gunzip_file", "fastp_gpu_stream_gunzip_file_mt",
 ]
 
 
@@ -379,6 +379,44 @@ class GpuEngine:
         if check:
             self._check(rc)
         return rc, int(n.value)
+
+    def format_interleaved(self, on=True, check=True):
+        """--stdout's stream of a paired run: a passing pair's two records go to out1, out2 gets nothing
+        (fastp_gpu_format_interleaved).  Returns rc"""
+        fn = self.lib.fastp_gpu_format_interleaved
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int]
+        rc = fn(self.h, int(bool(on)))
+        if check:
+            self._check(rc)
+        return rc
+
+    def format_pack_cuts(self, plan: abi.PackCuts | None, check=True):
+        """arm the next format_streams / format_all_streams call with a pack table (fastp_gpu_format_pack_cuts);
+        None disarms.  Returns rc"""
+        fn = self.lib.fastp_gpu_format_pack_cuts
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.PackCuts)]
+        rc = fn(self.h, C.byref(plan) if plan is not None else None)
+        if check:
+            self._check(rc)
+        return rc
+
+    def deflate_bgzf_segments(self, text_ptr, seg_off, seg_eof, level, out_ptr, out_capacity, check=True):
+        """device text cut at seg_off (host list of n + 1 ascending offsets) -> BGZF members that never span a cut
+        (fastp_gpu_deflate_bgzf_segments); seg_eof: host list of n flags or None.  Returns (rc, [n + 1 output offsets])"""
+        fn = self.lib.fastp_gpu_deflate_bgzf_segments
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                       C.POINTER(C.c_int64)]
+        n = len(seg_off) - 1
+        offs = (C.c_int64 * (n + 1))(*[int(x) for x in seg_off])
+        eof = (C.c_uint8 * max(n, 1))(*[1 if x else 0 for x in seg_eof]) if seg_eof is not None else None
+        out_off = (C.c_int64 * (n + 1))()
+        rc = fn(self.h, text_ptr, n, offs, eof, int(level), out_ptr, out_capacity, out_off)
+        if check:
+            self._check(rc)
+        return rc, [int(x) for x in out_off]
 
     # ---- FilterResult's adapter-string maps on the device (csrc/fq_census.h) ----
     def adapter_census(self, n, m1: abi.FormatIn, m2, corrections_ptr, n_corrections_ptr, corrections_capacity,

@@ -154,8 +154,23 @@ class FastqPipeline:
                     item = q_out.get()
                     if item is None:
                         return
-                    slot, lens = item
+                    slot, lens = item[0], item[1]
                     futs = []
+                    closing = []
+                    for file_no, close, spans in (item[2] if len(item) > 2 else ()):   # split outputs: the trip's pieces by file
+                        sw = self._split_w
+                        if sw["open"] != file_no:
+                            self._split_open(file_no)
+                        for q, (off, ln) in enumerate(spans):
+                            if sw["fd"][q] < 0 or not ln:
+                                continue
+                            mv = memoryview(self.stage_out[slot][q].numpy())[off:off + ln]
+                            for a in range(0, ln, self.IO_PIECE):
+                                futs.append(pool.submit(piece, sw["fd"][q], mv[a:min(ln, a + self.IO_PIECE)], sw["pos"][q] + a))
+                            sw["pos"][q] += ln
+                        if close:
+                            closing += [fd for fd in sw["fd"] if fd >= 0]
+                            sw["fd"], sw["open"] = [-1, -1], 0
                     for m in range(len(files)):
                         if files[m] is None or not lens[m]:
                             continue
@@ -166,9 +181,83 @@ class FastqPipeline:
                         pos[m] += lens[m]
                     for fu in futs:
                         fu.result()
+                    for fd in closing:
+                        os.close(fd)
                     q_done.put(slot)
         except Exception as e:
             q_done.put(e)
+
+    # ---- --split / --split_by_lines: the one worker's file state (src/threadconfig.cpp:106-157), as fq_stream.cpp keeps it ----
+    @staticmethod
+    def split_name(out: str, file_no: int, digits: int) -> str:
+        """dirname(out) / (number, zero-padded to `digits`) + "." + basename(out)"""
+        import os
+        d, b = os.path.split(out)
+        return os.path.join(d, str(file_no).rjust(digits, "0") + "." + b)
+
+    def _split_open(self, file_no):
+        import os
+        sp, sw = self._split, self._split_w
+        for q, out in enumerate(sp["out"]):
+            sw["fd"][q] = os.open(self.split_name(out, file_no, sp["digits"]), os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+            sw["pos"][q] = 0
+        sw["open"] = file_no
+
+    def _split_pack_done(self):
+        """ThreadConfig::markProcessed after a pack; True = the next file was opened"""
+        sp = self._split
+        sp["current"] += sp["pack_passed"] if sp["by_lines"] else sp["pack_units"]
+        sp["pack_units"] = sp["pack_passed"] = 0
+        if sp["current"] >= sp["size"] and (sp["by_lines"] or sp["working"] + 1 < sp["number"]):
+            sp["working"] += 1
+            sp["files"] += 1
+            sp["current"] = 0
+            return True
+        return False
+
+    def _split_pieces(self, n, passed):
+        """the trip's packs through the state machine: [(file, closes, first table entry, entry behind the last)]"""
+        sp = self._split
+        pieces, begin, i, u, end_all = [], 0, 0, sp["units"], sp["units"] + n
+        while u < end_all:
+            end = min(end_all, (u // abi.PACK_SIZE + 1) * abi.PACK_SIZE)
+            sp["pack_units"] += end - u
+            sp["pack_passed"] += int(passed[i])
+            u, i = end, i + 1
+            if end % abi.PACK_SIZE:
+                break                      # the pack goes on in the next trip (or is the input's last)
+            file_no = sp["working"] + 1
+            if self._split_pack_done():
+                pieces.append((file_no, True, begin, i))
+                begin = i
+        slices = (end_all - 1) // abi.PACK_SIZE - sp["units"] // abi.PACK_SIZE + 1
+        if begin < slices:
+            pieces.append((sp["working"] + 1, False, begin, slices))
+        sp["units"] = end_all
+        return pieces
+
+    def _split_finish(self):
+        """behind the last trip: the input's last pack (short or empty; it may open one more file), by-number mode's files that
+        were never reached (writeEmptyFilesForSplitting); every file still open or never created is finished"""
+        import os
+        sp, sw = self._split, self._split_w
+        todo = [sp["working"] + 1]
+        if self._split_pack_done():
+            todo.append(sp["working"] + 1)
+        while not sp["by_lines"] and sp["working"] + 1 < sp["number"]:
+            sp["working"] += 1
+            sp["files"] += 1
+            todo.append(sp["working"] + 1)
+        for file_no in todo:
+            if sw["open"] != file_no:
+                self._split_open(file_no)
+            for q, fd in enumerate(sw["fd"]):
+                if fd < 0:
+                    continue
+                if self.gz_out[q]:
+                    os.pwrite(fd, self.EOF_MEMBER, sw["pos"][q])
+                os.close(fd)
+            sw["fd"], sw["open"] = [-1, -1], 0
 
     @staticmethod
     def is_bgzf(path: str) -> bool:
@@ -222,7 +311,7 @@ class FastqPipeline:
 
     EOF_MEMBER = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")   # bgzip's empty last member
 
-    def _setup_outputs(self, paths, umi=None, fix_mgi_id=False):
+    def _setup_outputs(self, paths, umi=None, fix_mgi_id=False, interleaved=False, split=False):
         """device + pinned buffers for the streams that are written; paths[q] per abi stream index"""
         torch = self.torch
         nm = len(self.mates)
@@ -243,7 +332,8 @@ class FastqPipeline:
         both = nm * self.text_cap + 2 * names + self.max_records * (96 + 2 * grow)   # every record of both mates + tags
         one = self.text_cap + names + self.max_records * (64 + grow)
         # --overlapped_out's stream: parts of read 1's records + the name edit (fastp_gpu_format_all_streams' bound)
-        caps = [one, one, both, both, both, both, self.text_cap + names + self.max_records * grow]
+        # (out1 as --stdout's interleaved stream holds both mates' records: fastp_gpu_format_interleaved's bound)
+        caps = [both if interleaved else one, one, both, both, both, both, self.text_cap + names + self.max_records * grow]
         self.out_cap = [0] * abi.N_ALL_OUTPUTS
         self.gz_out = [bool(p) and p.endswith(".gz") for p in paths]
         for q in range(abi.N_ALL_OUTPUTS):
@@ -254,6 +344,8 @@ class FastqPipeline:
                 self.outs[q] = torch.empty(caps[q], dtype=torch.uint8, device=self.dev)
             if self.gz_out[q]:
                 gcap = caps[q] + 31 * (caps[q] // 65280 + 1) + 64
+                if split:   # a segment per pack of the trip, each with a last member and maybe an end-of-file member
+                    gcap += (31 + 28) * (self.max_records // abi.PACK_SIZE + 3)
                 if self.gzbuf[q] is None or self.gzbuf[q].numel() < gcap:
                     self.gzbuf[q] = torch.empty(gcap, dtype=torch.uint8, device=self.dev)
         need = [(self.gzbuf[q].numel() if self.gz_out[q] else caps[q]) if paths[q] else 0 for q in range(abi.N_ALL_OUTPUTS)]
@@ -268,7 +360,8 @@ class FastqPipeline:
     def run(self, in1: str, in2: str | None, out1: str, out2: str | None, failed_out: str | None = None,
             merged_out: str | None = None, unpaired1: str | None = None, unpaired2: str | None = None,
             umi: tuple | None = None, compression_level: int | None = None, overlapped_out: str | None = None,
-            fix_mgi_id: bool = False, adapter_counts: bool = False) -> dict:
+            fix_mgi_id: bool = False, adapter_counts: bool = False, interleaved_out: bool = False, split: tuple | None = None,
+            split_digits: int = 4) -> dict:
         """umi = (location "read1" | "read2" | "per_read", length[, prefix bytes[, delimiter bytes]]): the name edit that goes
         with params.umi_len1/2 (UmiProcessor::addUmiToName); or (location "index1" | "index2" | "per_index", 0[, prefix[,
         delimiter]]): the UMI is the index part of the name, nothing is trimmed.  fix_mgi_id: --fix_mgi_id, a space in front
@@ -277,14 +370,60 @@ class FastqPipeline:
         --overlapped_out's stream, needed when params.overlapped_out is set (a ".gz" path is compressed like the others).
         adapter_counts: FilterResult's adapter-string maps (the report's adapter_cutting.read1_adapter_counts /
         read2_adapter_counts) are counted on the device, per chunk, on the tensors the chunk already holds
-        (fastp_gpu_adapter_census); adapter_counts() returns them"""
+        (fastp_gpu_adapter_census); adapter_counts() returns them.
+        interleaved_out: --stdout of a paired run without merge (src/peprocessor.cpp:577-585): out1 receives both records of a
+        passing pair, read 1's first; out2 must be None.
+        split: ("lines", L) for --split_by_lines L, or ("files", N, reads_per_file) for --split N (reads_per_file: the input's
+        read count / N, the reference's estimate); split_digits: --split_prefix_digits.  out1 / out2 are then the name
+        templates: file k is dirname / (k padded to split_digits) + "." + basename, ".gz" names are compressed and every file
+        ends in bgzip's end-of-file member; as in the reference no other stream is written and merge / interleaved_out are
+        refused (src/threadconfig.cpp:106-157, the same rules as fastp_gpu_stream_set_split); stats["split_files"] = the files
+        opened per stream"""
         self.census = bool(adapter_counts)
         torch = self.torch
         if compression_level is not None and not 0 <= int(compression_level) <= 9:
             raise PipelineError("compression_level is 0 (the default) to 9")
         self.gz_level = None if compression_level is None else int(compression_level)
-        if self.paired != (in2 is not None) or self.paired != (out2 is not None):
+        if interleaved_out:
+            if not self.paired or self.params.merge:
+                raise PipelineError("interleaved_out (--stdout) is the stream of a paired run without merge")
+            if out2 is not None or not out1:
+                raise PipelineError("interleaved_out (--stdout): out1 receives the stream, out2 must be None")
+            if split is not None:
+                raise PipelineError("--split cannot be combined with interleaved_out (--stdout)")
+        if self.paired != (in2 is not None) or (self.paired != (out2 is not None) and not interleaved_out):
             raise PipelineError("paired engine needs in2/out2, single-end engine must not get them")
+        self._split, self._pieces = None, []
+        if split is not None:
+            if self.params.merge:
+                raise PipelineError("--split cannot be combined with --merge")
+            for name, v in (("failed_out", failed_out), ("merged_out", merged_out), ("unpaired1", unpaired1), ("unpaired2", unpaired2),
+                            ("overlapped_out", overlapped_out)):
+                if v:
+                    raise PipelineError(f"--split writes out1 / out2 only: the reference drops {name} in this mode")
+            if not isinstance(split, tuple) or not split or split[0] not in ("lines", "files") or len(split) != (2 if split[0] == "lines" else 3):
+                raise PipelineError('split is ("lines", L) or ("files", N, reads_per_file)')
+            by_lines = split[0] == "lines"
+            if by_lines and (int(split[1]) % 4 or int(split[1]) < 4):
+                raise PipelineError("--split_by_lines: a multiple of 4 lines")
+            size = int(split[1]) // 4 if by_lines else int(split[2])
+            if size < 1:
+                raise PipelineError("--split / --split_by_lines: reads_per_file below 1")
+            if not by_lines and not 2 <= int(split[1]) <= 999:
+                raise PipelineError("--split: number outside 2..999")
+            if not 0 <= int(split_digits) <= 10:
+                raise PipelineError("--split_prefix_digits outside 0..10")
+            if not out1:
+                raise PipelineError("--split: out1 is missing")
+            self._split = dict(by_lines=by_lines, size=size, number=0 if by_lines else int(split[1]), digits=int(split_digits),
+                               out=[out1, out2] if self.paired else [out1], units=0, working=0, current=0, pack_units=0,
+                               pack_passed=0, files=1, max_packs=self.max_records // abi.PACK_SIZE + 2)
+            self._split_w = dict(fd=[-1, -1], pos=[0, 0], open=0)
+            mp = self._split["max_packs"]
+            self._split["cut"] = torch.zeros(2 * (mp + 1), dtype=torch.int64, device=self.dev)
+            self._split["passed"] = torch.zeros(mp, dtype=torch.int32, device=self.dev)
+        if self.paired and not self.params.merge:
+            self.eng.format_interleaved(bool(interleaved_out))
         if self.params.merge and not merged_out:
             raise PipelineError("merge mode needs merged_out")
         if bool(self.params.overlapped_out) != bool(overlapped_out):
@@ -293,7 +432,7 @@ class FastqPipeline:
             raise PipelineError("params trim a UMI off the reads: pass umi=(location, length) for the name edit")
         out_paths = [out1, out2, failed_out, merged_out if self.params.merge else None, unpaired1 if self.paired else None,
                      unpaired2 if self.paired else None, overlapped_out]
-        self._setup_outputs(out_paths, umi, fix_mgi_id)
+        self._setup_outputs(out_paths, umi, fix_mgi_id, bool(interleaved_out), split is not None)
         self.fmt_opts = abi.FormatOptions()
         self.fmt_opts.want_failed = int(bool(failed_out))
         self.fmt_opts.want_unpaired1 = int(bool(out_paths[4]))
@@ -317,7 +456,9 @@ class FastqPipeline:
                         raise PipelineError(f"{p}: gzip but not BGZF - a single deflate stream has no independent blocks; "
                                             "decompress on the host (as the reference does) or recompress with bgzip")
         fin = [open(p, "rb", buffering=0) for p in paths]
-        fout = [open(p, "wb", buffering=0) if p else None for p in out_paths]
+        # (split outputs: out1 / out2 are name templates, the writer opens the files)
+        fout = [open(p, "wb", buffering=0) if p and not (self._split and q < 2) else None for q, p in enumerate(out_paths)]
+        finished = False
         q_free, q_full, q_out, q_done = queue.Queue(), queue.Queue(), queue.Queue(), queue.Queue()
         # a compressed chunk expands ~4-5x: read a quarter of the text budget per trip
         want = [self.chunk // 4 if g else self.chunk for g in gz]
@@ -407,12 +548,12 @@ class FastqPipeline:
                     oslot = out_free.pop(0)
                     t0 = time.perf_counter()
                     for q in range(abi.N_ALL_OUTPUTS):
-                        if fout[q] is not None and lens[q]:
+                        if (fout[q] is not None or (self._split and q < 2)) and lens[q]:
                             src = self.gzbuf[q] if self.gz_out[q] else self.outs[q]
                             self.stage_out[oslot][q][:lens[q]].copy_(src[:lens[q]], non_blocking=True)
                     torch.cuda.synchronize(self.dev)
                     st["t_d2h"] += time.perf_counter() - t0
-                    q_out.put((oslot, lens))
+                    q_out.put((oslot, lens, self._pieces) if self._split else (oslot, lens))
                     st["units"] += n
                     st["chunks"] += 1
                     st["bytes_out"] += sum(lens)
@@ -423,11 +564,19 @@ class FastqPipeline:
                         tail = self.mates[m].text[a:total[m]].clone()
                         self.mates[m].text[:left[m]].copy_(tail)
                     tcarry[m] = left[m]
+            finished = True
         finally:
             q_free.put(None)
             q_out.put(None)
             wr.join()
             rd.join(timeout=5)
+            if self._split:   # (the writer thread has joined: its file state is ours)
+                if finished:
+                    self._split_finish()
+                for fd in self._split_w["fd"]:
+                    if fd >= 0:
+                        os.close(fd)
+                st["split_files"] = self._split["files"]
             for q, f in enumerate(fout):
                 if f is not None and self.gz_out[q]:   # the writer thread has joined: append after its last positional write
                     os.pwrite(f.fileno(), self.EOF_MEMBER, os.fstat(f.fileno()).st_size)
@@ -477,6 +626,12 @@ class FastqPipeline:
             f = abi.FormatIn()
             f.text, f.line_off, f.line_len, f.res = M[m].text.data_ptr(), M[m].loff.data_ptr(), M[m].llen.data_ptr(), M[m].res.data_ptr()
             fi.append(f)
+        sp = self._split
+        if sp:   # the pack table of this trip: where out1 / out2 may change files
+            plan = abi.PackCuts()
+            plan.first_unit, plan.pack_size, plan.max_packs = sp["units"], abi.PACK_SIZE, sp["max_packs"]
+            plan.cut, plan.passed = sp["cut"].data_ptr(), sp["passed"].data_ptr()
+            self.eng.format_pack_cuts(plan)
         # the six streams of the worker loop, or all seven for an --overlapped_out run
         ns = abi.N_ALL_OUTPUTS if self.params.overlapped_out else abi.N_OUTPUTS
         fmt = self.eng.format_all_streams if self.params.overlapped_out else self.eng.format_streams
@@ -496,8 +651,21 @@ class FastqPipeline:
                                     self.ev.data_ptr() if self.ev_cap else None, self.nev.data_ptr() if self.ev_cap else None, self.ev_cap)
             st["t_census"] = st.get("t_census", 0.0) + time.perf_counter() - t0
         t0 = time.perf_counter()
+        if sp:
+            cut = sp["cut"].cpu().numpy().reshape(2, sp["max_packs"] + 1)
+            ranges = self._split_pieces(n, sp["passed"].cpu().numpy())
+            spans = [[(0, 0)] * len(sp["out"]) for _ in ranges]
+            for q in range(len(sp["out"])):
+                seg_off = [int(cut[q][r[2]]) for r in ranges] + [int(cut[q][ranges[-1][3]])]
+                if self.gz_out[q]:   # one call for the trip: a segment per piece, the end-of-file member behind a file that ends
+                    rc, seg_off = self.eng.deflate_bgzf_segments(self.outs[q].data_ptr(), seg_off, [r[1] for r in ranges], self.gz_level or 0,
+                                                                 self.gzbuf[q].data_ptr(), self.gzbuf[q].numel())
+                    lens[q] = seg_off[-1]
+                for k in range(len(ranges)):
+                    spans[k][q] = (seg_off[k], seg_off[k + 1] - seg_off[k])
+            self._pieces = [(r[0], r[1], spans[k]) for k, r in enumerate(ranges)]
         for q in range(abi.N_ALL_OUTPUTS):
-            if self.out_cap[q] and self.gz_out[q]:
+            if self.out_cap[q] and self.gz_out[q] and not (sp and q < 2):
                 rc, lens[q] = self.eng.deflate_bgzf(self.outs[q].data_ptr(), lens[q], self.gzbuf[q].data_ptr(), self.gzbuf[q].numel(),
                                                           level=self.gz_level)
         st["t_deflate"] = st.get("t_deflate", 0.0) + time.perf_counter() - t0

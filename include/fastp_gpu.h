@@ -546,6 +546,44 @@ int fastp_gpu_format_all_streams(fastp_gpu_ctx* ctx, int32_t n, const fastp_gpu_
                                  uint8_t* const out[FASTP_GPU_N_HOST_OUTPUTS], const int64_t out_capacity[FASTP_GPU_N_HOST_OUTPUTS],
                                  int64_t out_len[FASTP_GPU_N_HOST_OUTPUTS] /* host: bytes written (needed) per stream */);
 
+/* --stdout on paired input without merge (src/options.cpp:101-110, 167-180; src/peprocessor.cpp:577-585): a pair whose mates
+ * both pass goes to ONE stream, read 1's record and then read 2's.  A context switch like fastp_gpu_host_writes_overlapped:
+ * while it is on, fastp_gpu_format_streams / _all_streams write such a pair's two records into stream FASTP_GPU_OUT1, in that
+ * order, and stream FASTP_GPU_OUT2 gets no bytes (its buffer may be NULL, out_len[1] is 0).  The routing of failed, unpaired
+ * and overlapped records and --dedup's drops do not change (the reference's do not either).  out1 then needs the "both
+ * mates" bound of fastp_gpu_format_streams' comment without its tags: T1 + T2 + 2 * (sum G + n).
+ * FASTP_GPU_E_INVALID on a single-end or merge context (single-end: out1 is the stream already; merge mode: the merged
+ * stream is what goes to standard output, src/peprocessor.cpp:672-675). */
+int fastp_gpu_format_interleaved(fastp_gpu_ctx* ctx, int on);
+
+/* --split / --split_by_lines (src/threadconfig.cpp:106-157, src/peprocessor.cpp:645-651, src/seprocessor.cpp:298-314): the
+ * reference's worker moves on to the next output file only between two packs of PACK_SIZE units, and after a pack it adds
+ * either the pack's units or the units it wrote to out1 to the file's count.  Both are facts about slices of the unit
+ * sequence that the formatter has in hand.  A plan ARMS THE NEXT fastp_gpu_format_streams / _all_streams call of the
+ * context (that call consumes it, whatever it returns; plan == NULL disarms).  With first_unit the index of that call's
+ * unit 0 in the whole input, the call's n units fall into S = (first_unit + n - 1) / pack_size - first_unit / pack_size + 1
+ * slices (S = 0 for n == 0): slice 0 starts at the call's unit 0, every later one at a unit whose global index is a
+ * multiple of pack_size.  The call writes
+ *     cut[stream * (max_packs + 1) + i], i = 0..S, stream = FASTP_GPU_OUT1 / FASTP_GPU_OUT2:
+ *         the byte offset in the stream's buffer where slice i starts - the bytes of all units before it, whether or not its
+ *         first unit emits anything; entry S closes the table with the stream's length (out_len).  n == 0: the closing
+ *         entry alone, 0.  A single-end context gets zeros for FASTP_GPU_OUT2.
+ *     passed[i], i = 0..S-1: the units of slice i with a record in FASTP_GPU_OUT1 (single-end: seprocessor.cpp:281-286;
+ *         paired: both mates pass and the pair is no dropped duplicate, peprocessor.cpp:577-593)
+ * and nothing past those entries.  When first_unit is a multiple of pack_size the entries are exactly the pack boundaries
+ * inside the call plus the closing one; otherwise entry 0 belongs to the rest of a pack that an earlier call began, so
+ * that its count is not lost.  The offsets are those of buffers large enough: with FASTP_GPU_E_OVERFLOW they are the
+ * needed ones, like out_len.  FASTP_GPU_E_INVALID from the format call when S > max_packs (nothing is formatted).
+ * cut / passed: DEVICE memory, read back by the caller after the (synchronous) format call. */
+typedef struct fastp_gpu_pack_cuts {
+    int64_t first_unit;   /* >= 0 */
+    int32_t pack_size;    /* >= 1; the reference's PACK_SIZE is 1000 (src/common.h:30) */
+    int32_t max_packs;    /* >= 1 */
+    uint64_t* cut;        /* DEVICE [2][max_packs + 1] */
+    uint32_t* passed;     /* DEVICE [max_packs] */
+} fastp_gpu_pack_cuts;
+int fastp_gpu_format_pack_cuts(fastp_gpu_ctx* ctx, const fastp_gpu_pack_cuts* plan /* NULL: off */);
+
 /* ---- FilterResult's adapter-string maps ON THE DEVICE (the adapter census) ---------------------
  * FilterResult::mAdapter1 / mAdapter2 (src/filterresult.cpp:115-180; the report's adapter_cutting.read1_adapter_counts /
  * read2_adapter_counts) kept by the context: every string the worker loop hands to addAdapterTrimmed, with the reference's
@@ -617,6 +655,19 @@ int fastp_gpu_deflate_bgzf(fastp_gpu_ctx* ctx, const uint8_t* text, int64_t nbyt
  * above holds at every level (the stored-block fallback). */
 int fastp_gpu_deflate_bgzf_level(fastp_gpu_ctx* ctx, const uint8_t* text, int64_t nbytes, int write_eof, int level, uint8_t* out,
                                  int64_t out_capacity, int64_t* out_len);
+/* The same for a text that is cut into n_segments pieces which must not share a member - the slices of one trip's out1 that
+ * go to different --split files (src/peprocessor.cpp:645-651): segment i is text[seg_off[i], seg_off[i + 1]).  No member
+ * spans a segment boundary; within a segment the blocks are 65280 bytes from the segment's start on; an empty segment yields
+ * no member; seg_eof[i] != 0 appends the end-of-file member after segment i (an empty one included).  The bytes of segment i,
+ * out[seg_out_off[i], seg_out_off[i + 1]), are exactly what fastp_gpu_deflate_bgzf_level(text + seg_off[i], its length,
+ * seg_eof[i], level, ...) writes for that segment alone.  All segments go through the same rounds of kernel launches (a
+ * round is what is in flight at once), not one set per segment.  seg_off [n_segments + 1, ascending], seg_eof [n_segments, or
+ * NULL: none] and seg_out_off [n_segments + 1] are HOST arrays; text / out DEVICE pointers.  FASTP_GPU_E_OVERFLOW with the
+ * needed size in seg_out_off[n_segments] when out_capacity is too small (nothing is written past it).  With nbytes the sum of
+ * the segments' lengths, nbytes + 31 * (nbytes / 65280 + n_segments) + 28 * n_segments always suffices. */
+int fastp_gpu_deflate_bgzf_segments(fastp_gpu_ctx* ctx, const uint8_t* text, int32_t n_segments, const int64_t* seg_off,
+                                    const uint8_t* seg_eof /* may be NULL */, int level, uint8_t* out, int64_t out_capacity,
+                                    int64_t* seg_out_off);
 
 /* ---- the Evaluator pre-pass ON THE DEVICE ------------------------------
  * The loops of src/evaluator.cpp that scan a prefix of the input before the workers start, run on packed

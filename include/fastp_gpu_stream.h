@@ -127,6 +127,42 @@ int fastp_gpu_stream_overlapped_on_device(const fastp_gpu_stream* s);   /* 1 onc
  * A stream this was never called for takes the environment variable FASTP_GPU_STREAM_ADAPTERS (read at create): "device"
  * (or "1") = on, "host" or unset = the host replay, anything else FASTP_GPU_E_INVALID. */
 int fastp_gpu_stream_set_adapter_census(fastp_gpu_stream* s, int on);
+/* --stdout on paired input without merge (src/options.cpp:101-110, 167-180; src/peprocessor.cpp:577-585): between create and
+ * run, on != 0 sends both records of a passing pair to stream FASTP_GPU_OUT1, read 1's first (fastp_gpu_format_interleaved);
+ * out1's file descriptor or emit callback receives that stream - a caller passes descriptor 1 and compress 0 for --stdout.
+ * Needs paired input, no merge, want[FASTP_GPU_OUT1] set and want[FASTP_GPU_OUT2] clear (the reference has no out2 then);
+ * failed / unpaired / overlapped streams are routed as ever.  out1's buffers grow to both mates' bound.
+ * FASTP_GPU_E_INVALID otherwise, and once fastp_gpu_stream_run has been called.  Single-end --stdout is out1 with
+ * descriptor 1; --merge --stdout without --merged_out (src/peprocessor.cpp:672-675) is want[FASTP_GPU_MERGED] with
+ * descriptor 1: neither needs this call. */
+int fastp_gpu_stream_set_interleaved_output(fastp_gpu_stream* s, int on);
+/* --split / --split_by_lines / --split_prefix_digits (src/main.cpp:359-378, 487-499; src/options.cpp:235-244, 332-348;
+ * src/threadconfig.cpp:106-157; src/peprocessor.cpp:124-135, 197, 645-651, 688-691; src/seprocessor.cpp:298-314), as ONE
+ * worker writes them (-w 1).  Between create and run, on a stream created with want[OUT1] = want[OUT2] = 0: out1 [and out2]
+ * become split outputs.  File k (1-based) of a stream is dirname(out) / (k, zero-padded to `digits` characters; 0: not
+ * padded) + "." + basename(out); out2's files are numbered in step with out1's.  File 1 is open from the start; after every
+ * pack of 1000 units in input order (the last one short or empty) the worker adds the pack's units that went to out1
+ * (by_lines) or all of its units (by number) to the file's count, and once that reaches reads_per_file - in by-number mode
+ * only while fewer than `number` files exist - it opens the next file, even if nothing follows; in by-number mode the files
+ * up to `number` that were never reached are created empty at the end.  reads_per_file is the caller's: lines / 4 for
+ * --split_by_lines, Evaluator::evaluateReadNum's estimate / number (at least 1) for --split.
+ * config.compress[OUT1 / OUT2] makes the files gzip: the slices of a trip go through one fastp_gpu_deflate_bgzf_segments call
+ * per stream, and every file ends in bgzip's end-of-file member.  Files are created with O_CREAT | O_TRUNC, mode 0644.
+ * The reference writes no failed / unpaired / merged / overlapped stream in this mode (initOutput is never called) and
+ * refuses merge and --stdout: FASTP_GPU_E_INVALID, with the option's name in the message, for a merge context, interleaved
+ * output, any such stream wanted, reads_per_file < 1, by-number `number` outside 2..999, `digits` outside 0..10, out1 NULL,
+ * out2 NULL on a paired stream, and once fastp_gpu_stream_run has been called.
+ * stats.bytes_out[OUT1 / OUT2] are the sums over the files; fastp_gpu_stream_split_files the files opened per stream. */
+typedef struct fastp_gpu_stream_split {
+    int32_t by_lines;         /* 1: --split_by_lines, 0: --split                        */
+    int64_t reads_per_file;   /* the reference's split.size                             */
+    int32_t number;           /* --split's N (ignored with by_lines)                    */
+    int32_t digits;           /* --split_prefix_digits                                  */
+    const char* out1;         /* -o                                                     */
+    const char* out2;         /* -O; NULL for single-end                                */
+} fastp_gpu_stream_split;
+int fastp_gpu_stream_set_split(fastp_gpu_stream* s, const fastp_gpu_stream_split* split);
+int32_t fastp_gpu_stream_split_files(const fastp_gpu_stream* s);
 /* Replace a map of a host glue object (fastp_gpu_host.h) with the entries of an adapter census - fastp_gpu_adapter_census_read's
  * arrays: key i is chars[off[i], off[i + 1]), counts[i] its count - so that a host that counted on the device reads the maps
  * through fastp_gpu_host_adapter_entry as before.  What the stream does with config.host at the end of a census run; declared
